@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- SpMV GFLOP/s + achieved HBM GB/s (fp64) on 5-point Poisson, the metric of BASELINE.json.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`, `ms_per_step`, the workload's
+config).  Everything below the timed steps -- the kernel's roofline (replayed and cold), the CG leg, the opt-in plans, the COO
+tile kernel, the N > 1 exchange comparison and configs4 leg, the CPU baselines and their parity gate -- runs only with --full.
+--dump-outputs DIR writes what the last timed step computed, a fixed, seeded sample of y with its global row indices
+(DIR/y.npy, DIR/y_rows.npy, f64; N > 1: one pair per rank, suffixed _rank<r>), before any other leg runs.
 
 A "step" = one pass of the hot path over one batch of synthetic input = one y = A*x with A, x, y resident in HBM:
 cmi.multiply(A, x, y) -> the matrix's plan (cmi_plan_create, once) -> cmi_spmv_csr_plan_f64 -> the kernel the plan chose
@@ -63,6 +69,8 @@ M = 3162  # grid side: 3162^2 = 9 998 244 rows per GPU
 # cmi_hyb_entries_per_row, tools/autotune_hyb.py)
 HYB_WIDTH = 4
 HBM_PEAK_GBPS = 8000.0  # MI355X HBM3E peak (MI355X_MICROARCH.md); ~6300 GB/s is what a copy achieves
+DUMP_ROWS = 1 << 21     # --dump-outputs: rows of y sampled over all ranks (y and its row indices in f64: 32 MB)
+DUMP_SEED = 20240607
 
 
 def parse():
@@ -81,6 +89,11 @@ def parse():
                          "sharded over the N ranks, SpMV with both exchanges + CG (auto: when N == 8)")
     ap.add_argument("--configs4-grid", type=int, default=int(os.environ.get("CMI_BENCH_CONFIGS4_GRID", "10000")),
                     help="grid side of that leg (tests shrink it)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary legs: kernel roofline (replayed and cold), CG, the opt-in plans, the COO tile kernel, "
+                         "N>1 exchange comparison and configs[4], the CPU baselines and their parity gate")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (a fixed, seeded sample of y) as DIR/*.npy")
     ap.add_argument("--probe-peer", action="store_true", help=argparse.SUPPRESS)  # child mode, see peer_probe_child
     return ap.parse_args()
 
@@ -247,6 +260,21 @@ def stencil_expected(torch, cmi, m, n, lo, hi, dev, scale=1.0):
     s = s + term(1, ix < m - 1, -1.0)
     s = s + term(m, i + m < N, -1.0)
     return s
+
+
+def dump_outputs(out_dir, y, lo, rank, world):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- this rank's rows of y = A*x (f64) -- as a
+    fixed, seeded sample of DUMP_ROWS / world rows (all of them when fewer): y.npy and y_rows.npy (global row indices, f64);
+    N > 1: one pair per rank, suffixed _rank<r>.  Same arguments, same rows, same file names."""
+    import numpy as np
+    yh = y.cpu().numpy()
+    n = yh.shape[0]
+    k = min(n, DUMP_ROWS // world)
+    rows = np.arange(n) if k == n else np.sort(np.random.default_rng(DUMP_SEED + rank).choice(n, size=k, replace=False))
+    suffix = "" if world == 1 else f"_rank{rank}"
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"y{suffix}.npy"), yh[rows].astype(np.float64))
+    np.save(os.path.join(out_dir, f"y_rows{suffix}.npy"), (rows + lo).astype(np.float64))
 
 
 def configs4_leg(torch, cmi, dist, args, rank, world, dev, barrier, timed_steps):
@@ -459,6 +487,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:  # before any secondary leg launches anything
+        dump_outputs(args.dump_outputs, y, lo, rank, world)
 
     # ---- N>1: BOTH exchanges are first-class results: the default one (one-sided halo pull where it
     #      validated) carries `value`; the north-star's literal exchange -- RCCL all-gather of the whole x before each
@@ -478,7 +508,7 @@ def main():
         return float(tt.item()) / steps
 
     exchanges = None
-    if dist is not None:
+    if dist is not None and args.full:
         exchanges = {exchange_info["mode"]: {"value": round(2.0 * nnz_global / (elapsed / args.steps) / 1e9, 3), "unit": "GFLOP/s",
                                              "ms_per_step": round(elapsed / args.steps * 1e3, 5), "steps": args.steps,
                                              "values_received_per_rank": exchange_info["values_received_per_rank"],
@@ -508,36 +538,38 @@ def main():
     # so 20 launches after a cold start -- round 1's protocol -- could land 5 % off the average.
     KERNEL_BATCHES = 10
     per_batch = max(20, -(-max(args.steps, 200) // KERNEL_BATCHES))
-    evs = []
-    for _ in range(2 * KERNEL_BATCHES):
-        e = ctypes.c_void_p()
-        cmi.check(lib.cmi_event_create(ctypes.byref(e)))
-        evs.append(e)
     x_kernel = x if world == 1 else sh.x_view
     kernel_only = (lambda: cmi.multiply(Afmt, x_kernel, y))
-    for _ in range(10):  # re-warm: the secondary legs above ran other kernels
-        kernel_only()
-    torch.cuda.synchronize()
-    for bi in range(KERNEL_BATCHES):
-        cmi.check(lib.cmi_event_record(evs[2 * bi], sptr))
-        for _ in range(per_batch):
+    kernel_ms = None
+    if args.full:
+        evs = []
+        for _ in range(2 * KERNEL_BATCHES):
+            e = ctypes.c_void_p()
+            cmi.check(lib.cmi_event_create(ctypes.byref(e)))
+            evs.append(e)
+        for _ in range(10):  # re-warm: the secondary legs above ran other kernels
             kernel_only()
-        cmi.check(lib.cmi_event_record(evs[2 * bi + 1], sptr))
-    ledger += [["roofline_rewarm", 10], ["roofline", KERNEL_BATCHES * per_batch]]
-    batch_ms = []
-    for bi in range(KERNEL_BATCHES):
-        ms = ctypes.c_float()
-        cmi.check(lib.cmi_event_elapsed_ms(evs[2 * bi], evs[2 * bi + 1], ctypes.byref(ms)))
-        batch_ms.append(ms.value / per_batch)
-    for e in evs:
-        cmi.check(lib.cmi_event_destroy(e))
-    kernel_ms = sum(batch_ms) / len(batch_ms)
-    kernel_ms_median = sorted(batch_ms)[len(batch_ms) // 2]
-    kernel_ms_min = min(batch_ms)
-    if dist is not None:
-        t = torch.tensor([kernel_ms, kernel_ms_median, kernel_ms_min], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        kernel_ms, kernel_ms_median, kernel_ms_min = (float(v) for v in t.tolist())
+        torch.cuda.synchronize()
+        for bi in range(KERNEL_BATCHES):
+            cmi.check(lib.cmi_event_record(evs[2 * bi], sptr))
+            for _ in range(per_batch):
+                kernel_only()
+            cmi.check(lib.cmi_event_record(evs[2 * bi + 1], sptr))
+        ledger += [["roofline_rewarm", 10], ["roofline", KERNEL_BATCHES * per_batch]]
+        batch_ms = []
+        for bi in range(KERNEL_BATCHES):
+            ms = ctypes.c_float()
+            cmi.check(lib.cmi_event_elapsed_ms(evs[2 * bi], evs[2 * bi + 1], ctypes.byref(ms)))
+            batch_ms.append(ms.value / per_batch)
+        for e in evs:
+            cmi.check(lib.cmi_event_destroy(e))
+        kernel_ms = sum(batch_ms) / len(batch_ms)
+        kernel_ms_median = sorted(batch_ms)[len(batch_ms) // 2]
+        kernel_ms_min = min(batch_ms)
+        if dist is not None:
+            t = torch.tensor([kernel_ms, kernel_ms_median, kernel_ms_min], dtype=torch.float64, device=dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            kernel_ms, kernel_ms_median, kernel_ms_min = (float(v) for v in t.tolist())
 
     # ---- cold leg (N = 1): the same kernel with nothing of its operands left in any cache ---------------------
     # COLD_SETS distinct copies of (A, x, y) -- 800 MB each for CSR -- multiplied round-robin: between two uses of a line 3 other
@@ -545,7 +577,7 @@ def main():
     # keyed by the arrays' addresses), made and warmed before the timed batches.
     cold = None
     COLD_SETS = 4
-    if world == 1 and os.environ.get("CMI_BENCH_COLD", "1") != "0":
+    if args.full and world == 1 and os.environ.get("CMI_BENCH_COLD", "1") != "0":
         try:
             import copy as _copy
 
@@ -598,7 +630,7 @@ def main():
     # ---- the caller: CG iterations/s on the same matrix (cusp::krylov::cg's loop, cg.inl:80-105; fused device
     #      path, sharded when N>1), with the recurrence residual checked against b - A x at the end -----------
     cg_leg = None
-    if fmt == "csr" and args.cg_iterations > 0:
+    if args.full and fmt == "csr" and args.cg_iterations > 0:
         try:
             b_vec = torch.from_numpy(x_host).to(dev)
             x_sol = torch.zeros(rows_per_rank, dtype=torch.float64, device=dev)
@@ -724,7 +756,7 @@ def main():
         return out, pl
 
     c16 = packed = None
-    if fmt == "csr" and world == 1:
+    if args.full and fmt == "csr" and world == 1:
         try:
             c16, p16 = opt_in_leg("c16")
             if c16.get("granted") and args.cg_iterations > 0:
@@ -757,7 +789,7 @@ def main():
     # ---- N>1: BASELINE.json configs[4]'s literal shape -- poisson5pt(10000, 10000), 1e8 rows, row-block sharded over the
     #      N ranks, inside cusp::krylov::cg -- as a secondary leg (the headline stays weak-scaled: 3162^2 rows per GPU) ----
     configs4 = None
-    if dist is not None and (args.configs4 == "on" or (args.configs4 == "auto" and world == 8)):
+    if args.full and dist is not None and (args.configs4 == "on" or (args.configs4 == "auto" and world == 8)):
         try:
             configs4 = configs4_leg(torch, cmi, dist, args, rank, world, dev, barrier, timed_steps)
         except Exception as e:  # noqa: BLE001
@@ -784,7 +816,6 @@ def main():
         alg_bytes, kname = (cmi.csr_bytes(local_rows, local_nnz) if through_csr else coo_bytes_), "coo"
     else:  # hyb: the ELL part's bytes (x and y once) + the COO part's three streams; one launch (the matrix's HYB plan)
         alg_bytes, kname = cmi.ell_bytes(local_rows, HYB_WIDTH, Afmt.ell.pitch) + 16 * Afmt.coo.num_entries, "hyb"
-    achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
     cfg = cmi.tuning_select({"csr": 0, "ell": 1, "dia": 2, "coo": 3, "hyb": 1}[fmt], cmi.F64, local_rows, N_global,
                             local_nnz if fmt in ("csr", "coo") else local_rows * (HYB_WIDTH if fmt == "hyb" else 5))
     if world == 1 and fmt in ("csr", "coo"):  # what actually ran: the matrix's plan may have turned the table entry into another kernel
@@ -792,9 +823,11 @@ def main():
             cfg = Afmt.plan().config()
         except Exception:  # noqa: BLE001
             pass
-    traffic, traffic_src = pmc_traffic(kname, cfg.kernel if world == 1 and fmt in ("csr", "coo") else None)
+    if args.full:
+        achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
+        traffic, traffic_src = pmc_traffic(kname, cfg.kernel if world == 1 and fmt in ("csr", "coo") else None)
     coo_tile = None
-    if fmt == "coo" and world == 1:
+    if args.full and fmt == "coo" and world == 1:
         # what ran above: the matrix's plan found the entries sorted, built the row offsets they imply and multiplies with the CSR
         # kernel on them (the row indices are not read: 12 instead of 16 bytes per entry) -- `roofline` prices it on COO's 16.
         # Beside it: the COO format's own kernel for sorted entries (coo_tile: reads the row indices, no plan-owned memory).
@@ -840,23 +873,24 @@ def main():
                        "rows_per_gpu": local_rows, "entries_per_gpu": local_nnz,
                        "kernel_config": cfg.as_dict(), "parallelism": f"row-block x{world}",
                        "x_exchange": exchange_info},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
-                         "traffic_source": None if traffic is None else f"{traffic_src}: committed rocprofv3 --pmc summary of this kernel on this matrix and config (separate passes, FETCH_SIZE x2 correction); not collected in this run",
-                         "kernel_avg_ms": round(kernel_ms, 6), "kernel_median_ms": round(kernel_ms_median, 6),
-                         "kernel_min_ms": round(kernel_ms_min, 6),
-                         "kernel_timing": f"{KERNEL_BATCHES} batches x {per_batch} launches, one HIP event pair per batch on the launch stream",
-                         "kernel_avg_over_ms_per_step": round(kernel_ms / ms_per_step, 4),
-                         # the dominant kernel cannot take longer than the step that contains it: checked, not assumed
-                         "kernel_avg_le_step_x1.02": bool(kernel_ms <= ms_per_step * 1.02),
-                         "algorithmic_bytes_per_launch": alg_bytes,
-                         "kernel_gflops": round(2.0 * local_nnz / (kernel_ms * 1e-3) / 1e9, 2)},
             "settle_launches": SETTLE,
         }
         if world == 1:
             line["kernel_launch_ledger"] = ledger  # (phase, launches of the hot path's kernel) in launch order; later legs (CG, opt-in plans) follow
-        line["roofline"]["protocol"] = ("replay: one (A, x, y) multiplied back to back (the reference's protocol); x and part of the streams are served "
-                                        "from the 256 MiB Infinity Cache between launches -- see roofline_cold for the all-from-HBM figure")
+        if args.full:
+            line["roofline"] = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                                "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
+                                "traffic_source": None if traffic is None else f"{traffic_src}: committed rocprofv3 --pmc summary of this kernel on this matrix and config (separate passes, FETCH_SIZE x2 correction); not collected in this run",
+                                "kernel_avg_ms": round(kernel_ms, 6), "kernel_median_ms": round(kernel_ms_median, 6),
+                                "kernel_min_ms": round(kernel_ms_min, 6),
+                                "kernel_timing": f"{KERNEL_BATCHES} batches x {per_batch} launches, one HIP event pair per batch on the launch stream",
+                                "kernel_avg_over_ms_per_step": round(kernel_ms / ms_per_step, 4),
+                                # the dominant kernel cannot take longer than the step that contains it: checked, not assumed
+                                "kernel_avg_le_step_x1.02": bool(kernel_ms <= ms_per_step * 1.02),
+                                "algorithmic_bytes_per_launch": alg_bytes,
+                                "kernel_gflops": round(2.0 * local_nnz / (kernel_ms * 1e-3) / 1e9, 2)}
+            line["roofline"]["protocol"] = ("replay: one (A, x, y) multiplied back to back (the reference's protocol); x and part of the streams are served "
+                                            "from the 256 MiB Infinity Cache between launches -- see roofline_cold for the all-from-HBM figure")
         if cold is not None:
             if "error" in cold:
                 line["roofline_cold"] = cold
@@ -888,11 +922,11 @@ def main():
                                         "priced on the bytes that kernel moves (12 per entry + 20 per row); the COO arrays hold 16 per entry: coo_tile_kernel "
                                         "is the format's own kernel reading them")
             line["roofline"]["coo_algorithmic_bytes_per_launch"] = coo_bytes_
-        if world == 1 and not args.no_cpu_baseline and fmt == "csr":
+        if args.full and world == 1 and not args.no_cpu_baseline and fmt == "csr":
             base, omp = cpu_baseline(cmi, A, x_host, y.cpu().numpy(), args.cpu_seconds)
             line["cpu_baseline"] = base
             line["cpu_baseline_omp"] = omp
-        if not line["roofline"]["kernel_avg_le_step_x1.02"]:
+        if args.full and not line["roofline"]["kernel_avg_le_step_x1.02"]:
             print(f"bench.py: WARNING kernel_avg_ms {kernel_ms:.6f} > 1.02 x ms_per_step {ms_per_step:.6f}: the {args.steps} timed steps ran faster "
                   "than the kernel's average over the 200+ launches behind them (clock / placement drift between the two timed regions)", file=sys.stderr, flush=True)
         print(json.dumps(line), flush=True)

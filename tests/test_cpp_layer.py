@@ -82,6 +82,14 @@ DEVICE_EXAMPLES = ["Solvers_cg", "Gallery_poisson", "Monitors_monitor", "Monitor
                    "Solvers_bicgstab", "Solvers_cr", "Preconditioners_diagonal"]
 
 
+def _examples_env():
+    """The examples run against THIS checkout's libcusp_mi355x.so.  Their RUNPATH ($ORIGIN/../../../cusp-autotuned_amd/lib) only
+    reaches it while oracle/_ref really lies inside the checkout; a prebuilt _ref/ that is a link to another place resolves $ORIGIN
+    there.  LD_LIBRARY_PATH is searched before RUNPATH."""
+    lib = os.path.join(ROOT, "cusp-autotuned_amd", "lib")
+    return dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(p for p in (lib, os.environ.get("LD_LIBRARY_PATH")) if p))
+
+
 def _examples_ready():
     if os.path.isdir("/root/reference/examples"):
         r = subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "examples"], capture_output=True, text=True)
@@ -96,7 +104,7 @@ def test_reference_examples_build_unchanged_and_host_ones_run(cmi):
     if not _examples_ready():
         pytest.skip("reference tree not present and no prebuilt oracle/_ref/examples")
     for e in HOST_EXAMPLES:
-        r = subprocess.run([os.path.join(EXAMPLES, e)], capture_output=True, text=True, timeout=60)
+        r = subprocess.run([os.path.join(EXAMPLES, e)], capture_output=True, text=True, timeout=60, env=_examples_env())
         assert r.returncode == 0, e + r.stderr[-500:]
         first = r.stdout.splitlines()[0]
         if e == "Algorithms_multiply":  # dense 2x2 times [10, 20]: y = [50, 140] (examples/Algorithms/multiply.cu)
@@ -110,7 +118,7 @@ def test_reference_examples_build_unchanged_and_host_ones_run(cmi):
             assert "|z|_1 = 15" in r.stdout and "max(|z_i|) = 12" in r.stdout and r.stdout.count("array1d <2>") == 2, r.stdout
             continue
         assert first == ("sparse matrix <3, 4> with 8 entries" if e.endswith("hyb") else "sparse matrix <4, 3> with 6 entries"), (e, first)
-    coo = subprocess.run([os.path.join(EXAMPLES, "MatrixFormats_coo")], capture_output=True, text=True).stdout.splitlines()
+    coo = subprocess.run([os.path.join(EXAMPLES, "MatrixFormats_coo")], capture_output=True, text=True, env=_examples_env()).stdout.splitlines()
     assert coo[1].split() == ["0", "0", "(10)"] and coo[6].split() == ["3", "2", "(60)"]
 
 
@@ -125,7 +133,7 @@ def test_reference_examples_run_on_device(cmi, tmp_path):
     for e in DEVICE_EXAMPLES:
         if e == "Preconditioners_diagonal":  # reads ./A.mtx (InputOutput_matrix_market WRITES a file of that name: copy the fixture right before)
             shutil.copy(os.path.join(ROOT, "tests", "golden", "ref_data", "examples", "Preconditioners_A.mtx"), os.path.join(str(tmp_path), "A.mtx"))
-        r = subprocess.run([os.path.join(EXAMPLES, e)], capture_output=True, text=True, timeout=120, cwd=tmp_path)
+        r = subprocess.run([os.path.join(EXAMPLES, e)], capture_output=True, text=True, timeout=120, cwd=tmp_path, env=_examples_env())
         assert r.returncode == 0, e + r.stdout[-500:] + r.stderr[-500:]
         outs[e] = r.stdout
     assert "Successfully converged after" in outs["Solvers_cg"]

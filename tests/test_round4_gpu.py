@@ -372,7 +372,7 @@ def test_bench_under_torchrun_n1_agrees_with_the_plain_run(torch_cuda):
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
     s.close()
-    flags = ["--gpus", "1", "--steps", "200", "--warmup", "5", "--no-cpu-baseline", "--cg-iterations", "0"]
+    flags = ["--full", "--gpus", "1", "--steps", "200", "--warmup", "5", "--no-cpu-baseline", "--cg-iterations", "0"]
     env = dict(os.environ, CMI_BENCH_COLD="0")
 
     def line_of(cmd):

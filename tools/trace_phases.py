@@ -3,7 +3,7 @@
 roofline leg, the timed steps and the cold leg all launch the SAME kernel, so `--stats` gives one average for the three; per phase
 the trace must agree with the line's own HIP-event figures (`roofline.kernel_avg_ms`, `roofline_cold.kernel_avg_ms`).
 
-    rocprofv3 --kernel-trace --stats --output-format csv -d out -o bench -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > line.json
+    rocprofv3 --kernel-trace --stats --output-format csv -d out -o bench -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > line.json
     python3 tools/trace_phases.py out/bench_kernel_trace.csv line.json > profiles/rNN_bench_driver_cmd_trace_phases.txt
 """
 import csv
