@@ -17,6 +17,7 @@ KERNEL_AUTO = 0
 CSR_SCALAR, CSR_VECTOR, CSR_STREAM, CSR_STREAM_PIPE, CSR_BALANCED, CSR_STREAM_C16, CSR_STREAM_WAVE, CSR_STREAM_WAVEV, CSR_STREAM_WAVEX = 1, 2, 3, 4, 5, 6, 7, 8, 9
 CSR_STREAM_WAVER, CSR_STREAM_PACKED = 11, 12  # round 4: run-compressed column copy on wave tiles; ... with the values packed beside it (opt-in)
 ELL_ROW, DIA_ROW, COO_SEGMENTED, COO_LANE4, COO_TILE = 10, 20, 30, 31, 32
+CSR_SPMM_ROWS, CSR_SPMM_COLS = 40, 41  # cmi_spmm_csr_*: lane groups per row (row-major blocks) / one lane per row (column-major)
 
 
 class CmiError(RuntimeError):
@@ -116,6 +117,7 @@ def _declare(L):
     L.cmi_tuning_select.argtypes = [c_int, c_int, i64, i64, i64, cfgp]
     for suf in ("f64", "f32"):
         getattr(L, f"cmi_spmv_csr_{suf}").argtypes = [i64, i64, i64, vp, vp, vp, vp, vp, i32, cfgp, vp]
+        getattr(L, f"cmi_spmm_csr_{suf}").argtypes = [i64, i64, i64, vp, vp, vp, i64, vp, i64, i64, vp, i64, i64, i32, cfgp, vp]
         getattr(L, f"cmi_spmv_coo_{suf}").argtypes = [i64, i64, i64, vp, vp, vp, vp, vp, i32, cfgp, vp]
         getattr(L, f"cmi_spmv_ell_{suf}").argtypes = [i64, i64, i64, i64, vp, vp, vp, vp, vp, i32, cfgp, vp]
         getattr(L, f"cmi_spmv_dia_{suf}").argtypes = [i64, i64, i64, i64, vp, vp, vp, vp, i32, cfgp, vp]
@@ -294,6 +296,27 @@ def spmv_csr(num_rows, num_cols, Ap, Aj, Ax, x, y, accumulate=False, cfg=None, s
     fn = getattr(lib(), "cmi_spmv_csr_" + _suffix(y))
     check(fn(num_rows, num_cols, Aj.numel(), _ptr(Ap), _ptr(Aj), _ptr(Ax), _ptr(x), _ptr(y), int(bool(accumulate)),
              _cfg(cfg), _stream(stream)))
+
+
+def spmm_csr(num_rows, num_cols, Ap, Aj, Ax, X, Y, accumulate=False, cfg=None, stream=None):
+    """cmi_spmm_csr_*: Y = A X (or Y += A X) for 2-D tensors X (num_cols x k) and Y (num_rows x k).  Their stride() is
+    passed as the C-ABI's element strides, so transposed views and column slices of wider tensors work as they are."""
+    import torch
+    for t, n in ((Ap, "Ap"), (Aj, "Aj")):
+        _need(t, n, torch.int32)
+    _need(Ax, "Ax", Y.dtype)
+    for t, n in ((X, "X"), (Y, "Y")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise TypeError(f"{n} must be a CUDA/HIP torch tensor (device memory)")
+        if t.dtype != Y.dtype:
+            raise TypeError(f"{n} has dtype {t.dtype}, expected {Y.dtype}")
+        if t.dim() != 2:
+            raise ValueError(f"spmm_csr: {n} must be 2-D")
+    if Ap.numel() != num_rows + 1 or Aj.numel() != Ax.numel() or X.shape[0] != num_cols or Y.shape[0] != num_rows or X.shape[1] != Y.shape[1]:
+        raise ValueError("spmm_csr: array shapes do not match (X num_cols x k, Y num_rows x k)")
+    fn = getattr(lib(), "cmi_spmm_csr_" + _suffix(Y))
+    check(fn(num_rows, num_cols, Aj.numel(), _ptr(Ap), _ptr(Aj), _ptr(Ax), X.shape[1], _ptr(X), X.stride(0), X.stride(1),
+             _ptr(Y), Y.stride(0), Y.stride(1), int(bool(accumulate)), _cfg(cfg), _stream(stream)))
 
 
 class Plan:

@@ -17,11 +17,21 @@
 // temporary_array, which the fork's KTT hook fails to match -- SURVEY.md 3.3; here every vector type
 // reaches the tuned kernels).
 //
+// Dense blocks (SpMM): multiply(A, X, Y) with cusp::array2d X (num_cols x k) and Y (num_rows x k) and a CSR matrix or view
+// computes Y = A X column by column (reference csr_block_spmv.h; dispatch on X's format, section "dense blocks" below):
+//   host_memory   : the reference's sequential loop (sequential/multiply/csr_block_spmv.h), generic in the functors;
+//                   cusp::omp::par splits the rows over threads with the same per-row arithmetic.
+//   device_memory : cmi_spmm_csr_{f64,f32} with the strides of each array2d's orientation and pitch; a one-column block
+//                   with a contiguous column runs the container's planned SpMV (the reference forwards k == 1 the same
+//                   way, cuda/detail/multiply/csr_block_spmv.h:198-201).
+// Other sparse formats with an array2d X, and mixed array1d / array2d arguments, are compile-time errors.
+//
 // Execution policies: multiply(exec, A, x, y) with cusp::hip::par.on(stream) selects the stream.  A
 // user-derived policy reaches a user-provided multiply overload by ADL without being copied
 // (testing/multiply.cu:792-858): see cusp/execution_policy.h.
 #pragma once
 #include <utility>
+#include <vector>
 #include "array1d.h"
 #include "array2d.h"
 #include "convert.h"
@@ -285,6 +295,112 @@ void multiply_in_space(const A &a, const X &x, Y &y, I init, C comb, R red, void
     device_multiply(a, x, y, acc, stream, typename A::format());
 }
 
+// ---- dense blocks: Y = A X with array2d X and Y (SpMM) ------------------------------------------------------
+template <typename T, typename = void> struct is_block : std::false_type {};
+template <typename T> struct is_block<T, typename std::enable_if<std::is_same<typename T::format, array2d_format>::value>::type> : std::true_type {};
+
+// (row stride, column stride) of an array2d in elements: row-major (pitch, 1), column-major (1, pitch)
+template <typename T, typename M> void strides_of(const array2d<T, M, row_major> &a, int64_t *rs, int64_t *cs) { *rs = (int64_t)a.pitch; *cs = 1; }
+template <typename T, typename M> void strides_of(const array2d<T, M, column_major> &a, int64_t *rs, int64_t *cs) { *rs = 1; *cs = (int64_t)a.pitch; }
+
+template <typename A, typename X, typename Y> void check_block_shapes(const A &a, const X &x, const Y &y)
+{
+    if (x.num_rows != a.num_cols || y.num_rows != a.num_rows || x.num_cols != y.num_cols)
+        throw cusp::invalid_input_exception("cusp::multiply: array2d shapes do not match (X must be num_cols x k, Y num_rows x k)");
+}
+
+template <typename A> void require_csr_for_blocks()
+{
+    static_assert(std::is_same<typename A::format, csr_format>::value,
+                  "cusp::multiply(A, X, Y) with array2d X and Y is implemented for CSR matrices only: convert A to a csr_matrix with cusp::convert first");
+}
+
+// sequential/multiply/csr_block_spmv.h: per row, one accumulator per column, the row's entries in storage order.  `parallel`:
+// rows split over OpenMP threads (cusp::omp::par), the same per-row arithmetic.
+template <typename A, typename X, typename Y, typename Init, typename Comb, typename Red>
+void host_block_multiply(const A &a, const X &x, Y &y, Init initialize, Comb combine, Red reduce, bool parallel)
+{
+    typedef typename A::index_type I;
+    typedef typename Y::value_type V;
+    const long long n = static_cast<long long>(a.num_rows);
+    const size_t k = x.num_cols;
+#if defined(_OPENMP)
+#pragma omp parallel for if (parallel)
+#endif
+    for (long long i = 0; i < n; i++) {
+        std::vector<V> acc(k);
+        for (size_t c = 0; c < k; c++) acc[c] = initialize(y(i, c));
+        for (I jj = a.row_offsets[i]; jj < a.row_offsets[i + 1]; jj++) {
+            const I j = a.column_indices[jj];
+            const V aij = a.values[jj];
+            for (size_t c = 0; c < k; c++) acc[c] = reduce(acc[c], combine(aij, x(j, c)));
+        }
+        for (size_t c = 0; c < k; c++) y(i, c) = acc[c];
+    }
+    (void)parallel;
+}
+
+inline int spmm_csr(int64_t r, int64_t c, int64_t n, const int *Ap, const int *Aj, const double *Ax, int64_t k, const double *X, int64_t xrs, int64_t xcs,
+                    double *Y, int64_t yrs, int64_t ycs, int acc, void *s)
+{ return cmi_spmm_csr_f64(r, c, n, Ap, Aj, Ax, k, X, xrs, xcs, Y, yrs, ycs, acc, forced_config(), s); }
+inline int spmm_csr(int64_t r, int64_t c, int64_t n, const int *Ap, const int *Aj, const float *Ax, int64_t k, const float *X, int64_t xrs, int64_t xcs,
+                    float *Y, int64_t yrs, int64_t ycs, int acc, void *s)
+{ return cmi_spmm_csr_f32(r, c, n, Ap, Aj, Ax, k, X, xrs, xcs, Y, yrs, ycs, acc, forced_config(), s); }
+
+// a contiguous device column as the vector device_multiply takes
+template <typename T> struct column_ref {
+    T *p;
+    T *data() const { return p; }
+};
+
+template <typename A, typename X, typename Y> void device_block_multiply(const A &a, const X &x, Y &y, int acc, void *stream)
+{
+    require_int_index<A>();
+    typedef typename Y::value_type V;
+    int64_t xrs, xcs, yrs, ycs;
+    strides_of(x, &xrs, &xcs);
+    strides_of(y, &yrs, &ycs);
+    if (x.num_cols == 1 && (xrs == 1 || x.num_rows <= 1) && (yrs == 1 || y.num_rows <= 1)) { // one contiguous column: the planned SpMV
+        const column_ref<const V> xc{data_of(x)};
+        column_ref<V> yc{const_cast<V *>(data_of(y))};
+        device_multiply(a, xc, yc, acc, stream, csr_format());
+        return;
+    }
+    check(spmm_csr(a.num_rows, a.num_cols, a.num_entries, a.row_offsets.data(), a.column_indices.data(), a.values.data(), (int64_t)x.num_cols,
+                   data_of(x), xrs, xcs, const_cast<V *>(data_of(y)), yrs, ycs, acc, stream));
+}
+
+// the route every public overload takes: vectors -> the SpMV paths above, unchanged; array2d blocks -> SpMM
+template <typename X, typename Y> struct block_route {
+    static_assert(is_block<X>::value == is_block<Y>::value,
+                  "cusp::multiply: x and y must both be vectors (array1d) or both be dense blocks (array2d); mixed array1d / array2d arguments are not supported");
+    typedef std::integral_constant<bool, is_block<X>::value> type;
+};
+
+template <typename A, typename X, typename Y, typename I, typename C, typename R, typename Space>
+void multiply_route(const A &a, const X &x, Y &y, I init, C comb, R red, void *stream, Space, std::false_type)
+{
+    check_shapes(a, x, y);
+    multiply_in_space(a, x, y, init, comb, red, stream, Space());
+}
+template <typename A, typename X, typename Y, typename I, typename C, typename R>
+void multiply_route(const A &a, const X &x, Y &y, I init, C comb, R red, void *, host_memory, std::true_type)
+{
+    require_csr_for_blocks<A>();
+    check_block_shapes(a, x, y);
+    host_block_multiply(a, x, y, init, comb, red, false);
+}
+template <typename A, typename X, typename Y, typename I, typename C, typename R>
+void multiply_route(const A &a, const X &x, Y &y, I init, C comb, R red, void *stream, device_memory, std::true_type)
+{
+    require_csr_for_blocks<A>();
+    check_block_shapes(a, x, y);
+    typedef typename Y::value_type V;
+    const int acc = device_functors<V, I, C, R>::accumulate(init);
+    if (a.num_rows == 0 || x.num_cols == 0) return;
+    device_block_multiply(a, x, y, acc, stream);
+}
+
 } // namespace detail
 
 // ---- public overloads (reference cusp/multiply.h:40,101,113,190) ----------------------------------
@@ -297,8 +413,8 @@ void multiply(const LinearOperator &A, const Vector1 &x, Vector2 &y, UnaryFuncti
     static_assert(std::is_same<typename LinearOperator::memory_space, typename Vector2::memory_space>::value &&
                       std::is_same<typename Vector1::memory_space, typename Vector2::memory_space>::value,
                   "cusp::multiply: A, x and y must live in the same memory space");
-    detail::check_shapes(A, x, y);
-    detail::multiply_in_space(A, x, y, initialize, combine, reduce, nullptr, typename LinearOperator::memory_space());
+    detail::multiply_route(A, x, y, initialize, combine, reduce, nullptr, typename LinearOperator::memory_space(),
+                           typename detail::block_route<Vector1, Vector2>::type());
 }
 
 // y = A*x (initialize = 0, combine = *, reduce = +: generic/multiply.inl:104-110)
@@ -330,8 +446,8 @@ template <typename LinearOperator, typename Vector1, typename Vector2, typename 
 void multiply(const cusp::hip::execution_policy &exec, const LinearOperator &A, const Vector1 &x, Vector2 &y, UnaryFunction initialize,
               BinaryFunction1 combine, BinaryFunction2 reduce)
 {
-    detail::check_shapes(A, x, y);
-    detail::multiply_in_space(A, x, y, initialize, combine, reduce, exec.stream(), typename LinearOperator::memory_space());
+    detail::multiply_route(A, x, y, initialize, combine, reduce, exec.stream(), typename LinearOperator::memory_space(),
+                           typename detail::block_route<Vector1, Vector2>::type());
 }
 template <typename LinearOperator, typename Vector1, typename Vector2>
 void multiply(const cusp::hip::execution_policy &exec, const LinearOperator &A, const Vector1 &x, Vector2 &y)
@@ -361,6 +477,20 @@ void omp_multiply(const A &a, const X &x, Y &y, Init initialize, Comb combine, R
 }
 template <typename A, typename X, typename Y, typename Init, typename Comb, typename Red, typename F>
 void omp_multiply(const A &a, const X &x, Y &y, Init i, Comb c, Red r, F f) { host_dispatch(a, x, y, i, c, r, f); }
+
+template <typename A, typename X, typename Y, typename Init, typename Comb, typename Red>
+void omp_route(const A &a, const X &x, Y &y, Init i, Comb c, Red r, std::false_type)
+{
+    check_shapes(a, x, y);
+    omp_multiply(a, x, y, i, c, r, typename A::format());
+}
+template <typename A, typename X, typename Y, typename Init, typename Comb, typename Red>
+void omp_route(const A &a, const X &x, Y &y, Init i, Comb c, Red r, std::true_type)
+{
+    require_csr_for_blocks<A>();
+    check_block_shapes(a, x, y);
+    host_block_multiply(a, x, y, i, c, r, true);
+}
 } // namespace detail
 
 template <typename LinearOperator, typename Vector1, typename Vector2, typename UnaryFunction, typename BinaryFunction1, typename BinaryFunction2>
@@ -368,8 +498,7 @@ void multiply(const cusp::omp::execution_policy &, const LinearOperator &A, cons
               BinaryFunction1 combine, BinaryFunction2 reduce)
 {
     static_assert(std::is_same<typename LinearOperator::memory_space, host_memory>::value, "cusp::omp::par runs on host_memory containers");
-    detail::check_shapes(A, x, y);
-    detail::omp_multiply(A, x, y, initialize, combine, reduce, typename LinearOperator::format());
+    detail::omp_route(A, x, y, initialize, combine, reduce, typename detail::block_route<Vector1, Vector2>::type());
 }
 template <typename LinearOperator, typename Vector1, typename Vector2>
 void multiply(const cusp::omp::execution_policy &exec, const LinearOperator &A, const Vector1 &x, Vector2 &y)

@@ -183,7 +183,13 @@ def _capturing(stream):
 def multiply(A, x, y, accumulate=False, cfg=None, stream=None):
     """y = A*x (or y += A*x).  Mirrors the 3-argument cusp::multiply (cusp/multiply.h:40).  Without an explicit config
     CSR, COO and HYB matrices multiply through their plan (made once, at the first such call; not while a stream capture is
-    recording -- then the plan-less entry point runs the table's kernel)."""
+    recording -- then the plan-less entry point runs the table's kernel).  A 2-D x (num_cols x k) and y (num_rows x k)
+    with a CsrMatrix: Y = A X through cmi_spmm_csr_* (other formats: TypeError, convert to CSR first)."""
+    if getattr(x, "ndim", 1) == 2:
+        if not isinstance(A, CsrMatrix):
+            raise TypeError(f"multiply: a dense block X (2-D) needs a CSR matrix, got {type(A).__name__}; convert(A, 'csr') first")
+        B.spmm_csr(A.num_rows, A.num_cols, A.row_offsets, A.column_indices, A.values, x, y, accumulate, cfg, stream)
+        return y
     plan = None
     if isinstance(A, (CsrMatrix, CooMatrix)) and cfg is None and A.num_entries > 0:
         plan = A.plan(stream, create=not _capturing(stream))  # an existing plan is used inside a capture, none is made there

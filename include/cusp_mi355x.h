@@ -220,6 +220,13 @@ typedef enum cmi_kernel {
                                boundaries from the row indices, storage-order sums, plain stores of whole
                                runs of y -- no zero fill, no atomics (ref: coo_flat_spmv.h:231-463 needs
                                three launches and two temporaries for the same contract)            */
+    /* CSR x dense block (cmi_spmm_csr_*; ref: csr_block_spmv.h BlockSpmvKernel).  Never in the tuning table: a
+       NULL / AUTO config takes the built-in rule (row-major X -> ROWS, column-major X -> COLS). */
+    CMI_CSR_SPMM_ROWS = 40, /* threads_per_row lanes (1, 2, 4, .., 64) per row, 16 bytes of columns per lane (f64: 2,
+                               f32: 4), a panel of threads_per_row x that many columns per grid row; row-major blocks
+                               with 16-byte aligned rows move one vector per lane, anything else scalar elements */
+    CMI_CSR_SPMM_COLS = 41, /* one lane per row, items_per_thread (8 or 16) columns per register panel: for
+                               column-major X / Y (a wave's consecutive rows touch consecutive addresses)       */
 } cmi_kernel;
 
 typedef struct cmi_config {
@@ -419,6 +426,23 @@ int cmi_spmv_csr_plan_f64(const cmi_plan *plan, const int32_t *Ap, const int32_t
                           const double *x, double *y, int accumulate, void *stream);
 int cmi_spmv_csr_plan_f32(const cmi_plan *plan, const int32_t *Ap, const int32_t *Aj, const float *Ax,
                           const float *x, float *y, int accumulate, void *stream);
+/* Y = A X or Y = Y + A X, X num_cols x k, Y num_rows x k; element (r,c) of X at X[r*x_row_stride + c*x_col_stride]
+ * (one stride of each pair is 1).  Replaces cuda::detail::multiply(csr, array2d, array2d) (csr_block_spmv.h:187-220);
+ * host-order oracle: sequential/multiply/csr_block_spmv.h.  Column c is bit-identical to cmi_spmv_csr_* on column c.
+ * Strides are in elements; row-major with pitch p is (p, 1), column-major (1, p); X and Y may differ.  Rejected with
+ * CMI_ERROR_INVALID_VALUE before any device call: negative sizes, sizes beyond int32, null arrays with non-zero sizes,
+ * a stride pair with no unit stride or whose other stride is below the minor extent, Y overlapping X.  k == 0 or
+ * num_rows == 0: success, nothing launched.  cfg: NULL / AUTO (built-in rule), CMI_CSR_SPMM_ROWS or
+ * CMI_CSR_SPMM_COLS; anything else is CMI_ERROR_NOT_SUPPORTED.  No allocation, no synchronisation.  Callers find
+ * the feature by the symbol (CMI_VERSION is unchanged). */
+int cmi_spmm_csr_f64(int64_t num_rows, int64_t num_cols, int64_t num_entries, const int32_t *Ap, const int32_t *Aj,
+                     const double *Ax, int64_t k, const double *X, int64_t x_row_stride, int64_t x_col_stride,
+                     double *Y, int64_t y_row_stride, int64_t y_col_stride, int accumulate,
+                     const cmi_config *cfg, void *stream);
+int cmi_spmm_csr_f32(int64_t num_rows, int64_t num_cols, int64_t num_entries, const int32_t *Ap, const int32_t *Aj,
+                     const float *Ax, int64_t k, const float *X, int64_t x_row_stride, int64_t x_col_stride,
+                     float *Y, int64_t y_row_stride, int64_t y_col_stride, int accumulate,
+                     const cmi_config *cfg, void *stream);
 /* The same fusion for ELL (ELLR with row_lengths) and DIA: one lane per row owns y[row], so <y, w> costs one  */
 /* extra coalesced read of w and one partial per workgroup.                                                    */
 int cmi_spmv_ell_dot_f64(int64_t num_rows, int64_t num_cols, int64_t num_entries_per_row, int64_t pitch,

@@ -14,6 +14,7 @@
 // GFLOP/s = 2 nnz / t and GB/s with BOTH byte models: the reference's (x counted once per entry, y read
 // and written) and the compulsory one of SURVEY.md 8(d) (every array once).  A format whose fill-in
 // the conversion refuses (format_conversion_exception, as in the reference) is reported and skipped.
+// Then the CSR x dense-block lines csr_block(k), k = 2, 4, 8, 16, 32 (the reference driver's test_spmv_block).
 //
 //   g++ -std=c++17 -O2 -I cusp-autotuned_amd/include tools/spmv_bench.cpp -L cusp-autotuned_amd/lib -lcusp_mi355x -o tools/bin/spmv_bench
 #include <cusp/coo_matrix.h>
@@ -30,6 +31,7 @@
 #include <iostream>
 #include <map>
 #include <string>
+#include <vector>
 
 typedef std::map<std::string, std::string> ArgumentMap;
 static ArgumentMap args;
@@ -123,6 +125,54 @@ void bench_format(const char *name, const HostCsr &host_csr)
     cmi_event_destroy(e1);
 }
 
+// CSR x dense block of k columns (reference benchmark.h:183-200,249 test_spmv_block("csr_block", k, ...)): seeded row-major X,
+// the device multiply against the host cusp::multiply column by column (relative L2 error per column), the same event-timed
+// loop as bench_format; GB/s with the reference's bytes_per_spmv_block (bytes_per_spmv.h:42) and with the compulsory bytes
+// 4 (N + 1) + (4 + s) nnz + s k (num_cols + num_rows).
+template <typename HostCsr> void bench_block(const HostCsr &host_csr, size_t k)
+{
+    typedef typename HostCsr::value_type V;
+    typedef typename HostCsr::index_type I;
+    const size_t M = host_csr.num_rows, N = host_csr.num_cols, nnz = host_csr.num_entries;
+    cusp::array2d<V, cusp::host_memory> hx(N, k), hy(M, k, V(0));
+    for (size_t i = 0; i < N; i++)
+        for (size_t c = 0; c < k; c++) hx(i, c) = V(int((i * 7 + c * 13) % 21) - 10);
+    cusp::csr_matrix<I, V, cusp::device_memory> dev(host_csr);
+    cusp::array2d<V, cusp::device_memory> dx(hx), dy(hy);
+    cusp::multiply(host_csr, hx, hy);
+    cusp::multiply(dev, dx, dy);
+    cusp::array2d<V, cusp::host_memory> back(dy);
+    double err = 0;
+    std::vector<V> a(M), b(M);
+    for (size_t c = 0; c < k; c++) {
+        for (size_t i = 0; i < M; i++) { a[i] = back(i, c); b[i] = hy(i, c); }
+        err = std::max(err, l2_error(M, a.data(), b.data()));
+    }
+    void *e0, *e1;
+    cusp::detail::check(cmi_event_create(&e0));
+    cusp::detail::check(cmi_event_create(&e1));
+    float ms = 0;
+    cusp::detail::check(cmi_event_record(e0, nullptr));
+    cusp::multiply(dev, dx, dy);
+    cusp::detail::check(cmi_event_record(e1, nullptr));
+    cusp::detail::check(cmi_event_elapsed_ms(e0, e1, &ms));
+    const double estimated = ms / 1e3;
+    int iters = estimated <= 0 ? 500 : (int)std::min(500.0, std::max(100.0, 3.0 / estimated));
+    cusp::detail::check(cmi_event_record(e0, nullptr));
+    for (int i = 0; i < iters; i++) cusp::multiply(dev, dx, dy);
+    cusp::detail::check(cmi_event_record(e1, nullptr));
+    cusp::detail::check(cmi_event_elapsed_ms(e0, e1, &ms));
+    const double sec = ms / 1e3 / iters;
+    const double ref_bytes = 2.0 * sizeof(I) * M + sizeof(I) * (double)nnz + (k + 1.0) * sizeof(V) * nnz + (k + 1.0) * sizeof(V) * M;
+    const double min_bytes = sizeof(I) * (M + 1.0) + (sizeof(I) + sizeof(V)) * (double)nnz + sizeof(V) * (double)k * (N + M);
+    char name[32];
+    std::snprintf(name, sizeof(name), "csr_block(%zu)", k);
+    std::printf("\t%-14s: %9.4f ms  %8.2f GFLOP/s  %8.2f GB/s (reference byte model)  %8.2f GB/s (compulsory bytes)  [L2 error %.3e]%s\n",
+                name, sec * 1e3, 2.0 * k * nnz / sec / 1e9, ref_bytes / sec / 1e9, min_bytes / sec / 1e9, err, err > 1e-10 ? "  *** RESULT MISMATCH ***" : "");
+    cmi_event_destroy(e0);
+    cmi_event_destroy(e1);
+}
+
 template <typename I, typename V> int test_all_formats(const std::string &filename)
 {
     int ndev = 0;
@@ -152,6 +202,7 @@ template <typename I, typename V> int test_all_formats(const std::string &filena
     bench_format<cusp::dia_matrix<I, V, cusp::host_memory>, cusp::dia_matrix<I, V, cusp::device_memory>>("dia", host_matrix);
     bench_format<cusp::ell_matrix<I, V, cusp::host_memory>, cusp::ell_matrix<I, V, cusp::device_memory>>("ell", host_matrix);
     bench_format<cusp::hyb_matrix<I, V, cusp::host_memory>, cusp::hyb_matrix<I, V, cusp::device_memory>>("hyb", host_matrix);
+    for (size_t k : {2, 4, 8, 16, 32}) bench_block(host_matrix, k); // benchmark.h:249
     return 0;
 }
 
