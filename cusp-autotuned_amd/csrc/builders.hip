@@ -198,8 +198,10 @@ template <typename T>
 static int poisson_csr(int64_t m, int64_t n, int64_t rb, int64_t re, int *Ap, int *Aj, T *Ax, void *stream)
 {
     if (m < 1 || n < 1 || rb < 0 || re < rb || re > m * n) return fail(CMI_ERROR_INVALID_VALUE, "cmi_poisson5pt_csr: bad grid or row range");
-    if (m * n > INT32_MAX || cmi_poisson5pt_shard_entries(m, n, rb, re) > INT32_MAX)
-        return fail(CMI_ERROR_INVALID_VALUE, "cmi_poisson5pt_csr: sizes exceed the int32 index type");
+    if (m * n > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "cmi_poisson5pt_csr: sizes exceed the int32 index type");
+    // no shard the CSR multiplies would refuse: they take at most INT32_MAX - 65536 entries ("int32 index ceiling")
+    if (cmi_poisson5pt_shard_entries(m, n, rb, re) > INT32_MAX - 65536)
+        return fail(CMI_ERROR_INVALID_VALUE, "cmi_poisson5pt_csr: more than INT32_MAX - 65536 entries (the CSR kernels' ceiling)");
     if (!Ap || (re > rb && (!Aj || !Ax))) return fail(CMI_ERROR_INVALID_VALUE, "cmi_poisson5pt_csr: null array");
     hipLaunchKernelGGL((poisson_csr_kernel<T>), dim3(grid_1d(re - rb + 1)), dim3(256), 0, as_stream(stream), m, n, rb, re, Ap, Aj, Ax);
     CMI_LAUNCH_CHECK("poisson5pt csr");

@@ -397,6 +397,10 @@ static int plan_create(int format, int dtype, int64_t num_rows, int64_t num_cols
         return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_create: bad format or value type");
     if (num_rows < 0 || num_cols < 0 || num_entries < 0) return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_create: negative size");
     if (num_rows > INT32_MAX || num_cols > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_create: sizes exceed the int32 index type");
+    // a CSR plan is for cmi_spmv_csr_* / cmi_spmm_csr_*, which take at most INT32_MAX - 65536 entries ("int32 index
+    // ceiling"): refused here rather than by the first multiply
+    if (format == CMI_FORMAT_CSR && num_entries > INT32_MAX - 65536)
+        return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_create: more than INT32_MAX - 65536 CSR entries (the CSR kernels' ceiling)");
     const bool indexed = format == CMI_FORMAT_CSR || format == CMI_FORMAT_COO;
     if (indexed && !index_array && (format == CMI_FORMAT_CSR ? num_rows > 0 : num_entries > 0))
         return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_create: CSR / COO plans need the row offsets / row indices");

@@ -435,6 +435,11 @@ static int spmv_coo(int dtype, int64_t rows, int64_t cols, int64_t nnz, const in
     if (rows < 0 || cols < 0 || nnz < 0) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_coo: negative size");
     if (rows > INT32_MAX || cols > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_coo: sizes exceed the int32 index type");
     if (rows == 0) return CMI_SUCCESS;
+    // the tile kernel's ceiling (its entry positions are int), checked before the arrays when a plan-less call asks for it; a plan's
+    // choice meets the same check below
+    if (!plan && user && user->kernel == CMI_COO_TILE && nnz > INT32_MAX - 4096 && reinterpret_cast<uintptr_t>(Ai) % 16 == 0 &&
+        reinterpret_cast<uintptr_t>(Aj) % 16 == 0 && reinterpret_cast<uintptr_t>(Ax) % 16 == 0)
+        return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_coo: too many entries for the tile kernel");
     if (!y || (nnz > 0 && (!Ai || !Aj || !Ax || !x))) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_coo: null array");
     if (plan && plan->coo_csr_plan) { // sorted entries: the plan's row offsets + the CSR kernels (the row indices are not read)
         if constexpr (std::is_same<T, double>::value) return cmi_spmv_csr_plan_f64(plan->coo_csr_plan, plan->coo_offsets, Aj, Ax, x, y, accumulate, stream);

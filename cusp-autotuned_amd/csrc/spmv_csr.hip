@@ -1423,6 +1423,10 @@ static int spmv_csr(int dtype, int64_t rows, int64_t cols, int64_t nnz, const in
     // left in dot_partial, or 0 when the selected kernel cannot fuse it (the caller then runs a plain dot).
     if (dot_partials) *dot_partials = 0;
     if (rows < 0 || cols < 0 || nnz < 0) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_csr: negative size");
+    // The ceiling: nnz <= INT32_MAX - 65536.  Every kernel keeps entry positions in int; the largest any lane forms is the last
+    // entry plus one tile (csr_stream: 1024 x 4 x 4 = 16384; its long-row path: block x 4 = 4096; wave tiles: 64 x 10; wavev /
+    // wavex: 64 x 16; csr_balanced: int64), and the loop increments that leave a loop add at most one tile: all < 65536 past nz1.
+    // Audit table and what tests/test_index_ceiling_gpu.py runs at the ceiling: DESIGN.md section 10.
     if (rows > INT32_MAX || cols > INT32_MAX || nnz > INT32_MAX - 65536)
         return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_csr: sizes exceed the int32 index type");
     if (rows == 0) return CMI_SUCCESS;

@@ -371,7 +371,12 @@ csr_stream16_kernel(int64_t num_rows, int64_t num_entries, int num_cols, const i
         const int e = fbase + (k * block + tid) * 4;
         if (e < nz1) {
             const ushort4v u = ld<NT>(reinterpret_cast<const ushort4v *>(Aj16 + e)); // (allocation padded: always inside)
-            c[k][0] = base + (int)u.x; c[k][1] = base + (int)u.y; c[k][2] = base + (int)u.z; c[k][3] = base + (int)u.w;
+            // Up to three leading entries belong to the previous tile and hold offsets against ITS base (up to 65535): clamped
+            // BEFORE the add (0 <= base <= cmax), so a tile whose base lies within 65535 of INT32_MAX cannot wrap the sum negative
+            c[k][0] = (int)u.x > cmax - base ? cmax : base + (int)u.x;
+            c[k][1] = (int)u.y > cmax - base ? cmax : base + (int)u.y;
+            c[k][2] = (int)u.z > cmax - base ? cmax : base + (int)u.z;
+            c[k][3] = (int)u.w > cmax - base ? cmax : base + (int)u.w;
             if ((int64_t)e + 4 <= num_entries) {
                 if constexpr (sizeof(T) == 8) {
                     const double2v v01 = ld<NT>(reinterpret_cast<const double2v *>(Ax + e));
@@ -397,9 +402,7 @@ csr_stream16_kernel(int64_t num_rows, int64_t num_entries, int num_cols, const i
             T xv[4];
 #pragma unroll
             for (int i = 0; i < 4; i++) {
-                int col = c[k][i];
-                col = col > cmax ? cmax : col; // (base >= 0 and the offset is unsigned: never negative)
-                xv[i] = x[col];
+                xv[i] = x[c[k][i]]; // (clamped into [0, cols) when formed)
             }
 #pragma unroll
             for (int i = 0; i < 4; i++) prod[slot + i] = v[k][i] * xv[i];

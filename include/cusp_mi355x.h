@@ -414,7 +414,9 @@ int cmi_plan_info(const cmi_plan *plan, int64_t *max_row_length, int64_t *entrie
 
 /* Replaces cuda::detail::multiply(csr) (csr_vector_spmv.h:225-258), spmv_csr_scalar
  * (csr_scalar.h:82-109) and the KTT csr_spmv kernel (ktt/kernels/csr_kernel.h:378-410).
- * Host-order oracle: sequential/multiply/csr_spmv.h:42-74. */
+ * Host-order oracle: sequential/multiply/csr_spmv.h:42-74.
+ * Sizes: num_rows, num_cols <= INT32_MAX and num_entries <= INT32_MAX - 65536 (the CSR ceiling, also that of cmi_spmm_csr_*,
+ * of CSR plans and of cmi_poisson5pt_csr_*); larger sizes are refused with CMI_ERROR_INVALID_VALUE before any device call. */
 int cmi_spmv_csr_f64(int64_t num_rows, int64_t num_cols, int64_t num_entries, const int32_t *Ap,
                      const int32_t *Aj, const double *Ax, const double *x, double *y, int accumulate,
                      const cmi_config *cfg, void *stream);
@@ -510,7 +512,10 @@ int cmi_spmv_dia_f32(int64_t num_rows, int64_t num_cols, int64_t num_diagonals, 
  * reduce_by_key fallback that device COO actually runs on modern Thrust
  * (generic/multiply/spmv.h:185-238) and the KTT coo_spmv composite (ktt/kernels/coo_kernel.h:372-392).
  * Entries may be in any order (sorted by row is fastest).  No scratch allocation.
- * Oracle: sequential/multiply/coo_spmv.h:42-68. */
+ * Oracle: sequential/multiply/coo_spmv.h:42-68.
+ * Sizes: num_rows, num_cols <= INT32_MAX; num_entries is int64 and CMI_COO_SEGMENTED / CMI_COO_LANE4 (and the default choice)
+ * are exact past 2^31 entries.  CMI_COO_TILE takes at most INT32_MAX - 4096 entries and refuses more with
+ * CMI_ERROR_INVALID_VALUE. */
 int cmi_spmv_coo_f64(int64_t num_rows, int64_t num_cols, int64_t num_entries, const int32_t *Ai,
                      const int32_t *Aj, const double *Ax, const double *x, double *y, int accumulate,
                      const cmi_config *cfg, void *stream);
@@ -687,6 +692,7 @@ int cmi_ell_row_lengths(int64_t num_rows, int64_t width, int64_t pitch, const in
 
 /* ------------------------------------------------------------------------- */
 /* BLAS-1 on device vectors (f64 and f32): the routines cusp::krylov::cg calls */
+/* n is int64 and every index inside is int64: exact past 2^31 elements.       */
 /* (cusp/krylov/detail/cg.inl:63-105; generic/blas.h:175-220,283-340).          */
 /* dot / nrm2 write their scalar to a DEVICE double (*result_dev) without a     */
 /* host sync; the caller copies it back when it needs the value.                */

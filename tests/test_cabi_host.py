@@ -176,6 +176,83 @@ def test_argument_validation_of_the_newer_entry_points(cmi):
     assert L.cmi_spmv_csr_dot_plan_partials_f64(None, None, None, None, None, None, None, None, None, None) == 1   # null plan
 
 
+CSR_CEILING = 2**31 - 1 - 65536  # the most entries any CSR multiply takes ("int32 index ceiling")
+
+
+def test_csr_entry_ceiling_is_refused_before_touching_the_gpu(cmi):
+    """Every CSR / SpMM entry point and every CSR plan constructor refuses one entry past the ceiling with
+    CMI_ERROR_INVALID_VALUE and a message; at the ceiling itself the size check passes and the null arrays are what is
+    refused.  Null pointers throughout: nothing here reaches a device."""
+    L = cmi.lib()
+    h = ctypes.create_string_buffer(64)  # a non-null host address for arrays checked before the sizes: never touched
+    p = ctypes.cast(h, ctypes.c_void_p)
+    rows = 2**26
+    for nnz, over in ((CSR_CEILING + 1, True), (CSR_CEILING, False), (2**31 - 1, True), (2**31, True)):
+        for suf in ("f64", "f32"):
+            calls = {
+                "cmi_spmv_csr": lambda: getattr(L, "cmi_spmv_csr_" + suf)(rows, rows, nnz, None, None, None, None, None, 0, None, None),
+                "cmi_spmv_csr_dot": lambda: getattr(L, "cmi_spmv_csr_dot_" + suf)(rows, rows, nnz, None, None, None, None, None, p, p, p, None, None),
+                "cmi_spmm_csr": lambda: getattr(L, "cmi_spmm_csr_" + suf)(rows, rows, nnz, None, None, None, 2, None, 2, 1, None, 2, 1, 0, None, None),
+            }
+            for name, call in calls.items():
+                assert call() == 1, (name, suf, nnz)
+                msg = L.cmi_last_error()
+                if over:
+                    assert b"exceed" in msg, (name, suf, nnz, msg)
+                else:
+                    assert b"null" in msg, (name, suf, nnz, msg)
+        code = cmi.F64
+        out = ctypes.c_void_p()
+        plans = {
+            "cmi_plan_create": lambda: L.cmi_plan_create(cmi.FORMAT_CSR, code, rows, rows, nnz, None, None, None, ctypes.byref(out)),
+            "cmi_plan_create_csr": lambda: L.cmi_plan_create_csr(code, rows, rows, nnz, None, p, None, None, ctypes.byref(out)),
+            "cmi_plan_create_csr_values": lambda: L.cmi_plan_create_csr_values(code, rows, rows, nnz, None, p, p, None, None, ctypes.byref(out)),
+        }
+        for name, call in plans.items():
+            assert call() == 1 and not out.value, (name, nnz)
+            msg = L.cmi_last_error()
+            assert (b"INT32_MAX - 65536" in msg) == over and (over or b"row offsets" in msg), (name, nnz, msg)
+    # a COO plan is not bound by the CSR ceiling (its plan-less kernels take int64 positions): only its null row indices are refused
+    out = ctypes.c_void_p()
+    assert L.cmi_plan_create(cmi.FORMAT_COO, cmi.F32, rows, rows, CSR_CEILING + 1, None, None, None, ctypes.byref(out)) == 1
+    assert b"row indices" in L.cmi_last_error()
+
+
+def test_coo_tile_ceiling_and_int64_coo_sizes(cmi):
+    """The row-sorted COO tile kernel takes at most INT32_MAX - 4096 entries; the plan-less COO kernels take int64 positions,
+    so past 2^31 entries only the null arrays are refused.  (Null pointers count as 16-byte aligned: the tile kernel's case.)"""
+    L = cmi.lib()
+    tile = cmi.Config(kernel=cmi.COO_TILE)
+    for suf in ("f64", "f32"):
+        fn = getattr(L, "cmi_spmv_coo_" + suf)
+        for nnz, over in ((2**31 - 1 - 4096, False), (2**31 - 1 - 4095, True), (2**31 + 4099, True)):
+            assert fn(2**20, 2**20, nnz, None, None, None, None, None, 0, ctypes.byref(tile), None) == 1
+            assert (b"too many entries for the tile kernel" in L.cmi_last_error()) == over, (suf, nnz)
+            if not over:
+                assert b"null" in L.cmi_last_error()
+        for kern in (cmi.COO_LANE4, cmi.COO_SEGMENTED, None):  # int64 positions: only the null arrays are refused
+            cfg = None if kern is None else ctypes.byref(cmi.Config(kernel=kern))
+            assert fn(2**20, 2**20, 2**31 + 4099, None, None, None, None, None, 0, cfg, None) == 1 and b"null" in L.cmi_last_error()
+        assert fn(2**31, 4, 8, None, None, None, None, None, 0, None, None) == 1 and b"exceed" in L.cmi_last_error()
+
+
+def test_poisson_csr_builder_stays_under_the_csr_ceiling(cmi):
+    """cmi_poisson5pt_csr builds no matrix that the CSR multiplies would refuse: 20724^2 (2 147 337 984 entries, the largest square
+    grid under the ceiling) passes the size check; 20724 x 20725 has fewer than INT32_MAX entries but more than the ceiling and is
+    refused."""
+    L = cmi.lib()
+    assert cmi.poisson5pt_num_entries(20724, 20724) == 2147337984 <= CSR_CEILING
+    assert CSR_CEILING < cmi.poisson5pt_num_entries(20724, 20725) == 2147441602 <= 2**31 - 1
+    for suf in ("f64", "f32"):
+        fn = getattr(L, "cmi_poisson5pt_csr_" + suf)
+        n = 20724**2
+        assert fn(20724, 20724, 0, n, None, None, None, None) == 1 and b"null" in L.cmi_last_error()
+        n = 20724 * 20725
+        assert fn(20724, 20725, 0, n, None, None, None, None) == 1 and b"INT32_MAX - 65536" in L.cmi_last_error()
+        # a shard of that grid under the ceiling is still built (row-range shards are how such a grid is distributed)
+        assert fn(20724, 20725, 0, n // 2, None, None, None, None) == 1 and b"null" in L.cmi_last_error()
+
+
 def test_python_plumbing_refuses_host_tensors(cmi):
     import torch
     t = torch.zeros(4, dtype=torch.float64)

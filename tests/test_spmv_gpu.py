@@ -1117,7 +1117,8 @@ def test_full_size_properties(cmi, torch_cuda, big):
 
 # ------------------------------------------------------------------------------------------------
 # BASELINE.json configs[4] size on ONE device: poisson5pt 10000 x 10000 (N = 1e8, nnz = 499 960 000) -- value arrays
-# of 4 GB, i.e. byte offsets beyond 2^32 and entry positions near the int32 limit, in every format and kernel.
+# of 4 GB, i.e. byte offsets beyond 2^32 in every format and kernel.  Its entry positions reach about 2^29, a quarter
+# of the int32 ceiling: the ceiling itself (INT32_MAX - 65536 entries) is tested in test_index_ceiling_gpu.py.
 # Checked against the stencil's closed form (bench.stencil_expected: bit-identical to the oracle, tests/
 # test_bench_helpers.py) so that no 1e8-row host oracle run is needed.
 # ------------------------------------------------------------------------------------------------
