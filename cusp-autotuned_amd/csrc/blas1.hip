@@ -10,14 +10,13 @@
 // index order and writes the scalar to device memory -- no host sync, no atomics, no per-call
 // allocation (the reference's Thrust reductions allocate temporaries and synchronise every call).
 #include "common.h"
-#include <cstdlib>
 
 namespace cmi {
 
 constexpr int kBlasBlock = 256;
-constexpr int kCgStorePolicy = 1; // x with the nt hint; see cg_store_policy() and the note in cg_update_kernel
+constexpr int kCgStorePolicy = 1; // which vectors a CG step stores with the nt hint (bit 0 x, bit 1 p, bit 2 r): x; see the note in cg_update_kernel
 constexpr int kBlasMaxGrid = kCus * 8;   // reductions: 2048 partials
-constexpr int kFusedMaxGrid = 1 << 16;           // fused update+reduce kernels store too: near one-shot grids (65536 partials; the workspace holds kPartialCapacity)
+constexpr int kFusedMaxGrid = 1 << 16;           // fused update+reduce kernels store too: near one-shot grids (one partial per workgroup; the folds take up to kPartialCapacity)
 
 // reductions: a fixed, capped grid (one partial per workgroup, deterministic tree)
 static int blas_grid(int64_t n, int per_thread)
@@ -116,7 +115,7 @@ dot_partial_kernel(int64_t n, const T *__restrict__ x, const T *__restrict__ y, 
     if (blockIdx.x == 0 && threadIdx.x == 0) reset_fold_state(partial);
 }
 
-// Long partial lists (one-shot fused kernels leave up to 65536 of them) are folded by several
+// Long partial lists (up to kPartialCapacity = 131072 of them) are folded by several
 // workgroups -- workgroup g folds partial[g*kFoldChunk, (g+1)*kFoldChunk) into folded[g] -- and the
 // LAST workgroup to finish (a ticket counter) folds `folded` in index order and writes the scalar:
 // one launch, and still a fixed summation tree whichever workgroup happens to be last.  The ticket
@@ -125,34 +124,28 @@ dot_partial_kernel(int64_t n, const T *__restrict__ x, const T *__restrict__ y, 
 constexpr int kFoldDirect = 2048; // up to here one workgroup folds the list directly
 
 // Hand-off of one chunk sum to whichever workgroup arrives last (thread 0 of every folding workgroup calls it; returns true in
-// the last arriver).  Default: the memory model's own recipe -- payload store, agent-scope RELEASE fence (buffer_wbl2 sc1, waited
-// for: the inline-asm wait is the one the compiler may not drop, MI355X_MICROARCH.md "Compiler hazard"), relaxed ticket add; the
-// last arriver follows its add with an agent-scope ACQUIRE fence (buffer_inv sc1, waited for before the workgroup barrier that
-// lets its other waves read).  `relaxed` != 0 ($CMI_FOLD_RELAXED=1): the fence-free form of round 2 -- write-through (sc1) payload
-// store drained by s_waitcnt vmcnt(0), relaxed ticket add, sc1 loads by the last arriver -- a form the guide lists as measured-valid
-// on gfx950 (inter-workgroup visibility table, first row) but which the memory model does not order; kept for measurements.
-__device__ __forceinline__ bool fold_handoff(double *folded_slot, double s, unsigned int *ticket, unsigned int groups, int relaxed)
+// the last arriver): the memory model's own recipe -- payload store, agent-scope RELEASE fence (buffer_wbl2 sc1, waited for: the
+// inline-asm wait is the one the compiler may not drop, MI355X_MICROARCH.md "Compiler hazard"), relaxed ticket add; the last
+// arriver follows its add with an agent-scope ACQUIRE fence (buffer_inv sc1, waited for before the workgroup barrier that lets its
+// other waves read).  The fences cost 1.5 us per CG iteration against round 2's fence-free form, which the memory model does not
+// order (profiles/r03_cg_bench_{fenced,relaxed}_folds.txt).
+__device__ __forceinline__ bool fold_handoff(double *folded_slot, double s, unsigned int *ticket, unsigned int groups)
 {
     __hip_atomic_store(folded_slot, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (!relaxed) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const unsigned int t = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const bool last = t == groups - 1;
-    if (last && !relaxed) {
+    if (last) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     return last;
 }
-static int fold_relaxed()
-{
-    static const int env = [] { const char *e = std::getenv("CMI_FOLD_RELAXED"); return (e && e[0] == '1') ? 1 : 0; }();
-    return env;
-}
 
 template <typename T>
 __global__ void __launch_bounds__(kBlasBlock)
-dot_fold_final_kernel(int npartial, double *__restrict__ workspace, T *__restrict__ result, double *__restrict__ mirror, int take_sqrt, int relaxed)
+dot_fold_final_kernel(int npartial, double *__restrict__ workspace, T *__restrict__ result, double *__restrict__ mirror, int take_sqrt)
 {
     __shared__ double slots[kBlasBlock / kWave];
     __shared__ int is_last;
@@ -173,7 +166,7 @@ dot_fold_final_kernel(int npartial, double *__restrict__ workspace, T *__restric
 #pragma unroll
     for (int k = 0; k < 4; k++) acc += v[k];
     double s = block_sum(acc, slots);
-    if (threadIdx.x == 0) is_last = fold_handoff(folded + blockIdx.x, s, ticket_of(workspace), gridDim.x, relaxed); // (at most 64 workgroups)
+    if (threadIdx.x == 0) is_last = fold_handoff(folded + blockIdx.x, s, ticket_of(workspace), gridDim.x); // (at most kFoldedMax workgroups)
     __syncthreads();
     if (!is_last) return;
     acc = 0.0;
@@ -210,7 +203,7 @@ static void reduce_partials(int npartial, double *workspace, T *result, int take
 {
     if (npartial > kFoldDirect) {
         const int groups = (npartial + kFoldChunk - 1) / kFoldChunk;
-        hipLaunchKernelGGL((dot_fold_final_kernel<T>), dim3(groups), dim3(kBlasBlock), 0, s, npartial, workspace, result, mirror, take_sqrt, fold_relaxed());
+        hipLaunchKernelGGL((dot_fold_final_kernel<T>), dim3(groups), dim3(kBlasBlock), 0, s, npartial, workspace, result, mirror, take_sqrt);
     } else {
         hipLaunchKernelGGL((dot_final_mirror_kernel<T>), dim3(1), dim3(kBlasBlock), 0, s, npartial, (const double *)workspace, result, mirror, take_sqrt);
     }
@@ -341,7 +334,7 @@ cg_direction_kernel(int64_t n, const double *__restrict__ rr_new, const double *
 // ---------------------------------------------------------------------------------------------
 // A fused CG iteration had two one-workgroup-deep reductions between its three big kernels: 2 x (a 4.6 us fold kernel + a
 // launch gap).  Here the kernel that NEEDS the scalar folds the list itself: its first G workgroups (G = one per 1024
-// partials, <= 64; they are dispatched first) fold their chunks exactly as dot_fold_final_kernel does -- same tree, same
+// partials, <= kFoldedMax; they are dispatched first) fold their chunks exactly as dot_fold_final_kernel does -- same tree, same
 // hand-off -- and the last of them to arrive publishes the sum in kScalarCopies slots (a single 8-byte store each: the value
 // IS the flag; "pending" is a NaN payload no sum produces).  Every workgroup requests its vectors first, then one lane polls
 // its slot (sc1 load, sleeping in between; the producer kernel left the slots pending) -- for all but the first ~2000
@@ -353,7 +346,7 @@ cg_direction_kernel(int64_t n, const double *__restrict__ rr_new, const double *
 constexpr int kFoldSpinLimit = 1 << 15; // x ~0.5 us of s_sleep
 
 __device__ __forceinline__ double fold_ahead(int npartial, double *area, double *result_out, double *mirror, double *slots_lds,
-                                             double *value_lds, int relaxed)
+                                             double *value_lds)
 {
     const int groups = npartial <= kFoldDirect ? 1 : (npartial + kFoldChunk - 1) / kFoldChunk;
     double *slots = slots_of(area);
@@ -379,7 +372,7 @@ __device__ __forceinline__ double fold_ahead(int npartial, double *area, double 
         double s = block_sum(acc, slots_lds);
         if (groups > 1) {
             __shared__ int is_last;
-            if (threadIdx.x == 0) is_last = fold_handoff(folded + blockIdx.x, s, ticket_of(area), (unsigned)groups, relaxed);
+            if (threadIdx.x == 0) is_last = fold_handoff(folded + blockIdx.x, s, ticket_of(area), (unsigned)groups);
             __syncthreads();
             last = is_last != 0;
             if (last) {
@@ -420,7 +413,7 @@ __device__ __forceinline__ double fold_ahead(int npartial, double *area, double 
 template <typename T>
 __global__ void __launch_bounds__(kBlasBlock)
 cg_update_fold_kernel(int64_t n, const double *__restrict__ rz, int npartial_in, double *__restrict__ area_in, double *__restrict__ yp_out,
-                      const T *__restrict__ y, T *__restrict__ r, double *__restrict__ area_out, int vec, int pol, int relaxed)
+                      const T *__restrict__ y, T *__restrict__ r, double *__restrict__ area_out, int vec, int pol)
 {
     typedef typename vec16<T>::type V;
     constexpr int W = vec16<T>::n;
@@ -434,7 +427,7 @@ cg_update_fold_kernel(int64_t n, const double *__restrict__ rz, int npartial_in,
     const bool first = vec && t < nv;
     if (first) { y0 = reinterpret_cast<const V *>(y)[t]; r0 = reinterpret_cast<V *>(r)[t]; }
     const double rzv = *rz;
-    const double ypv = fold_ahead(npartial_in, area_in, yp_out, nullptr, slots, &value, relaxed);
+    const double ypv = fold_ahead(npartial_in, area_in, yp_out, nullptr, slots, &value);
     const T alpha = (T)(rzv / ypv);
     double acc = 0.0;
     if (vec) {
@@ -472,7 +465,7 @@ template <typename T>
 __global__ void __launch_bounds__(kBlasBlock)
 cg_direction_fold_kernel(int64_t n, int npartial_in, double *__restrict__ area_in, double *__restrict__ rr_new_out, double *__restrict__ mirror,
                          const double *__restrict__ rr_old, const double *__restrict__ yp, const T *__restrict__ r, T *__restrict__ p,
-                         T *__restrict__ x, int vec, int pol, int relaxed)
+                         T *__restrict__ x, int vec, int pol)
 {
     typedef typename vec16<T>::type V;
     constexpr int W = vec16<T>::n;
@@ -485,7 +478,7 @@ cg_direction_fold_kernel(int64_t n, int npartial_in, double *__restrict__ area_i
     const bool first = vec && t < nv;
     if (first) { r0 = reinterpret_cast<const V *>(r)[t]; p0 = reinterpret_cast<V *>(p)[t]; x0 = reinterpret_cast<V *>(x)[t]; }
     const double rro = *rr_old, ypv = *yp;
-    const double rrn = fold_ahead(npartial_in, area_in, rr_new_out, mirror, slots, &value, relaxed);
+    const double rrn = fold_ahead(npartial_in, area_in, rr_new_out, mirror, slots, &value);
     const T alpha = (T)(rro / ypv);
     const T beta = (T)(rrn / rro);
     if (vec) {
@@ -592,13 +585,6 @@ static int fused_grid(int64_t n, int per_thread)
 
 namespace {
 
-// which of the vectors a CG step writes get the nt hint: bit 0 x, bit 1 p, bit 2 r (CMI_CG_STORE_POLICY overrides: measurements)
-static int cg_store_policy()
-{
-    static const int pol = [] { const char *e = std::getenv("CMI_CG_STORE_POLICY"); return e ? std::atoi(e) : kCgStorePolicy; }();
-    return pol;
-}
-
 template <typename T>
 int cg_update_impl(int64_t n, const double *rz_dev, const double *yp_dev, const T *p, const T *y, T *x, T *r, double *rr_dev,
                    double *rr_host_mirror, void *workspace, void *stream)
@@ -608,7 +594,7 @@ int cg_update_impl(int64_t n, const double *rz_dev, const double *yp_dev, const 
     if (n > 0 && (!y || !r || (x && !p))) return fail(CMI_ERROR_INVALID_VALUE, "cmi_cg_update: null array");
     const int grid = fused_grid(n, vec16<T>::n);
     const int vec = aligned16(y) && aligned16(r) && (!x || (aligned16(p) && aligned16(x)));
-    hipLaunchKernelGGL((cg_update_kernel<T>), dim3(grid), dim3(kBlasBlock), 0, as_stream(stream), n, rz_dev, yp_dev, p, y, x, r, (double *)workspace, vec, cg_store_policy());
+    hipLaunchKernelGGL((cg_update_kernel<T>), dim3(grid), dim3(kBlasBlock), 0, as_stream(stream), n, rz_dev, yp_dev, p, y, x, r, (double *)workspace, vec, kCgStorePolicy);
     reduce_partials<double>(grid, (double *)workspace, rr_dev, 0, as_stream(stream), rr_host_mirror);
     CMI_LAUNCH_CHECK("cg_update");
     return CMI_SUCCESS;
@@ -625,7 +611,7 @@ int cg_direction_impl(int64_t n, const double *rr_new_dev, const double *rr_old_
     if (!r || !p || (with_x && !x)) { set_error("%s: null array", who); return CMI_ERROR_INVALID_VALUE; }
     const int vec = aligned16(r) && aligned16(p) && (!with_x || aligned16(x));
     hipLaunchKernelGGL((cg_direction_kernel<T>), dim3(stream_grid(n, vec16<T>::n)), dim3(kBlasBlock), 0, as_stream(stream), n, rr_new_dev,
-                       rr_old_dev, yp_dev, r, p, with_x ? x : (T *)nullptr, vec, cg_store_policy());
+                       rr_old_dev, yp_dev, r, p, with_x ? x : (T *)nullptr, vec, kCgStorePolicy);
     CMI_LAUNCH_CHECK("cg_direction");
     return CMI_SUCCESS;
 }
@@ -645,7 +631,7 @@ int cg_update_fold_impl(int64_t n, const double *rz_dev, double *yp_dev, int npa
     const int vec = aligned16(y) && aligned16(r);
     double *area_in = (double *)workspace, *area_out = (double *)workspace + kFoldArea;
     hipLaunchKernelGGL((cg_update_fold_kernel<T>), dim3(grid), dim3(kBlasBlock), 0, as_stream(stream), n, rz_dev, npartials_yp, area_in, yp_dev,
-                       y, r, area_out, vec, cg_store_policy(), fold_relaxed());
+                       y, r, area_out, vec, kCgStorePolicy);
     CMI_LAUNCH_CHECK("cg_update_fold");
     *npartials_rr = grid;
     return CMI_SUCCESS;
@@ -665,7 +651,7 @@ int cg_direction_fold_impl(int64_t n, double *rr_new_dev, double *rr_host_mirror
     const int vec = aligned16(r) && aligned16(p) && aligned16(x);
     double *area_in = (double *)workspace + kFoldArea;
     hipLaunchKernelGGL((cg_direction_fold_kernel<T>), dim3(grid), dim3(kBlasBlock), 0, as_stream(stream), n, npartials_rr, area_in, rr_new_dev,
-                       rr_host_mirror, rr_old_dev, yp_dev, r, p, x, vec, cg_store_policy(), fold_relaxed());
+                       rr_host_mirror, rr_old_dev, yp_dev, r, p, x, vec, kCgStorePolicy);
     CMI_LAUNCH_CHECK("cg_direction_x_fold");
     return CMI_SUCCESS;
 }

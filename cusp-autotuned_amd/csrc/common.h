@@ -219,14 +219,7 @@ typedef float __attribute__((ext_vector_type(4))) float4v;
 constexpr int kPolLoadNT = 1, kPolStoreNT = 2;
 constexpr int64_t kInfinityCacheBytes = 256ll << 20; // MALL, shared by the 8 XCDs
 constexpr int kWaveTileMaxK = 10; // csr_wave: entries per lane (= the longest row of the matrix)
-constexpr int kPolPairs = 8;   // csr_stream, f64, single-pass tile path: streams requested as (int2, double2) pairs -- every line requested once (round 3)
 constexpr int kPolStrided = 4; // csr_stream only: entry streams requested lane-strided (a dword / a value per lane per instruction), not as 16-byte vectors
-// $CMI_CSR_STRIDED=0/1 overrides the bit (measurements: A/B of the two request shapes through every tool and test)
-inline int csr_lane_strided(int policy_bits)
-{
-    static const int env = [] { const char *e = std::getenv("CMI_CSR_STRIDED"); return e ? std::atoi(e) : -1; }();
-    return env >= 0 ? (env != 0) : ((policy_bits & kPolStrided) != 0);
-}
 
 template <bool NT, typename V> __device__ __forceinline__ V ld(const V *p)
 {
@@ -268,15 +261,18 @@ template <typename T> __device__ __forceinline__ T sum_in_order(T s, const T *p,
     return s;
 }
 
-// run `f(std::integral_constant<int, POL>)` for the runtime policy value 0..3
-template <typename F> inline void with_policy(int pol, F f)
+// run `f(std::integral_constant<int, V>())` for the runtime value v among the instances Vs...; false when v is none of them
+template <int... Vs, typename F> inline bool with_int(int v, F &&f)
 {
-    switch (pol & 3) {
-    case 0: f(std::integral_constant<int, 0>()); break;
-    case 1: f(std::integral_constant<int, 1>()); break;
-    case 2: f(std::integral_constant<int, 2>()); break;
-    default: f(std::integral_constant<int, 3>()); break;
-    }
+    return ((v == Vs ? (f(std::integral_constant<int, Vs>()), true) : false) || ...);
+}
+// run `f(std::integral_constant<int, POL>)` for the runtime policy value 0..3
+template <typename F> inline void with_policy(int pol, F &&f) { with_int<0, 1, 2, 3>(pol & 3, f); }
+// run `f(std::bool_constant<b>)` for the runtime flag b
+template <typename F> inline void with_bool(bool b, F &&f)
+{
+    if (b) f(std::true_type());
+    else f(std::false_type());
 }
 
 } // namespace cmi

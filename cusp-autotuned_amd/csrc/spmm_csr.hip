@@ -256,20 +256,12 @@ static int spmm_csr(int64_t rows, int64_t cols, int64_t nnz, const int *Ap, cons
     const bool vec = xcs == 1 && ycs == 1 && (cols == 0 || reinterpret_cast<uintptr_t>(X) % vb == 0) && reinterpret_cast<uintptr_t>(Y) % vb == 0 &&
                      ((size_t)xrs * sizeof(T)) % vb == 0 && ((size_t)yrs * sizeof(T)) % vb == 0;
     constexpr int CPL = 16 / sizeof(T);
-    auto go = [&](auto LL) {
-        constexpr int LC = decltype(LL)::value;
-        if (vec) hipLaunchKernelGGL((spmm_csr_kernel<T, LC, CPL, true, 4>), grid, dim3(B), 0, s, rows, Ap, Aj, Ax, k, X, xrs, xcs, Y, yrs, ycs, accumulate);
-        else     hipLaunchKernelGGL((spmm_csr_kernel<T, LC, CPL, false, 4>), grid, dim3(B), 0, s, rows, Ap, Aj, Ax, k, X, xrs, xcs, Y, yrs, ycs, accumulate);
-    };
-    switch (L) {
-    case 1: go(std::integral_constant<int, 1>()); break;
-    case 2: go(std::integral_constant<int, 2>()); break;
-    case 4: go(std::integral_constant<int, 4>()); break;
-    case 8: go(std::integral_constant<int, 8>()); break;
-    case 16: go(std::integral_constant<int, 16>()); break;
-    case 32: go(std::integral_constant<int, 32>()); break;
-    default: go(std::integral_constant<int, 64>()); break;
-    }
+    with_int<1, 2, 4, 8, 16, 32, 64>(L, [&](auto LL) { // (spmm_rule and the checks above: a power of two, at most 64)
+        with_bool(vec, [&](auto VEC) {
+            hipLaunchKernelGGL((spmm_csr_kernel<T, decltype(LL)::value, CPL, decltype(VEC)::value, 4>), grid, dim3(B), 0, s, rows, Ap, Aj, Ax, k, X,
+                               xrs, xcs, Y, yrs, ycs, accumulate);
+        });
+    });
     CMI_LAUNCH_CHECK("csr spmm");
     return CMI_SUCCESS;
 }

@@ -78,7 +78,7 @@ __global__ void __launch_bounds__(1024)
 csr_stream_kernel(int64_t num_rows, int64_t num_entries, const int *__restrict__ Ap,
                   const int *__restrict__ Aj, const T *__restrict__ Ax, const T *__restrict__ x,
                   T *__restrict__ y, int rows_per_block, int64_t num_tiles, int64_t tiles_per_xcd,
-                  int swizzle, int accumulate, int tpr, int long_len, int lane_strided, int spread_rows, int pairs, const T *__restrict__ w = nullptr,
+                  int swizzle, int accumulate, int tpr, int long_len, int lane_strided, const T *__restrict__ w = nullptr,
                   double *__restrict__ dot_partial = nullptr)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -167,90 +167,52 @@ csr_stream_kernel(int64_t num_rows, int64_t num_entries, const int *__restrict__
         const int nz0 = Ap[r0], nz1 = Ap[r0 + nr];
         const int fbase = nz0 & ~3;
         if (tpr == 1 && nr <= block && nz1 - fbase <= tile_entries && (int64_t)((nz1 + 3) & ~3) <= num_entries) {
-            // Which lane adds which row.  Default: lane r adds row r -- for long rows (80 rows of 45 entries in a 512-lane tile) that is
-            // one and a quarter waves adding serially behind the barrier while the other waves have nothing to do, with up to 32 lanes of
-            // one LDS instruction colliding on banks.  SPREAD (round 3; kernel argument, uniform): the rows are dealt round the WAVES --
-            // wave w adds rows w, w + W, w + 2 W, ... on its lanes 0, 1, 2, ... -- so every SIMD works on the sum phase at once and an LDS
-            // instruction carries nr / W lanes.  Same products, same order per row: same bits.
-            int myrow = tid;
-            if (spread_rows == 1) { const int W = block >> 6; myrow = (tid & (kWave - 1)) * W + (tid >> 6); }
-            else if (spread_rows == 2) { // (measurement variant: a contiguous chunk of rows per wave -- neighbouring lanes keep neighbouring rows)
-                const int W = block >> 6, chunk = (nr + W - 1) / W, l = tid & (kWave - 1);
-                myrow = l < chunk ? (tid >> 6) * chunk + l : block;
-            }
-            const bool has_row = myrow < nr;
-            const int a = Ap[r0 + (has_row ? myrow : nr)], b = Ap[r0 + (has_row ? myrow + 1 : nr)];
-            // Request shape of the f64 streams.  16-BYTE VECTORS (rounds 1-2): an int4 of columns and two double2 of values per lane and
-            // vector -- the two value loads of a wave interleave, every 128-byte line of Ax is touched by both instructions.  PAIRS
-            // (round 3, `pairs`, f64 only): an int2 of columns and ONE double2 of values per lane and load, twice as many loads -- every
-            // load instruction covers one contiguous span (512 B of indices, 1 KiB of values) and every line is requested exactly once,
-            // the property of the lane-strided / wave-tile kernels; the products land in LDS 16 bytes per lane, lanes contiguous (no
-            // bank conflict; the vector form's 32-byte lane stride is a 2-way one).  Same products, same slots: same bits.
-            if (sizeof(T) == 8 && pairs && nz1 > nz0) { // (a tile of empty rows has no last pair to clamp to: the guarded vector body below loads nothing)
-                constexpr int NP = 2 * IPT;
-                int2v c2[NP];
-                double2v v2[NP];
-                const int lastp = (nz1 - 1) & ~1; // lanes past the tile's last pair re-read it and park products in their own (unread) slots
-#pragma unroll
-                for (int k = 0; k < NP; k++) {
-                    int e = fbase + (k * block + tid) * 2;
-                    e = e < lastp ? e : lastp;
-                    c2[k] = ld<NT>(reinterpret_cast<const int2v *>(Aj + e));
-                }
-#pragma unroll
-                for (int k = 0; k < NP; k++) {
-                    int e = fbase + (k * block + tid) * 2;
-                    e = e < lastp ? e : lastp;
-                    v2[k] = ld<NT>(reinterpret_cast<const double2v *>(Ax + e));
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int k = 0; k < NP; k++) {
-                    const double x0 = x[c2[k].x], x1 = x[c2[k].y];
-                    *reinterpret_cast<double2v *>(prod + (k * block + tid) * 2) = double2v{v2[k].x * x0, v2[k].y * x1};
-                }
-            } else {
+            // Lane r adds row r, and the f64 streams are requested as 16-byte vectors.  (Round 3 measured two alternatives, both slower
+            // or equal, profiles/HISTORY.md section R3: the row sums dealt round the waves -- ldoor-like 100 -> 110 us, nlpkkt120-like
+            // 213 -> 236 / 218 us, profiles/r03_long_rows_experiments.txt -- and an int2 of columns with ONE double2 of values per load,
+            // no gain at the table's shape and 99 against 86.7 us at block 256 x 32 rows.)
+            const bool has_row = tid < nr;
+            const int a = Ap[r0 + (has_row ? tid : nr)], b = Ap[r0 + (has_row ? tid + 1 : nr)];
             // IPT vectors per lane, all requested before the first product is formed (round 2: the path also serves the
-                // longer-row shapes of the table, IPT 2 and 4 -- FEM-like matrices of 27-80 entries per row)
-                int4v c[IPT];
-                T v[IPT][4];
-    #pragma unroll
-                for (int k = 0; k < IPT; k++) {
-                    const int e = fbase + (k * block + tid) * 4;
-                    if (e < nz1) {
-                        c[k] = ld<NT>(reinterpret_cast<const int4v *>(Aj + e));
-                        if constexpr (sizeof(T) == 8) {
-                            const double2v v01 = ld<NT>(reinterpret_cast<const double2v *>(Ax + e));
-                            const double2v v23 = ld<NT>(reinterpret_cast<const double2v *>(Ax + e + 2));
-                            v[k][0] = v01.x; v[k][1] = v01.y; v[k][2] = v23.x; v[k][3] = v23.y;
-                        } else {
-                            const float4v vv = ld<NT>(reinterpret_cast<const float4v *>(Ax + e));
-                            v[k][0] = vv.x; v[k][1] = vv.y; v[k][2] = vv.z; v[k][3] = vv.w;
-                        }
+            // longer-row shapes of the table, IPT 2 and 4 -- FEM-like matrices of 27-80 entries per row)
+            int4v c[IPT];
+            T v[IPT][4];
+#pragma unroll
+            for (int k = 0; k < IPT; k++) {
+                const int e = fbase + (k * block + tid) * 4;
+                if (e < nz1) {
+                    c[k] = ld<NT>(reinterpret_cast<const int4v *>(Aj + e));
+                    if constexpr (sizeof(T) == 8) {
+                        const double2v v01 = ld<NT>(reinterpret_cast<const double2v *>(Ax + e));
+                        const double2v v23 = ld<NT>(reinterpret_cast<const double2v *>(Ax + e + 2));
+                        v[k][0] = v01.x; v[k][1] = v01.y; v[k][2] = v23.x; v[k][3] = v23.y;
                     } else {
-                        c[k] = int4v{0, 0, 0, 0};
-                        v[k][0] = v[k][1] = v[k][2] = v[k][3] = T(0);
+                        const float4v vv = ld<NT>(reinterpret_cast<const float4v *>(Ax + e));
+                        v[k][0] = vv.x; v[k][1] = vv.y; v[k][2] = vv.z; v[k][3] = vv.w;
                     }
+                } else {
+                    c[k] = int4v{0, 0, 0, 0};
+                    v[k][0] = v[k][1] = v[k][2] = v[k][3] = T(0);
                 }
-    #pragma unroll
-                for (int k = 0; k < IPT; k++) {
-                    const int slot = (k * block + tid) * 4;
-                    if (fbase + slot < nz1) { // (uniform per wave except at the tile's end: the gathers of a wave stay together)
-                        const T x0 = x[c[k].x], x1 = x[c[k].y], x2 = x[c[k].z], x3 = x[c[k].w];
-                        prod[slot + 0] = v[k][0] * x0; prod[slot + 1] = v[k][1] * x1;
-                        prod[slot + 2] = v[k][2] * x2; prod[slot + 3] = v[k][3] * x3;
-                    }
+            }
+#pragma unroll
+            for (int k = 0; k < IPT; k++) {
+                const int slot = (k * block + tid) * 4;
+                if (fbase + slot < nz1) { // (uniform per wave except at the tile's end: the gathers of a wave stay together)
+                    const T x0 = x[c[k].x], x1 = x[c[k].y], x2 = x[c[k].z], x3 = x[c[k].w];
+                    prod[slot + 0] = v[k][0] * x0; prod[slot + 1] = v[k][1] * x1;
+                    prod[slot + 2] = v[k][2] * x2; prod[slot + 3] = v[k][3] * x3;
                 }
             }
             T wv = T(0);
-            if constexpr (DOT) { if (has_row) wv = w[r0 + myrow]; } // requested before the barrier
+            if constexpr (DOT) { if (has_row) wv = w[r0 + tid]; } // requested before the barrier
             __syncthreads();
             double d = 0.0;
             if (has_row) {
-                T s = accumulate ? y[r0 + myrow] : T(0);
+                T s = accumulate ? y[r0 + tid] : T(0);
                 if constexpr (IPT == 1) { for (int j = a; j < b; j++) s = s + prod[j - fbase]; } // short rows: the plain loop is faster
                 else s = sum_in_order(s, prod + (a - fbase), b - a);
-                st<(POL & kPolStoreNT) != 0>(y + r0 + myrow, s);
+                st<(POL & kPolStoreNT) != 0>(y + r0 + tid, s);
                 if constexpr (DOT) d = (double)s * (double)wv;
             }
             if constexpr (DOT) {
@@ -462,10 +424,8 @@ template <typename T, int K, int POL, bool DOT>
 __global__ void __launch_bounds__(1024)
 csr_wave_kernel(int64_t num_rows, const int *Ap /* not restrict: see the asm below */, const int *__restrict__ Aj,
                 const T *__restrict__ Ax, const T *__restrict__ x, T *__restrict__ y, int rows_per_wave, int64_t num_tiles,
-                int64_t tiles_per_xcd, int swizzle, int accumulate, const T *__restrict__ w, double *__restrict__ dot_partial, int dot_ablate = 0)
+                int64_t tiles_per_xcd, int swizzle, int accumulate, const T *__restrict__ w, double *__restrict__ dot_partial)
 {
-    // dot_ablate (measurements only, $CMI_DOT_ABLATE; WRONG <y, w> by design): bit 1 -- w is not loaded; bit 2 -- no workgroup combine (no
-    // barrier: wave 0 stores its own partial)
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ double dot_slots[DOT ? 1024 / kWave : 1];
     constexpr bool NT = (POL & kPolLoadNT) != 0, NTS = (POL & kPolStoreNT) != 0;
@@ -481,7 +441,7 @@ csr_wave_kernel(int64_t num_rows, const int *Ap /* not restrict: see the asm bel
         const int cnt = nz1 - nz0;
         int a = Ap[r0 + (lane < nr ? lane : nr)];
         T wv = T(0);
-        if constexpr (DOT) { if (lane < nr) wv = (dot_ablate & 1) ? T(1) : w[r0 + lane]; }
+        if constexpr (DOT) { if (lane < nr) wv = w[r0 + lane]; }
         if (cnt > 0 && cnt <= kWave * K) { // (uniform per wave)
             T *mine = reinterpret_cast<T *>(smem) + (size_t)wave * kWave * K;
             int c[K];
@@ -543,11 +503,7 @@ csr_wave_kernel(int64_t num_rows, const int *Ap /* not restrict: see the asm bel
         }
     }
     if constexpr (DOT) {
-        if (dot_ablate & 2) {
-            d = wave_sum_to_last(d);
-            if (threadIdx.x == kWave - 1) dot_partial[tile] = d;
-        } else
-            tile_dot_store(d, dot_slots, dot_partial + tile);
+        tile_dot_store(d, dot_slots, dot_partial + tile);
         if (tile == 0 && threadIdx.x == 0) reset_fold_state(dot_partial);
     }
 }
@@ -662,14 +618,9 @@ csr_wavep_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, const in
 // first vector starts at the 16-byte boundary at or below its first entry), so a tile always fits its wave's slots; the partition
 // is wave_partition_kernel's (8 bytes per tile, plan-owned).  Same products, storage-order sums: bit-exact.
 // The last vector of the ARRAYS may reach past num_entries: that one wave sums its rows straight from the arrays.
-// ABL != 0: ablation instances for measurements only ($CMI_WAVEV_ABLATE, f64 / V = 4; WRONG results by design) --
-//   bit 1: no x gathers (the columns are still loaded);  bit 2: no LDS, no row sums (every lane adds its own products, the wave
-//   folds them and lanes < rows store the total);  bit 4: products parked in LDS as usual, but a row's lane reads only its first one.
-//   bit 8 (with bit 2): the LDS ALLOCATION is kept (one store per lane), nothing else of it.
-// WPB: wave tiles per workgroup (4: the shipped shape; 1 / 2: $CMI_WAVEV_WPB, V = 4 -- a workgroup's LDS goes back when its LAST wave ends).
-// LDIV (ablation 10 / 11 only): the kept allocation is 1 / LDIV of the real one.
-template <typename T, int V, int POL, bool DOT, int ABL = 0, int WPB = 4, int LDIV = 1>
-__global__ void __launch_bounds__(kWave * WPB)
+// Four wave tiles per workgroup.
+template <typename T, int V, int POL, bool DOT>
+__global__ void __launch_bounds__(256)
 csr_wavev_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t num_entries, const int *Ap /* not restrict: see csr_wave */,
                  const int *__restrict__ Aj, const T *__restrict__ Ax, const T *__restrict__ x, T *__restrict__ y, int64_t num_tiles,
                  int64_t tiles_per_xcd, int swizzle, int accumulate, const T *__restrict__ w, double *__restrict__ dot_partial)
@@ -682,13 +633,13 @@ csr_wavev_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t 
     constexpr int E = sizeof(T) == 8 ? 2 : 4, NL = (V * 4) / E, SLOTS = kWave * V * 4;
     typedef int __attribute__((ext_vector_type(E))) idx_t;
     typedef T __attribute__((ext_vector_type(E))) val_t;
-    __shared__ __attribute__((aligned(16))) T prod[WPB][SLOTS / LDIV];
-    __shared__ double dot_slots[DOT ? WPB : 1];
+    __shared__ __attribute__((aligned(16))) T prod[4][SLOTS];
+    __shared__ double dot_slots[DOT ? 4 : 1];
     constexpr bool NT = (POL & kPolLoadNT) != 0, NTS = (POL & kPolStoreNT) != 0;
     const int64_t tile = tile_of_block(blockIdx.x, tiles_per_xcd, swizzle);
     if (tile >= num_tiles) return; // whole workgroup
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave), lane = threadIdx.x & (kWave - 1);
-    const int64_t wt = tile * WPB + wave;
+    const int64_t wt = tile * 4 + wave;
     double d = 0.0;
     if (wt < wave_tiles) {
         const int2v lo = *reinterpret_cast<const int2v *>(start + 2 * wt), hi = *reinterpret_cast<const int2v *>(start + 2 * wt + 2);
@@ -722,40 +673,22 @@ csr_wavev_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t 
 #pragma unroll
                 for (int k = 0; k < NL; k++)
 #pragma unroll
-                    for (int i = 0; i < E; i++) {
-                        if constexpr ((ABL & 1) != 0) { asm volatile("" ::"v"(c[k][i])); xv[k][i] = T(1); }
-                        else xv[k][i] = x[c[k][i]];
-                    }
+                    for (int i = 0; i < E; i++) xv[k][i] = x[c[k][i]];
                 asm volatile("" : "+v"(a)); // the row offset was requested in front of the streams
-                T lane_sum = T(0);
 #pragma unroll
                 for (int k = 0; k < NL; k++) {
                     val_t pr;
 #pragma unroll
                     for (int i = 0; i < E; i++) pr[i] = v[k][i] * xv[k][i];
-                    if constexpr ((ABL & 2) != 0) {
-#pragma unroll
-                        for (int i = 0; i < E; i++) lane_sum = lane_sum + pr[i];
-                    } else
-                        *reinterpret_cast<val_t *>(mine + (k * kWave + lane) * E) = pr; // 16 bytes per lane, lanes contiguous: no bank conflict
+                    *reinterpret_cast<val_t *>(mine + (k * kWave + lane) * E) = pr; // 16 bytes per lane, lanes contiguous: no bank conflict
                 }
                 __builtin_amdgcn_wave_barrier(); // (compiler only: the hardware runs a wave's LDS instructions in order)
-                if constexpr ((ABL & 2) != 0) {
-                    if constexpr ((ABL & 8) != 0) *reinterpret_cast<volatile T *>(mine + lane) = lane_sum;
-                    // every lane's products must be NEEDED: without this the compiler masks the loads of the lanes >= nr off (session 22's
-                    // first "no LDS" figures were of a kernel that read a third of the matrix)
-                    lane_sum = (T)wave_sum_to_last((double)lane_sum);
-                    lane_sum = (T)__shfl((double)lane_sum, kWave - 1);
-                    if (lane < nr) st<NTS>(y + rs + lane, lane_sum);
-                    return;
-                }
             }
             b = __builtin_amdgcn_update_dpp(first_turn_end, a, 0x130 /* wave_shl:1: the next lane's start; lane 63 keeps the 64th row's end */, 0xf, 0xf, false);
             for (int r = lane; r < nr; r += kWave) { // (one turn, except over a stretch of very short rows)
                 if (r >= kWave) { a = Ap[rs + r]; b = Ap[rs + r + 1]; }
                 T sum = accumulate ? y[rs + r] : T(0);
-                if constexpr ((ABL & 4) != 0) { if (fits && b > a) sum = sum + mine[a - fbase]; }
-                else if (fits) sum = sum_in_order(sum, mine + (a - fbase), b - a);
+                if (fits) sum = sum_in_order(sum, mine + (a - fbase), b - a);
                 else for (int j = a; j < b; j++) sum = sum + Ax[j] * x[Aj[j]]; // (the array's last vector, or an empty tile)
                 st<NTS>(y + rs + r, sum);
                 if constexpr (DOT) d += (double)sum * (double)w[rs + r];
@@ -1370,45 +1303,300 @@ static int grid_for(int64_t work_items, int block, int items_per_block_thread = 
     return (int)blocks;
 }
 
-template <typename T, bool NT>
-static int launch_vector(int tpr, int grid, int block, hipStream_t s, int64_t rows, const int *Ap, const int *Aj,
-                         const T *Ax, const T *x, T *y, int acc)
+// XCD dealing of csr_stream's fused SpMV + <y, w> instance (and the 16-bit copy's stream kernel) with a table shape: launch order
+// inside a solve (see launch_stream); a shape the caller gave the plan: as given
+static int dot_swizzle(int table_swizzle, const cmi_plan *plan)
 {
-    switch (tpr) {
-    case 2:  hipLaunchKernelGGL((csr_vector_kernel<T, 2, NT>),  dim3(grid), dim3(block), 0, s, rows, Ap, Aj, Ax, x, y, acc); break;
-    case 4:  hipLaunchKernelGGL((csr_vector_kernel<T, 4, NT>),  dim3(grid), dim3(block), 0, s, rows, Ap, Aj, Ax, x, y, acc); break;
-    case 8:  hipLaunchKernelGGL((csr_vector_kernel<T, 8, NT>),  dim3(grid), dim3(block), 0, s, rows, Ap, Aj, Ax, x, y, acc); break;
-    case 16: hipLaunchKernelGGL((csr_vector_kernel<T, 16, NT>), dim3(grid), dim3(block), 0, s, rows, Ap, Aj, Ax, x, y, acc); break;
-    case 32: hipLaunchKernelGGL((csr_vector_kernel<T, 32, NT>), dim3(grid), dim3(block), 0, s, rows, Ap, Aj, Ax, x, y, acc); break;
-    case 64: hipLaunchKernelGGL((csr_vector_kernel<T, 64, NT>), dim3(grid), dim3(block), 0, s, rows, Ap, Aj, Ax, x, y, acc); break;
-    default: return fail(CMI_ERROR_NOT_SUPPORTED, "csr_vector: threads_per_row must be 2,4,8,16,32 or 64");
-    }
+    return plan && plan->cfg_explicit ? table_swizzle : 0;
+}
+
+template <typename T>
+static int launch_scalar(const cmi_config &c, int pol, hipStream_t s, int64_t rows, const int *Ap, const int *Aj, const T *Ax, const T *x,
+                         T *y, int accumulate)
+{
+    const int block = c.block_size;
+    const int grid = grid_for(rows, block);
+    with_policy(pol, [&](auto P) {
+        hipLaunchKernelGGL((csr_scalar_kernel<T, decltype(P)::value>), dim3(grid), dim3(block), 0, s, rows, Ap, Aj, Ax, x, y, accumulate);
+    });
     return CMI_SUCCESS;
 }
 
-// XCD dealing of the fused SpMV + <y, w> instance when the shape is the table's (see the call site)
-static int dot_swizzle(int table_swizzle, const cmi_plan *plan, int inside_a_solve = 0)
+template <typename T>
+static int launch_vector(const cmi_config &c, int pol, hipStream_t s, int64_t rows, const int *Ap, const int *Aj, const T *Ax, const T *x,
+                         T *y, int accumulate)
 {
-    static const int env = [] { const char *e = std::getenv("CMI_DOT_SWIZZLE"); return e ? std::atoi(e) : -1; }();
-    if (plan && plan->cfg_explicit) return table_swizzle; // a shape the caller gave the plan: as given
-    return env >= 0 ? env : inside_a_solve;
+    const int block = c.block_size, tpr = c.threads_per_row;
+    const int grid = grid_for(rows * tpr, block);
+    const bool launched = with_int<2, 4, 8, 16, 32, 64>(tpr, [&](auto TPR) {
+        with_bool((pol & kPolLoadNT) != 0, [&](auto NT) {
+            hipLaunchKernelGGL((csr_vector_kernel<T, decltype(TPR)::value, decltype(NT)::value>), dim3(grid), dim3(block), 0, s, rows, Ap, Aj,
+                               Ax, x, y, accumulate);
+        });
+    });
+    if (!launched) return fail(CMI_ERROR_NOT_SUPPORTED, "csr_vector: threads_per_row must be 2,4,8,16,32 or 64");
+    return CMI_SUCCESS;
 }
 
-template <typename T, bool VEC, int POL, bool DOT = false, bool LONG = false>
-static int launch_stream_ipt(int ipt, int grid, int block, size_t lds, hipStream_t s, int64_t rows, int64_t nnz,
-                             const int *Ap, const int *Aj, const T *Ax, const T *x, T *y, int rpb, int64_t tiles,
-                             int64_t tpx, int swz, int acc, int tpr, int long_len, int strided, int spread, int pairs, const T *w = nullptr, double *dot_partial = nullptr)
+template <typename T>
+static int launch_stream(const cmi_config &c, const cmi_config *user, const cmi_plan *plan, int64_t known_max_len, int pol, hipStream_t s,
+                         int64_t rows, int64_t nnz, const int *Ap, const int *Aj, const T *Ax, const T *x, T *y, int accumulate, const T *w,
+                         double *dot_partial, int *dot_partials)
 {
-#define CMI_STREAM_LAUNCH(IPT)                                                                                              \
-    hipLaunchKernelGGL((csr_stream_kernel<T, IPT, VEC, POL, DOT, LONG>), dim3(grid), dim3(block), lds, s, rows, nnz, Ap, Aj, \
-                       Ax, x, y, rpb, tiles, tpx, swz, acc, tpr, long_len, strided, spread, pairs, w, dot_partial)
-    switch (ipt) {
-    case 1: CMI_STREAM_LAUNCH(1); break;
-    case 2: CMI_STREAM_LAUNCH(2); break;
-    case 4: CMI_STREAM_LAUNCH(4); break;
-    default: return fail(CMI_ERROR_NOT_SUPPORTED, "csr_stream: items_per_thread must be 1, 2 or 4");
+    int rpb = c.rows_per_block;
+    const int ipt = c.items_per_thread;
+    // The fused <y, w> instance wants whole waves of rows: with the table's 176 rows per tile (2.75 waves) the dot costs
+    // +9.3 us on the headline matrix, with 192 (3 waves) +3.7 us (archive/tools/r2_probe.hip csrx flags 5 vs 1 at rpb 176 / 192,
+    // archive/profiles/r02_probe_dot_ablation.txt).  So a table-chosen shape (not a caller's explicit one) is rounded up to the
+    // next multiple of 64 rows when the tile's single LDS pass still holds them.
+    int block = c.block_size; // (the dot instance may widen it)
+    if (w && dot_partial && (!user || user->kernel == CMI_KERNEL_AUTO || user->rows_per_block == 0) && c.threads_per_row <= 1 && rows > 0) {
+        const int up = (rpb + kWave - 1) / kWave * kWave;
+        const double mean = (double)nnz / (double)rows;
+        const int64_t tile_entries = (int64_t)block * ipt * 4;
+        if (up != rpb && up <= block && (double)up * mean + 3.0 <= (double)tile_entries) rpb = up;
     }
-#undef CMI_STREAM_LAUNCH
+    // ... and one partial per tile must fit the workspace: a table shape with small tiles (f32's 96 rows of 128 lanes at 10^7
+    // rows: 104 000 tiles) is doubled -- lanes and rows together, the same fill of the LDS pass -- until it does
+    if (w && dot_partial && (!user || user->kernel == CMI_KERNEL_AUTO || user->rows_per_block == 0) && c.threads_per_row <= 1)
+        while (ceil_div(rows, rpb) > kPartialCapacity && block * 2 <= 1024) { block *= 2; rpb *= 2; }
+    int tpr = c.threads_per_row <= 1 ? 1 : c.threads_per_row;
+    if (tpr > 64 || (tpr & (tpr - 1)) != 0) return fail(CMI_ERROR_NOT_SUPPORTED, "csr_stream: threads_per_row must be 0/1 or a power of two <= 64");
+    // threads_per_row == 0: rows of kLongRowPerLane entries per lane of a group (at least kLongRowMin) or more
+    // are streamed by the whole workgroup (re-associated); == 1: storage order for every row, whatever its length
+    const int long_len = c.threads_per_row == 1 ? 0 : (tpr * kLongRowPerLane > kLongRowMin ? tpr * kLongRowPerLane : kLongRowMin);
+    if (rpb < 1 || rpb > 4 * (block / tpr)) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream: rows_per_block must be in [1, 4*block_size/threads_per_row]");
+    const int64_t tiles = ceil_div(rows, rpb);
+    const int64_t tpx = ceil_div(tiles, kXcds);
+    int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
+    // ... and its tiles go out in launch order: inside the solve that measured 2.3-3.5 us per iteration better than any chunk
+    // dealing, for every tile shape (tools/cg_dot_shape_probe.py, archive/profiles/r02_cg_dot_shape.txt) -- stand-alone it is the
+    // other way round (section 3.1 of DESIGN.md).  A caller's explicit shape is left alone.
+    if (w && dot_partial && (!user || user->kernel == CMI_KERNEL_AUTO)) swz = dot_swizzle(swz, plan);
+    const int64_t grid64 = swz == 0 ? tiles : swz == 1 ? tpx * kXcds : ceil_div(tiles, (int64_t)kXcds * swz) * kXcds * swz;
+    if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream: grid too large");
+    const size_t lds = (size_t)block * ipt * 4 * sizeof(T) + (size_t)(rpb + 1) * sizeof(int);
+    if (lds > 160 * 1024) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream: tile does not fit 160 KiB of LDS");
+    const bool vec = (reinterpret_cast<uintptr_t>(Aj) % 16 == 0) && (reinterpret_cast<uintptr_t>(Ax) % 16 == 0);
+    const bool dot = w && dot_partial && vec && tiles <= kPartialCapacity;
+    // the LONG instance only for a matrix whose plan shows such a row (no plan: the ordinary instance, which sums
+    // any row, one lane or lane group at a time -- correct, slow on a long row)
+    const bool lng = long_len > 0 && nnz >= long_len && known_max_len >= long_len;
+    const int strided = (c.nontemporal & kPolStrided) != 0;
+    bool launched = false;
+    with_policy(pol, [&](auto P) {
+        launched = with_int<1, 2, 4>(ipt, [&](auto I) {
+            auto go = [&](auto VEC, auto DOT, auto LONG) {
+                hipLaunchKernelGGL((csr_stream_kernel<T, decltype(I)::value, decltype(VEC)::value, decltype(P)::value, decltype(DOT)::value,
+                                                      decltype(LONG)::value>),
+                                   dim3((unsigned)grid64), dim3(block), lds, s, rows, nnz, Ap, Aj, Ax, x, y, rpb, tiles, tpx, swz, accumulate, tpr,
+                                   long_len, strided, w, dot_partial);
+            };
+            with_bool(lng, [&](auto LONG) { // (the dot instance needs the 16-byte vector body)
+                if (dot) go(std::true_type(), std::true_type(), LONG);
+                else with_bool(vec, [&](auto VEC) { go(VEC, std::false_type(), LONG); });
+            });
+        });
+    });
+    if (!launched) return fail(CMI_ERROR_NOT_SUPPORTED, "csr_stream: items_per_thread must be 1, 2 or 4");
+    if (dot && dot_partials) *dot_partials = (int)tiles;
+    return CMI_SUCCESS;
+}
+
+template <typename T>
+static int launch_wave(const cmi_config &c, const cmi_plan *plan, int pol, hipStream_t s, int64_t rows, const int *Ap,
+                       const int *Aj, const T *Ax, const T *x, T *y, int accumulate, const T *w, double *dot_partial, int *dot_partials)
+{
+    const int K = c.items_per_thread;
+    if (plan && plan->wave_row_start) { // irregular short rows: the plan's partition (above)
+        if (K < 2 || K > kWaveTileMaxK) return fail(CMI_ERROR_NOT_SUPPORTED, "csr_wave: items_per_thread (entries per lane) must be 2..10");
+        const int64_t tiles = ceil_div(plan->wave_tiles, (int64_t)4);
+        const int64_t tpx = ceil_div(tiles, kXcds);
+        const int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
+        const int64_t grid64 = padded_grid(tiles, swz);
+        if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_wave: grid too large");
+        const bool dot = w && dot_partial && tiles <= kPartialCapacity;
+        with_policy(pol, [&](auto P) {
+            with_int<2, 3, 4, 5, 6, 7, 8, 9, 10>(K, [&](auto KK) {
+                with_bool(dot, [&](auto DOT) {
+                    hipLaunchKernelGGL((csr_wavep_kernel<T, decltype(KK)::value, decltype(P)::value, decltype(DOT)::value>), dim3((unsigned)grid64),
+                                       dim3(256), 0, s, plan->wave_row_start, plan->wave_tiles, Ap, Aj, Ax, x, y, tiles, tpx, swz, accumulate, w,
+                                       dot_partial);
+                });
+            });
+        });
+        if (dot && dot_partials) *dot_partials = (int)tiles;
+        return CMI_SUCCESS;
+    }
+    const int block = c.block_size, waves = block / kWave;
+    if (K < 2 || K > kWaveTileMaxK) return fail(CMI_ERROR_NOT_SUPPORTED, "csr_wave: items_per_thread (entries per lane) must be 2..10");
+    if (c.rows_per_block < waves || c.rows_per_block % waves != 0 || c.rows_per_block / waves > kWave)
+        return fail(CMI_ERROR_INVALID_VALUE, "csr_wave: rows_per_block must be block_size/64 waves x 1..64 rows each");
+    const int rpw = c.rows_per_block / waves;
+    const int64_t tiles = ceil_div(rows, (int64_t)c.rows_per_block);
+    const int64_t tpx = ceil_div(tiles, kXcds);
+    // (the wave-tile kernel keeps the table's chunk dealing inside a solve too: 239 against 243.5 us per CG iteration in launch
+    //  order, archive/profiles/r02_cg_wave_dot.txt -- csr_stream's dot instance is the other way round)
+    const int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
+    const int64_t grid64 = padded_grid(tiles, swz);
+    if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_wave: grid too large");
+    const size_t lds = (size_t)block * K * sizeof(T);
+    if (lds > 64 * 1024) return fail(CMI_ERROR_INVALID_VALUE, "csr_wave: block_size x items_per_thread products do not fit 64 KiB of LDS");
+    const bool dot = w && dot_partial && tiles <= kPartialCapacity;
+    with_policy(pol, [&](auto P) {
+        with_int<2, 3, 4, 5, 6, 7, 8, 9, 10>(K, [&](auto KK) {
+            with_bool(dot, [&](auto DOT) {
+                hipLaunchKernelGGL((csr_wave_kernel<T, decltype(KK)::value, decltype(P)::value, decltype(DOT)::value>), dim3((unsigned)grid64),
+                                   dim3(block), lds, s, rows, Ap, Aj, Ax, x, y, rpw, tiles, tpx, swz, accumulate, w, dot_partial);
+            });
+        });
+    });
+    if (dot && dot_partials) *dot_partials = (int)tiles;
+    return CMI_SUCCESS;
+}
+
+// wave-private tiles, 16-byte-vector body, on the plan's row partition
+template <typename T>
+static int launch_wavev(const cmi_config &c, const cmi_plan *plan, int pol, hipStream_t s, int64_t nnz, const int *Ap, const int *Aj,
+                        const T *Ax, const T *x, T *y, int accumulate, const T *w, double *dot_partial, int *dot_partials)
+{
+    const int V = c.items_per_thread;
+    if (!plan || !plan->wave_row_start || plan->wave_q <= 0) return fail(CMI_ERROR_NOT_SUPPORTED, "CMI_CSR_STREAM_WAVEV runs through a plan (cmi_plan_create) only");
+    if (V != 1 && V != 2 && V != 4) return fail(CMI_ERROR_NOT_SUPPORTED, "csr_wavev: items_per_thread (index vectors per lane) must be 1, 2 or 4");
+    if (reinterpret_cast<uintptr_t>(Aj) % 16 != 0 || reinterpret_cast<uintptr_t>(Ax) % 16 != 0) return fail(CMI_ERROR_INVALID_VALUE, "csr_wavev: Aj and Ax must be 16-byte aligned");
+    const int64_t tiles = ceil_div(plan->wave_tiles, (int64_t)4);
+    const int64_t tpx = ceil_div(tiles, kXcds);
+    const int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
+    const int64_t grid64 = padded_grid(tiles, swz);
+    if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_wavev: grid too large");
+    const bool dot = w && dot_partial && tiles <= kPartialCapacity;
+    with_policy(pol, [&](auto P) {
+        with_int<1, 2, 4>(V, [&](auto VV) {
+            with_bool(dot, [&](auto DOT) {
+                hipLaunchKernelGGL((csr_wavev_kernel<T, decltype(VV)::value, decltype(P)::value, decltype(DOT)::value>), dim3((unsigned)grid64),
+                                   dim3(256), 0, s, plan->wave_row_start, plan->wave_tiles, nnz, Ap, Aj, Ax, x, y, tiles, tpx, swz, accumulate, w,
+                                   dot_partial);
+            });
+        });
+    });
+    if (dot && dot_partials) *dot_partials = (int)tiles;
+    return CMI_SUCCESS;
+}
+
+// csr_wavev + an x window in LDS per workgroup (gather-bound band matrices)
+template <typename T>
+static int launch_wavex(const cmi_config &c, const cmi_plan *plan, int pol, hipStream_t s, int64_t rows, int64_t cols, int64_t nnz,
+                        const int *Ap, const int *Aj, const T *Ax, const T *x, T *y, int accumulate, const T *w, double *dot_partial,
+                        int *dot_partials)
+{
+    const int V = c.items_per_thread;
+    if (!plan || !plan->wave_row_start || plan->wave_q <= 0) return fail(CMI_ERROR_NOT_SUPPORTED, "CMI_CSR_STREAM_WAVEX runs through a plan (cmi_plan_create) only");
+    if (V != 2 && V != 4) return fail(CMI_ERROR_NOT_SUPPORTED, "csr_wavex: items_per_thread (index vectors per lane) must be 2 or 4");
+    if (reinterpret_cast<uintptr_t>(Aj) % 16 != 0 || reinterpret_cast<uintptr_t>(Ax) % 16 != 0 || reinterpret_cast<uintptr_t>(x) % 16 != 0)
+        return fail(CMI_ERROR_INVALID_VALUE, "csr_wavex: Aj, Ax and x must be 16-byte aligned");
+    const int xe = 16 / (int)sizeof(T);
+    int window = c.rows_per_block > 0 ? c.rows_per_block : 4096; // (the config's rows_per_block field carries the window length for this kernel)
+    window = (window + 256 * xe - 1) / (256 * xe) * (256 * xe);
+    if (window > 8 * 256 * xe) window = 8 * 256 * xe;
+    const int64_t tiles = ceil_div(plan->wave_tiles, (int64_t)4);
+    const int64_t tpx = ceil_div(tiles, kXcds);
+    const int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
+    const int64_t grid64 = padded_grid(tiles, swz);
+    if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_wavex: grid too large");
+    const size_t lds = ((size_t)window + (size_t)4 * kWave * V * 4) * sizeof(T);
+    const bool dot = w && dot_partial && tiles <= kPartialCapacity;
+    with_policy(pol, [&](auto P) {
+        with_int<2, 4>(V, [&](auto VV) {
+            with_bool(dot, [&](auto DOT) {
+                hipLaunchKernelGGL((csr_wavex_kernel<T, decltype(VV)::value, decltype(P)::value, decltype(DOT)::value>), dim3((unsigned)grid64),
+                                   dim3(256), lds, s, plan->wave_row_start, plan->wave_tiles, nnz, rows, cols, Ap, Aj, Ax, x, y, tiles, tpx, swz,
+                                   accumulate, window, w, dot_partial);
+            });
+        });
+    });
+    if (dot && dot_partials) *dot_partials = (int)tiles;
+    return CMI_SUCCESS;
+}
+
+// the plan's run-compressed column copy on wave tiles (spmv_csr_runs.hip); Aj is read by the array-tail fall-back only
+template <typename T>
+static int launch_runs(const cmi_config &c, const cmi_plan *plan, int pol, hipStream_t s, const int *Ap, const int *Aj, const T *Ax,
+                       const T *x, T *y, int accumulate, const T *w, double *dot_partial, int *dot_partials)
+{
+    if (!plan) return fail(CMI_ERROR_NOT_SUPPORTED, "CMI_CSR_STREAM_WAVER / _PACKED run through a plan of cmi_plan_create_csr only");
+    if (plan->csr16_packed) { // stencil-like rows: packed wave tiles of the 16-bit copy (spmv_csr16.hip); neither Ap nor Aj nor Ax is read
+        if constexpr (std::is_same<T, double>::value) return csr16_multiply_f64(plan, Ap, Ax, x, y, accumulate, s, w, dot_partial, dot_partials, pol, c.xcd_swizzle);
+        else return csr16_multiply_f32(plan, Ap, Ax, x, y, accumulate, s, w, dot_partial, dot_partials, pol, c.xcd_swizzle);
+    }
+    if constexpr (std::is_same<T, double>::value) return csr_runs_multiply_f64(plan, Ap, Aj, Ax, x, y, accumulate, s, w, dot_partial, dot_partials, pol, c.xcd_swizzle);
+    else return csr_runs_multiply_f32(plan, Ap, Aj, Ax, x, y, accumulate, s, w, dot_partial, dot_partials, pol, c.xcd_swizzle);
+}
+
+// the plan's 16-bit column copy (spmv_csr16.hip); Aj itself is not read
+template <typename T>
+static int launch_c16(const cmi_config &c, const cmi_plan *plan, int pol, hipStream_t s, const int *Ap, const T *Ax, const T *x, T *y,
+                      int accumulate, const T *w, double *dot_partial, int *dot_partials)
+{
+    if (!plan || !plan->csr16_cols) return fail(CMI_ERROR_NOT_SUPPORTED, "CMI_CSR_STREAM_C16 runs through a plan of cmi_plan_create_csr only");
+    if (reinterpret_cast<uintptr_t>(Ax) % 16 != 0) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream_c16: values must be 16-byte aligned");
+    // (the stream kernel of the copy deals its fused dot's tiles as csr_stream does; the wave-tiled copy keeps the table's dealing)
+    const int swz = w && dot_partial && plan->csr16_wave_k == 0 ? dot_swizzle(c.xcd_swizzle, plan) : c.xcd_swizzle;
+    if constexpr (std::is_same<T, double>::value) return csr16_multiply_f64(plan, Ap, Ax, x, y, accumulate, s, w, dot_partial, dot_partials, pol, swz);
+    else return csr16_multiply_f32(plan, Ap, Ax, x, y, accumulate, s, w, dot_partial, dot_partials, pol, swz);
+}
+
+template <typename T>
+static int launch_pipe(const cmi_config &c, int pol, hipStream_t s, int64_t rows, int64_t nnz, const int *Ap, const int *Aj, const T *Ax,
+                       const T *x, T *y, int accumulate)
+{
+    const int block = c.block_size, rpb = c.rows_per_block;
+    if (rpb < 1 || rpb >= block) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream_pipe: rows_per_block must be in [1, block_size-1]");
+    const bool vec = (reinterpret_cast<uintptr_t>(Aj) % 16 == 0) && (reinterpret_cast<uintptr_t>(Ax) % 16 == 0);
+    if (!vec || nnz < 4) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream_pipe: needs 16-byte aligned Aj/Ax and >= 4 entries (use CMI_CSR_STREAM)");
+    const int64_t tiles = ceil_div(rows, rpb);
+    const size_t lds = 2 * ((size_t)block * 4 * sizeof(T) + (size_t)block * sizeof(int));
+    const int bpc = c.blocks_per_cu > 0 ? c.blocks_per_cu : 8;
+    int64_t grid64 = (int64_t)kCus * bpc;
+    if (grid64 > tiles) grid64 = tiles;
+    const int chunked = c.xcd_swizzle != 0;
+    with_policy(pol, [&](auto P) {
+        with_bool(accumulate != 0, [&](auto ACC) {
+            hipLaunchKernelGGL((csr_stream_pipe_kernel<T, decltype(P)::value, decltype(ACC)::value>), dim3((int)grid64), dim3(block), lds, s, rows,
+                               nnz, Ap, Aj, Ax, x, y, rpb, tiles, chunked);
+        });
+    });
+    return CMI_SUCCESS;
+}
+
+template <typename T>
+static int launch_balanced(const cmi_config &c, hipStream_t s, int64_t rows, int64_t nnz, const int *Ap, const int *Aj, const T *Ax,
+                           const T *x, T *y, int accumulate)
+{
+    if (rows + nnz > ((int64_t)1 << 40)) return fail(CMI_ERROR_INVALID_VALUE, "csr_balanced: matrix too large");
+    const int64_t tiles = ceil_div(rows + nnz, kBalItems);
+    // A workgroup walks `per` consecutive tiles (one search of the row offsets, then tile ends chain) and the
+    // workgroups are dealt in launch order, so the tiles in flight form ONE window sweeping the arrays --
+    // measured 2x faster than giving each of 2048 resident workgroups its own distant chunk (2048 DRAM fronts).
+    // blocks_per_cu > 0 asks for that persistent shape instead (grid = CUs * blocks_per_cu).
+    int64_t per = c.items_per_thread > 0 ? c.items_per_thread : 4;
+    int64_t grid64 = ceil_div(tiles, per);
+    if (c.blocks_per_cu > 0) {
+        grid64 = (int64_t)kCus * c.blocks_per_cu;
+        if (grid64 > tiles) grid64 = tiles;
+        per = ceil_div(tiles, grid64);
+    }
+    const int64_t chunks = grid64;
+    const int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
+    const int64_t cpx = ceil_div(chunks, kXcds);
+    grid64 = padded_grid(chunks, swz);
+    if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_balanced: grid too large");
+    if (!accumulate) // rows split across tiles are completed with atomics: they start from zero
+        hipLaunchKernelGGL((zero_fill_kernel<T>), dim3((unsigned)ceil_div(rows, 256)), dim3(256), 0, s, rows, y);
+    const bool vec = (reinterpret_cast<uintptr_t>(Aj) % 16 == 0) && (reinterpret_cast<uintptr_t>(Ax) % 16 == 0);
+    with_bool(vec, [&](auto VEC) {
+        hipLaunchKernelGGL((csr_balanced_kernel<T, decltype(VEC)::value>), dim3((unsigned)grid64), dim3(kBalBlock), 0, s, rows, nnz, Ap, Aj, Ax,
+                           x, y, tiles, per, accumulate, chunks, cpx, swz);
+    });
     return CMI_SUCCESS;
 }
 
@@ -1475,344 +1663,36 @@ static int spmv_csr(int dtype, int64_t rows, int64_t cols, int64_t nnz, const in
         }
     }
     hipStream_t s = as_stream(stream);
-    const int block = c.block_size;
     int pol = c.nontemporal & 3;
     // The fused <y, w> instance runs inside a solver, between vector kernels whose vectors (p, r, y: 240 MB) would fit the
     // 256 MiB Infinity Cache if the matrix streams did not push them out: here the once-read index / value streams carry the nt
     // hint whatever the table says for the stand-alone multiply (where plain loads measured equal or better).  CG iteration on the
     // headline matrix 263-268 -> 255-257 us, with the 16-bit column copy 248-251 -> 245-248 (archive/profiles/r02_cg_dot_policy.txt;
     // the y-store hint and load hints in the vector kernels measured no effect: r02_cg_y_store_policy.txt,
-    // r02_cg_vector_load_policy.txt).  $CMI_DOT_POLICY=0..3 overrides (measurements).
-    if (w && dot_partial) {
-        static const int dot_pol = [] { const char *e = std::getenv("CMI_DOT_POLICY"); return e ? std::atoi(e) & 3 : -1; }();
-        // (only for a matrix that does not itself fit the cache: see select_config's residency rule, tuning.hip)
-        const bool resident = nnz * (int64_t)(sizeof(int) + sizeof(T)) <= kInfinityCacheBytes + kInfinityCacheBytes / 4;
-        pol = dot_pol >= 0 ? dot_pol : resident ? pol : (pol | kPolLoadNT);
-    }
-    int st = CMI_SUCCESS;
+    // r02_cg_vector_load_policy.txt).  Only for a matrix that does not itself fit the cache: see select_config's residency rule,
+    // tuning.hip.
+    if (w && dot_partial && nnz * (int64_t)(sizeof(int) + sizeof(T)) > kInfinityCacheBytes + kInfinityCacheBytes / 4) pol |= kPolLoadNT;
 
+    int st;
     switch (c.kernel) {
-    case CMI_CSR_SCALAR: {
-        const int grid = grid_for(rows, block);
-        with_policy(pol, [&](auto P) {
-            hipLaunchKernelGGL((csr_scalar_kernel<T, decltype(P)::value>), dim3(grid), dim3(block), 0, s, rows, Ap, Aj, Ax, x, y, accumulate);
-        });
+    case CMI_CSR_SCALAR: st = launch_scalar(c, pol, s, rows, Ap, Aj, Ax, x, y, accumulate); break;
+    case CMI_CSR_VECTOR: st = launch_vector(c, pol, s, rows, Ap, Aj, Ax, x, y, accumulate); break;
+    case CMI_CSR_STREAM:
+        st = launch_stream(c, user, plan, known_max_len, pol, s, rows, nnz, Ap, Aj, Ax, x, y, accumulate, w, dot_partial, dot_partials);
         break;
-    }
-    case CMI_CSR_VECTOR: {
-        const int tpr = c.threads_per_row;
-        const int grid = grid_for(rows * tpr, block);
-        st = (pol & kPolLoadNT) ? launch_vector<T, true>(tpr, grid, block, s, rows, Ap, Aj, Ax, x, y, accumulate)
-                                : launch_vector<T, false>(tpr, grid, block, s, rows, Ap, Aj, Ax, x, y, accumulate);
-        if (st) return st;
+    case CMI_CSR_STREAM_WAVE: st = launch_wave(c, plan, pol, s, rows, Ap, Aj, Ax, x, y, accumulate, w, dot_partial, dot_partials); break;
+    case CMI_CSR_STREAM_WAVEV: st = launch_wavev(c, plan, pol, s, nnz, Ap, Aj, Ax, x, y, accumulate, w, dot_partial, dot_partials); break;
+    case CMI_CSR_STREAM_WAVEX:
+        st = launch_wavex(c, plan, pol, s, rows, cols, nnz, Ap, Aj, Ax, x, y, accumulate, w, dot_partial, dot_partials);
         break;
-    }
-    case CMI_CSR_STREAM: {
-        int rpb = c.rows_per_block;
-        const int ipt = c.items_per_thread;
-        // The fused <y, w> instance wants whole waves of rows: with the table's 176 rows per tile (2.75 waves) the dot costs
-        // +9.3 us on the headline matrix, with 192 (3 waves) +3.7 us (archive/tools/r2_probe.hip csrx flags 5 vs 1 at rpb 176 / 192,
-        // archive/profiles/r02_probe_dot_ablation.txt).  So a table-chosen shape (not a caller's explicit one) is rounded up to the
-        // next multiple of 64 rows when the tile's single LDS pass still holds them.
-        if (w && dot_partial && (!user || user->kernel == CMI_KERNEL_AUTO || user->rows_per_block == 0) && c.threads_per_row <= 1 && rows > 0) {
-            const int up = (rpb + kWave - 1) / kWave * kWave;
-            const double mean = (double)nnz / (double)rows;
-            const int64_t tile_entries = (int64_t)block * ipt * 4;
-            if (up != rpb && up <= block && (double)up * mean + 3.0 <= (double)tile_entries) rpb = up;
-        }
-        // ... and one partial per tile must fit the workspace: a table shape with small tiles (f32's 96 rows of 128 lanes at 10^7
-        // rows: 104 000 tiles) is doubled -- lanes and rows together, the same fill of the LDS pass -- until it does
-        int block = c.block_size; // (shadows the function's: the dot instance may widen it)
-        if (w && dot_partial && (!user || user->kernel == CMI_KERNEL_AUTO || user->rows_per_block == 0) && c.threads_per_row <= 1)
-            while (ceil_div(rows, rpb) > kPartialCapacity && block * 2 <= 1024) { block *= 2; rpb *= 2; }
-        int tpr = c.threads_per_row <= 1 ? 1 : c.threads_per_row;
-        if (tpr > 64 || (tpr & (tpr - 1)) != 0) return fail(CMI_ERROR_NOT_SUPPORTED, "csr_stream: threads_per_row must be 0/1 or a power of two <= 64");
-        // threads_per_row == 0: rows of kLongRowPerLane entries per lane of a group (at least kLongRowMin) or more
-        // are streamed by the whole workgroup (re-associated); == 1: storage order for every row, whatever its length
-        const int long_len = c.threads_per_row == 1 ? 0 : (tpr * kLongRowPerLane > kLongRowMin ? tpr * kLongRowPerLane : kLongRowMin);
-        if (rpb < 1 || rpb > 4 * (block / tpr)) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream: rows_per_block must be in [1, 4*block_size/threads_per_row]");
-        const int64_t tiles = ceil_div(rows, rpb);
-        const int64_t tpx = ceil_div(tiles, kXcds);
-        int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
-        // ... and its tiles go out in launch order: inside the solve that measured 2.3-3.5 us per iteration better than any chunk
-        // dealing, for every tile shape (tools/cg_dot_shape_probe.py, archive/profiles/r02_cg_dot_shape.txt) -- stand-alone it is the
-        // other way round (section 3.1 of DESIGN.md).  A caller's explicit shape is left alone; $CMI_DOT_SWIZZLE overrides.
-        if (w && dot_partial && (!user || user->kernel == CMI_KERNEL_AUTO)) swz = dot_swizzle(swz, plan);
-        const int64_t grid64 = swz == 0 ? tiles : swz == 1 ? tpx * kXcds : ceil_div(tiles, (int64_t)kXcds * swz) * kXcds * swz;
-        if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream: grid too large");
-        const size_t lds = (size_t)block * ipt * 4 * sizeof(T) + (size_t)(rpb + 1) * sizeof(int);
-        if (lds > 160 * 1024) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream: tile does not fit 160 KiB of LDS");
-        const bool vec = (reinterpret_cast<uintptr_t>(Aj) % 16 == 0) && (reinterpret_cast<uintptr_t>(Ax) % 16 == 0);
-        const bool dot = w && dot_partial && vec && tiles <= kPartialCapacity;
-        // the LONG instance only for a matrix whose plan shows such a row (no plan: the ordinary instance, which sums
-        // any row, one lane or lane group at a time -- correct, slow on a long row)
-        const bool lng = long_len > 0 && nnz >= long_len && known_max_len >= long_len;
-        const int strided = csr_lane_strided(c.nontemporal);
-        // row sums dealt round the waves ($CMI_CSR_SPREAD=1: row r -> wave r % W; =2: a contiguous chunk of rows per wave): MEASURED SLOWER on
-        // the long-row matrices it was meant for (ldoor-like 100 -> 110 us, nlpkkt120-like 213 -> 236 / 218 us, profiles/r03_long_rows_experiments.txt)
-        // -- lane r adds row r stays the default; the switch stays for measurements
-        static const int spread_env = [] { const char *e = std::getenv("CMI_CSR_SPREAD"); return e ? std::atoi(e) : 0; }();
-        const int spread = tpr == 1 ? spread_env : 0;
-        // f64 streams requested as (int2, double2) pairs instead of 16-byte vectors in the single-pass tile path: $CMI_CSR_PAIRS=0/1, else the
-        // config's policy bit kPolPairs
-        static const int pairs_env = [] { const char *e = std::getenv("CMI_CSR_PAIRS"); return e ? std::atoi(e) : -1; }();
-        const int pairs = pairs_env >= 0 ? pairs_env : ((c.nontemporal & kPolPairs) != 0);
-#define CMI_STREAM_GO(VEC_, DOT_, LONG_, ...) \
-    launch_stream_ipt<T, VEC_, POL, DOT_, LONG_>(ipt, (int)grid64, block, lds, s, rows, nnz, Ap, Aj, Ax, x, y, rpb, tiles, tpx, swz, accumulate, tpr, long_len, strided, spread, pairs, ##__VA_ARGS__)
-        with_policy(pol, [&](auto P) {
-            constexpr int POL = decltype(P)::value;
-            if (dot) {
-                st = lng ? CMI_STREAM_GO(true, true, true, w, dot_partial) : CMI_STREAM_GO(true, true, false, w, dot_partial);
-                return;
-            }
-            if (vec) st = lng ? CMI_STREAM_GO(true, false, true) : CMI_STREAM_GO(true, false, false);
-            else     st = lng ? CMI_STREAM_GO(false, false, true) : CMI_STREAM_GO(false, false, false);
-        });
-#undef CMI_STREAM_GO
-        if (st) return st;
-        if (dot && dot_partials) *dot_partials = (int)tiles;
-        break;
-    }
-    case CMI_CSR_STREAM_WAVE: {
-        const int K = c.items_per_thread;
-        if (plan && plan->wave_row_start) { // irregular short rows: the plan's partition (above)
-            if (K < 2 || K > kWaveTileMaxK) return fail(CMI_ERROR_NOT_SUPPORTED, "csr_wave: items_per_thread (entries per lane) must be 2..10");
-            const int64_t tiles = ceil_div(plan->wave_tiles, (int64_t)4);
-            const int64_t tpx = ceil_div(tiles, kXcds);
-            int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
-            if (w && dot_partial) swz = dot_swizzle(swz, plan, swz);
-            const int64_t grid64 = padded_grid(tiles, swz);
-            if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_wave: grid too large");
-            const bool dot = w && dot_partial && tiles <= kPartialCapacity;
-            with_policy(pol, [&](auto P) {
-                constexpr int POL = decltype(P)::value;
-                auto go = [&](auto KK) {
-                    constexpr int KC = decltype(KK)::value;
-                    if (dot) hipLaunchKernelGGL((csr_wavep_kernel<T, KC, POL, true>), dim3((unsigned)grid64), dim3(256), 0, s, plan->wave_row_start, plan->wave_tiles, Ap, Aj, Ax, x, y, tiles, tpx, swz, accumulate, w, dot_partial);
-                    else     hipLaunchKernelGGL((csr_wavep_kernel<T, KC, POL, false>), dim3((unsigned)grid64), dim3(256), 0, s, plan->wave_row_start, plan->wave_tiles, Ap, Aj, Ax, x, y, tiles, tpx, swz, accumulate, (const T *)nullptr, (double *)nullptr);
-                };
-                switch (K) {
-                case 2: go(std::integral_constant<int, 2>()); break;
-                case 3: go(std::integral_constant<int, 3>()); break;
-                case 4: go(std::integral_constant<int, 4>()); break;
-                case 5: go(std::integral_constant<int, 5>()); break;
-                case 6: go(std::integral_constant<int, 6>()); break;
-                case 7: go(std::integral_constant<int, 7>()); break;
-                case 8: go(std::integral_constant<int, 8>()); break;
-                case 9: go(std::integral_constant<int, 9>()); break;
-                default: go(std::integral_constant<int, 10>()); break;
-                }
-            });
-            if (dot && dot_partials) *dot_partials = (int)tiles;
-            break;
-        }
-        const int waves = block / kWave;
-        if (K < 2 || K > kWaveTileMaxK) return fail(CMI_ERROR_NOT_SUPPORTED, "csr_wave: items_per_thread (entries per lane) must be 2..10");
-        if (c.rows_per_block < waves || c.rows_per_block % waves != 0 || c.rows_per_block / waves > kWave)
-            return fail(CMI_ERROR_INVALID_VALUE, "csr_wave: rows_per_block must be block_size/64 waves x 1..64 rows each");
-        const int rpw = c.rows_per_block / waves;
-        const int64_t tiles = ceil_div(rows, (int64_t)c.rows_per_block);
-        const int64_t tpx = ceil_div(tiles, kXcds);
-        int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
-        // (the wave-tile kernel keeps the table's chunk dealing inside a solve too: 239 against 243.5 us per CG iteration in launch
-        //  order, archive/profiles/r02_cg_wave_dot.txt -- csr_stream's dot instance is the other way round)
-        if (w && dot_partial && (!user || user->kernel == CMI_KERNEL_AUTO)) swz = dot_swizzle(swz, plan, swz);
-        const int64_t grid64 = padded_grid(tiles, swz);
-        if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_wave: grid too large");
-        const size_t lds = (size_t)block * K * sizeof(T);
-        if (lds > 64 * 1024) return fail(CMI_ERROR_INVALID_VALUE, "csr_wave: block_size x items_per_thread products do not fit 64 KiB of LDS");
-        const bool dot = w && dot_partial && tiles <= kPartialCapacity;
-        static const int dot_ablate = [] { const char *e = std::getenv("CMI_DOT_ABLATE"); return e ? std::atoi(e) : 0; }();
-        with_policy(pol, [&](auto P) {
-            constexpr int POL = decltype(P)::value;
-            auto go = [&](auto KK) {
-                constexpr int KC = decltype(KK)::value;
-                if (dot) hipLaunchKernelGGL((csr_wave_kernel<T, KC, POL, true>), dim3((unsigned)grid64), dim3(block), lds, s, rows, Ap, Aj, Ax, x, y, rpw, tiles, tpx, swz, accumulate, w, dot_partial, dot_ablate);
-                else     hipLaunchKernelGGL((csr_wave_kernel<T, KC, POL, false>), dim3((unsigned)grid64), dim3(block), lds, s, rows, Ap, Aj, Ax, x, y, rpw, tiles, tpx, swz, accumulate, (const T *)nullptr, (double *)nullptr);
-            };
-            switch (K) {
-            case 2: go(std::integral_constant<int, 2>()); break;
-            case 3: go(std::integral_constant<int, 3>()); break;
-            case 4: go(std::integral_constant<int, 4>()); break;
-            case 5: go(std::integral_constant<int, 5>()); break;
-            case 6: go(std::integral_constant<int, 6>()); break;
-            case 7: go(std::integral_constant<int, 7>()); break;
-            case 8: go(std::integral_constant<int, 8>()); break;
-            case 9: go(std::integral_constant<int, 9>()); break;
-            default: go(std::integral_constant<int, 10>()); break;
-            }
-        });
-        if (dot && dot_partials) *dot_partials = (int)tiles;
-        break;
-    }
-    case CMI_CSR_STREAM_WAVEV: { // wave-private tiles, 16-byte-vector body, on the plan's row partition
-        const int V = c.items_per_thread;
-        if (!plan || !plan->wave_row_start || plan->wave_q <= 0) return fail(CMI_ERROR_NOT_SUPPORTED, "CMI_CSR_STREAM_WAVEV runs through a plan (cmi_plan_create) only");
-        if (V != 1 && V != 2 && V != 4) return fail(CMI_ERROR_NOT_SUPPORTED, "csr_wavev: items_per_thread (index vectors per lane) must be 1, 2 or 4");
-        if (reinterpret_cast<uintptr_t>(Aj) % 16 != 0 || reinterpret_cast<uintptr_t>(Ax) % 16 != 0) return fail(CMI_ERROR_INVALID_VALUE, "csr_wavev: Aj and Ax must be 16-byte aligned");
-        static const int wpb_env = [] { const char *e = std::getenv("CMI_WAVEV_WPB"); const int v = e ? std::atoi(e) : 4; return v == 1 || v == 2 ? v : 4; }();
-        const int wpb = V == 4 ? wpb_env : 4; // wave tiles per workgroup
-        const int64_t tiles = ceil_div(plan->wave_tiles, (int64_t)wpb);
-        const int64_t tpx = ceil_div(tiles, kXcds);
-        int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
-        const int64_t grid64 = padded_grid(tiles, swz);
-        if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_wavev: grid too large");
-        const bool dot = w && dot_partial && tiles <= kPartialCapacity;
-        if (wpb != 4) {
-            with_policy(pol, [&](auto P) {
-                constexpr int POL = decltype(P)::value;
-                auto go = [&](auto WW) {
-                    constexpr int WC = decltype(WW)::value;
-                    if (dot) hipLaunchKernelGGL((csr_wavev_kernel<T, 4, POL, true, 0, WC>), dim3((unsigned)grid64), dim3(kWave * WC), 0, s, plan->wave_row_start, plan->wave_tiles, nnz, Ap, Aj, Ax, x, y, tiles, tpx, swz, accumulate, w, dot_partial);
-                    else     hipLaunchKernelGGL((csr_wavev_kernel<T, 4, POL, false, 0, WC>), dim3((unsigned)grid64), dim3(kWave * WC), 0, s, plan->wave_row_start, plan->wave_tiles, nnz, Ap, Aj, Ax, x, y, tiles, tpx, swz, accumulate, (const T *)nullptr, (double *)nullptr);
-                };
-                if (wpb == 1) go(std::integral_constant<int, 1>()); else go(std::integral_constant<int, 2>());
-            });
-            if (dot && dot_partials) *dot_partials = (int)tiles;
-            break;
-        }
-        if constexpr (sizeof(T) == 8) { // measurements only: ablated instances (wrong results by design), f64 / V = 4 / nt loads and stores
-            static const int ablate = [] { const char *e = std::getenv("CMI_WAVEV_ABLATE"); return e ? std::atoi(e) : 0; }();
-            if (ablate > 0 && ablate < 16 && V == 4 && !dot) {
-                auto run = [&](auto A) {
-                    constexpr int AB = decltype(A)::value;
-                    hipLaunchKernelGGL((csr_wavev_kernel<T, 4, 3, false, AB>), dim3((unsigned)grid64), dim3(256), 0, s, plan->wave_row_start, plan->wave_tiles, nnz, Ap, Aj, Ax, x, y, tiles, tpx, swz, accumulate, (const T *)nullptr, (double *)nullptr);
-                };
-                switch (ablate) {
-                case 1: run(std::integral_constant<int, 1>()); break;
-                case 2: run(std::integral_constant<int, 2>()); break;
-                case 3: run(std::integral_constant<int, 3>()); break;
-                case 4: run(std::integral_constant<int, 4>()); break;
-                case 5: run(std::integral_constant<int, 5>()); break;
-                case 10: {
-                    static const int ldiv = [] { const char *e = std::getenv("CMI_WAVEV_LDIV"); return e ? std::atoi(e) : 1; }();
-                    auto run_l = [&](auto L) {
-                        constexpr int LD = decltype(L)::value;
-                        hipLaunchKernelGGL((csr_wavev_kernel<T, 4, 3, false, 10, 4, LD>), dim3((unsigned)grid64), dim3(256), 0, s, plan->wave_row_start, plan->wave_tiles, nnz, Ap, Aj, Ax, x, y, tiles, tpx, swz, accumulate, (const T *)nullptr, (double *)nullptr);
-                    };
-                    switch (ldiv) {
-                    case 2: run_l(std::integral_constant<int, 2>()); break;
-                    case 4: run_l(std::integral_constant<int, 4>()); break;
-                    case 8: run_l(std::integral_constant<int, 8>()); break;
-                    case 16: run_l(std::integral_constant<int, 16>()); break;
-                    default: run_l(std::integral_constant<int, 1>()); break;
-                    }
-                    break;
-                }
-                case 11: run(std::integral_constant<int, 11>()); break;
-                default: return fail(CMI_ERROR_NOT_SUPPORTED, "CMI_WAVEV_ABLATE: 1..5, 10, 11");
-                }
-                break;
-            }
-        }
-        with_policy(pol, [&](auto P) {
-            constexpr int POL = decltype(P)::value;
-            auto go = [&](auto VV) {
-                constexpr int VC = decltype(VV)::value;
-                if (dot) hipLaunchKernelGGL((csr_wavev_kernel<T, VC, POL, true>), dim3((unsigned)grid64), dim3(256), 0, s, plan->wave_row_start, plan->wave_tiles, nnz, Ap, Aj, Ax, x, y, tiles, tpx, swz, accumulate, w, dot_partial);
-                else     hipLaunchKernelGGL((csr_wavev_kernel<T, VC, POL, false>), dim3((unsigned)grid64), dim3(256), 0, s, plan->wave_row_start, plan->wave_tiles, nnz, Ap, Aj, Ax, x, y, tiles, tpx, swz, accumulate, (const T *)nullptr, (double *)nullptr);
-            };
-            switch (V) {
-            case 1: go(std::integral_constant<int, 1>()); break;
-            case 2: go(std::integral_constant<int, 2>()); break;
-            default: go(std::integral_constant<int, 4>()); break;
-            }
-        });
-        if (dot && dot_partials) *dot_partials = (int)tiles;
-        break;
-    }
-    case CMI_CSR_STREAM_WAVEX: { // csr_wavev + an x window in LDS per workgroup (gather-bound band matrices)
-        const int V = c.items_per_thread;
-        if (!plan || !plan->wave_row_start || plan->wave_q <= 0) return fail(CMI_ERROR_NOT_SUPPORTED, "CMI_CSR_STREAM_WAVEX runs through a plan (cmi_plan_create) only");
-        if (V != 2 && V != 4) return fail(CMI_ERROR_NOT_SUPPORTED, "csr_wavex: items_per_thread (index vectors per lane) must be 2 or 4");
-        if (reinterpret_cast<uintptr_t>(Aj) % 16 != 0 || reinterpret_cast<uintptr_t>(Ax) % 16 != 0 || reinterpret_cast<uintptr_t>(x) % 16 != 0)
-            return fail(CMI_ERROR_INVALID_VALUE, "csr_wavex: Aj, Ax and x must be 16-byte aligned");
-        const int xe = 16 / (int)sizeof(T);
-        int window = c.rows_per_block > 0 ? c.rows_per_block : 4096; // (the config's rows_per_block field carries the window length for this kernel)
-        window = (window + 256 * xe - 1) / (256 * xe) * (256 * xe);
-        if (window > 8 * 256 * xe) window = 8 * 256 * xe;
-        const int64_t tiles = ceil_div(plan->wave_tiles, (int64_t)4);
-        const int64_t tpx = ceil_div(tiles, kXcds);
-        const int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
-        const int64_t grid64 = padded_grid(tiles, swz);
-        if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_wavex: grid too large");
-        const size_t lds = ((size_t)window + (size_t)4 * kWave * V * 4) * sizeof(T);
-        const bool dot = w && dot_partial && tiles <= kPartialCapacity;
-        with_policy(pol, [&](auto P) {
-            constexpr int POL = decltype(P)::value;
-            auto go = [&](auto VV) {
-                constexpr int VC = decltype(VV)::value;
-                if (dot) hipLaunchKernelGGL((csr_wavex_kernel<T, VC, POL, true>), dim3((unsigned)grid64), dim3(256), lds, s, plan->wave_row_start, plan->wave_tiles, nnz, rows, cols, Ap, Aj, Ax, x, y, tiles, tpx, swz, accumulate, window, w, dot_partial);
-                else     hipLaunchKernelGGL((csr_wavex_kernel<T, VC, POL, false>), dim3((unsigned)grid64), dim3(256), lds, s, plan->wave_row_start, plan->wave_tiles, nnz, rows, cols, Ap, Aj, Ax, x, y, tiles, tpx, swz, accumulate, window, (const T *)nullptr, (double *)nullptr);
-            };
-            if (V == 2) go(std::integral_constant<int, 2>()); else go(std::integral_constant<int, 4>());
-        });
-        if (dot && dot_partials) *dot_partials = (int)tiles;
-        break;
-    }
     case CMI_CSR_STREAM_WAVER:
-    case CMI_CSR_STREAM_PACKED: { // the plan's run-compressed column copy on wave tiles (spmv_csr_runs.hip); Aj is read by the array-tail fall-back only
-        if (!plan) return fail(CMI_ERROR_NOT_SUPPORTED, "CMI_CSR_STREAM_WAVER / _PACKED run through a plan of cmi_plan_create_csr only");
-        if (plan->csr16_packed) { // stencil-like rows: packed wave tiles of the 16-bit copy (spmv_csr16.hip); neither Ap nor Aj nor Ax is read
-            const int swz16 = (w && dot_partial) ? dot_swizzle(c.xcd_swizzle, plan, c.xcd_swizzle) : c.xcd_swizzle;
-            if constexpr (std::is_same<T, double>::value) return csr16_multiply_f64(plan, Ap, Ax, x, y, accumulate, s, w, dot_partial, dot_partials, pol, swz16);
-            else return csr16_multiply_f32(plan, Ap, Ax, x, y, accumulate, s, w, dot_partial, dot_partials, pol, swz16);
-        }
-        if constexpr (std::is_same<T, double>::value) return csr_runs_multiply_f64(plan, Ap, Aj, Ax, x, y, accumulate, s, w, dot_partial, dot_partials, pol, c.xcd_swizzle);
-        else return csr_runs_multiply_f32(plan, Ap, Aj, Ax, x, y, accumulate, s, w, dot_partial, dot_partials, pol, c.xcd_swizzle);
-    }
-    case CMI_CSR_STREAM_C16: { // the plan's 16-bit column copy (spmv_csr16.hip); Aj itself is not read
-        if (!plan || !plan->csr16_cols) return fail(CMI_ERROR_NOT_SUPPORTED, "CMI_CSR_STREAM_C16 runs through a plan of cmi_plan_create_csr only");
-        if (reinterpret_cast<uintptr_t>(Ax) % 16 != 0) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream_c16: values must be 16-byte aligned");
-        if constexpr (std::is_same<T, double>::value) return csr16_multiply_f64(plan, Ap, Ax, x, y, accumulate, s, w, dot_partial, dot_partials, pol, (w && dot_partial) ? dot_swizzle(c.xcd_swizzle, plan, plan->csr16_wave_k > 0 ? c.xcd_swizzle : 0) : c.xcd_swizzle);
-        else return csr16_multiply_f32(plan, Ap, Ax, x, y, accumulate, s, w, dot_partial, dot_partials, pol, (w && dot_partial) ? dot_swizzle(c.xcd_swizzle, plan, plan->csr16_wave_k > 0 ? c.xcd_swizzle : 0) : c.xcd_swizzle);
-    }
-    case CMI_CSR_STREAM_PIPE: {
-        const int rpb = c.rows_per_block;
-        if (rpb < 1 || rpb >= block) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream_pipe: rows_per_block must be in [1, block_size-1]");
-        const bool vec = (reinterpret_cast<uintptr_t>(Aj) % 16 == 0) && (reinterpret_cast<uintptr_t>(Ax) % 16 == 0);
-        if (!vec || nnz < 4) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream_pipe: needs 16-byte aligned Aj/Ax and >= 4 entries (use CMI_CSR_STREAM)");
-        const int64_t tiles = ceil_div(rows, rpb);
-        const size_t lds = 2 * ((size_t)block * 4 * sizeof(T) + (size_t)block * sizeof(int));
-        const int bpc = c.blocks_per_cu > 0 ? c.blocks_per_cu : 8;
-        int64_t grid64 = (int64_t)kCus * bpc;
-        if (grid64 > tiles) grid64 = tiles;
-        const int chunked = c.xcd_swizzle != 0;
-        with_policy(pol, [&](auto P) {
-            constexpr int POL = decltype(P)::value;
-            if (accumulate) hipLaunchKernelGGL((csr_stream_pipe_kernel<T, POL, true>), dim3((int)grid64), dim3(block), lds, s, rows, nnz, Ap, Aj, Ax, x, y, rpb, tiles, chunked);
-            else            hipLaunchKernelGGL((csr_stream_pipe_kernel<T, POL, false>), dim3((int)grid64), dim3(block), lds, s, rows, nnz, Ap, Aj, Ax, x, y, rpb, tiles, chunked);
-        });
-        break;
-    }
-    case CMI_CSR_BALANCED: {
-        if (rows + nnz > ((int64_t)1 << 40)) return fail(CMI_ERROR_INVALID_VALUE, "csr_balanced: matrix too large");
-        const int64_t tiles = ceil_div(rows + nnz, kBalItems);
-        // A workgroup walks `per` consecutive tiles (one search of the row offsets, then tile ends chain) and the
-        // workgroups are dealt in launch order, so the tiles in flight form ONE window sweeping the arrays --
-        // measured 2x faster than giving each of 2048 resident workgroups its own distant chunk (2048 DRAM fronts).
-        // blocks_per_cu > 0 asks for that persistent shape instead (grid = CUs * blocks_per_cu).
-        int64_t per = c.items_per_thread > 0 ? c.items_per_thread : 4;
-        int64_t grid64 = ceil_div(tiles, per);
-        if (c.blocks_per_cu > 0) {
-            grid64 = (int64_t)kCus * c.blocks_per_cu;
-            if (grid64 > tiles) grid64 = tiles;
-            per = ceil_div(tiles, grid64);
-        }
-        const int64_t chunks = grid64;
-        const int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
-        const int64_t cpx = ceil_div(chunks, kXcds);
-        grid64 = padded_grid(chunks, swz);
-        if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_balanced: grid too large");
-        if (!accumulate) // rows split across tiles are completed with atomics: they start from zero
-            hipLaunchKernelGGL((zero_fill_kernel<T>), dim3((unsigned)ceil_div(rows, 256)), dim3(256), 0, s, rows, y);
-        const bool vec = (reinterpret_cast<uintptr_t>(Aj) % 16 == 0) && (reinterpret_cast<uintptr_t>(Ax) % 16 == 0);
-        if (vec) hipLaunchKernelGGL((csr_balanced_kernel<T, true>), dim3((unsigned)grid64), dim3(kBalBlock), 0, s, rows, nnz, Ap, Aj, Ax, x, y, tiles, per, accumulate, chunks, cpx, swz);
-        else     hipLaunchKernelGGL((csr_balanced_kernel<T, false>), dim3((unsigned)grid64), dim3(kBalBlock), 0, s, rows, nnz, Ap, Aj, Ax, x, y, tiles, per, accumulate, chunks, cpx, swz);
-        break;
-    }
+    case CMI_CSR_STREAM_PACKED: return launch_runs(c, plan, pol, s, Ap, Aj, Ax, x, y, accumulate, w, dot_partial, dot_partials); // (checks its launch)
+    case CMI_CSR_STREAM_C16: return launch_c16(c, plan, pol, s, Ap, Ax, x, y, accumulate, w, dot_partial, dot_partials);         // (checks its launch)
+    case CMI_CSR_STREAM_PIPE: st = launch_pipe(c, pol, s, rows, nnz, Ap, Aj, Ax, x, y, accumulate); break;
+    case CMI_CSR_BALANCED: st = launch_balanced(c, s, rows, nnz, Ap, Aj, Ax, x, y, accumulate); break;
     default: return fail(CMI_ERROR_NOT_SUPPORTED, "cmi_spmv_csr: config.kernel is not a CSR kernel");
     }
+    if (st) return st;
     CMI_LAUNCH_CHECK("csr spmv");
     return CMI_SUCCESS;
 }

@@ -442,24 +442,13 @@ static int csr16_multiply(const cmi_plan *p, const int *Ap, const T *Ax, const T
         if (wgrid > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream_packed: grid too large");
         const size_t wlds = (size_t)wblock * K * sizeof(T);
         const bool wdot = w && dot_partial && wtiles <= kPartialCapacity;
-        with_policy(pol & 3, [&](auto P) {
-            constexpr int POL = decltype(P)::value;
-            auto go = [&](auto KK) {
-                constexpr int KC = decltype(KK)::value;
-                if (wdot) hipLaunchKernelGGL((csr_wave16p_kernel<T, KC, POL, true>), dim3((unsigned)wgrid), dim3(wblock), wlds, s, rows, p->csr16_packed, x, y, wtiles, wtpx, wswz, accumulate, w, dot_partial);
-                else      hipLaunchKernelGGL((csr_wave16p_kernel<T, KC, POL, false>), dim3((unsigned)wgrid), dim3(wblock), wlds, s, rows, p->csr16_packed, x, y, wtiles, wtpx, wswz, accumulate, (const T *)nullptr, (double *)nullptr);
-            };
-            switch (K) {
-            case 2: go(std::integral_constant<int, 2>()); break;
-            case 3: go(std::integral_constant<int, 3>()); break;
-            case 4: go(std::integral_constant<int, 4>()); break;
-            case 5: go(std::integral_constant<int, 5>()); break;
-            case 6: go(std::integral_constant<int, 6>()); break;
-            case 7: go(std::integral_constant<int, 7>()); break;
-            case 8: go(std::integral_constant<int, 8>()); break;
-            case 9: go(std::integral_constant<int, 9>()); break;
-            default: go(std::integral_constant<int, 10>()); break;
-            }
+        with_policy(pol, [&](auto P) {
+            with_int<2, 3, 4, 5, 6, 7, 8, 9, 10>(K, [&](auto KK) { // (csr16_wave_k: the longest row, 2..10, plan.hip wave_tiles_fit)
+                with_bool(wdot, [&](auto DOT) {
+                    hipLaunchKernelGGL((csr_wave16p_kernel<T, decltype(KK)::value, decltype(P)::value, decltype(DOT)::value>), dim3((unsigned)wgrid), dim3(wblock),
+                                       wlds, s, rows, p->csr16_packed, x, y, wtiles, wtpx, wswz, accumulate, w, dot_partial);
+                });
+            });
         });
         CMI_LAUNCH_CHECK("csr_wave16p spmv");
         if (wdot && dot_partials) *dot_partials = (int)wtiles;
@@ -474,24 +463,13 @@ static int csr16_multiply(const cmi_plan *p, const int *Ap, const T *Ax, const T
         if (wgrid > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream_c16: grid too large");
         const size_t wlds = (size_t)wblock * K * sizeof(T);
         const bool wdot = w && dot_partial && wtiles <= kPartialCapacity;
-        with_policy(pol & 3, [&](auto P) {
-            constexpr int POL = decltype(P)::value;
-            auto go = [&](auto KK) {
-                constexpr int KC = decltype(KK)::value;
-                if (wdot) hipLaunchKernelGGL((csr_wave16_kernel<T, KC, POL, true>), dim3((unsigned)wgrid), dim3(wblock), wlds, s, rows, Ap, p->csr16_cols, p->csr16_base, Ax, x, y, wtiles, wtpx, wswz, accumulate, w, dot_partial);
-                else      hipLaunchKernelGGL((csr_wave16_kernel<T, KC, POL, false>), dim3((unsigned)wgrid), dim3(wblock), wlds, s, rows, Ap, p->csr16_cols, p->csr16_base, Ax, x, y, wtiles, wtpx, wswz, accumulate, (const T *)nullptr, (double *)nullptr);
-            };
-            switch (K) {
-            case 2: go(std::integral_constant<int, 2>()); break;
-            case 3: go(std::integral_constant<int, 3>()); break;
-            case 4: go(std::integral_constant<int, 4>()); break;
-            case 5: go(std::integral_constant<int, 5>()); break;
-            case 6: go(std::integral_constant<int, 6>()); break;
-            case 7: go(std::integral_constant<int, 7>()); break;
-            case 8: go(std::integral_constant<int, 8>()); break;
-            case 9: go(std::integral_constant<int, 9>()); break;
-            default: go(std::integral_constant<int, 10>()); break;
-            }
+        with_policy(pol, [&](auto P) {
+            with_int<2, 3, 4, 5, 6, 7, 8, 9, 10>(K, [&](auto KK) { // (csr16_wave_k: the longest row, 2..10, plan.hip wave_tiles_fit)
+                with_bool(wdot, [&](auto DOT) {
+                    hipLaunchKernelGGL((csr_wave16_kernel<T, decltype(KK)::value, decltype(P)::value, decltype(DOT)::value>), dim3((unsigned)wgrid), dim3(wblock),
+                                       wlds, s, rows, Ap, p->csr16_cols, p->csr16_base, Ax, x, y, wtiles, wtpx, wswz, accumulate, w, dot_partial);
+                });
+            });
         });
         CMI_LAUNCH_CHECK("csr_wave16 spmv");
         if (wdot && dot_partials) *dot_partials = (int)wtiles;
@@ -505,23 +483,18 @@ static int csr16_multiply(const cmi_plan *p, const int *Ap, const T *Ax, const T
     const size_t lds = (size_t)block * ipt * 4 * sizeof(T);
     if (lds > 160 * 1024) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream_c16: tile does not fit 160 KiB of LDS");
     const bool dot = w && dot_partial && tiles <= kPartialCapacity;
-    const int strided = csr_lane_strided(c.nontemporal);
-    int st = CMI_SUCCESS;
-    with_policy(pol & 3, [&](auto P) {
-        constexpr int POL = decltype(P)::value;
-        auto go = [&](auto I) {
-            constexpr int IPT = decltype(I)::value;
-            if (dot) hipLaunchKernelGGL((csr_stream16_kernel<T, IPT, POL, true>), dim3((unsigned)grid64), dim3(block), lds, s, rows, nnz, (int)p->cols, Ap, p->csr16_cols, p->csr16_base, Ax, x, y, rpb, tiles, tpx, swz, accumulate, strided, w, dot_partial);
-            else     hipLaunchKernelGGL((csr_stream16_kernel<T, IPT, POL, false>), dim3((unsigned)grid64), dim3(block), lds, s, rows, nnz, (int)p->cols, Ap, p->csr16_cols, p->csr16_base, Ax, x, y, rpb, tiles, tpx, swz, accumulate, strided, (const T *)nullptr, (double *)nullptr);
-        };
-        switch (ipt) {
-        case 1: go(std::integral_constant<int, 1>()); break;
-        case 2: go(std::integral_constant<int, 2>()); break;
-        case 4: go(std::integral_constant<int, 4>()); break;
-        default: st = fail(CMI_ERROR_NOT_SUPPORTED, "csr_stream_c16: items_per_thread must be 1, 2 or 4"); break;
-        }
+    const int strided = (c.nontemporal & kPolStrided) != 0;
+    bool launched = false;
+    with_policy(pol, [&](auto P) {
+        launched = with_int<1, 2, 4>(ipt, [&](auto I) {
+            with_bool(dot, [&](auto DOT) {
+                hipLaunchKernelGGL((csr_stream16_kernel<T, decltype(I)::value, decltype(P)::value, decltype(DOT)::value>), dim3((unsigned)grid64),
+                                   dim3(block), lds, s, rows, nnz, (int)p->cols, Ap, p->csr16_cols, p->csr16_base, Ax, x, y, rpb, tiles, tpx, swz,
+                                   accumulate, strided, w, dot_partial);
+            });
+        });
     });
-    if (st) return st;
+    if (!launched) return fail(CMI_ERROR_NOT_SUPPORTED, "csr_stream_c16: items_per_thread must be 1, 2 or 4");
     CMI_LAUNCH_CHECK("csr_stream_c16 spmv");
     if (dot && dot_partials) *dot_partials = (int)tiles;
     return CMI_SUCCESS;

@@ -215,9 +215,7 @@ int csr_runs_build(cmi_plan *p, const int *Ap, const int *Aj, int v, double min_
     // Pieces of at most 4 or at most 3 entries?  Three degrees of freedom per node give runs of 3, 6, 9 ...: cut at 4 they become 4 + 2,
     // 4 + 4 + 1 -- no fewer pieces than cut at 3, and the pieces of 4 park their x values 32 bytes apart in LDS (a 4-way bank conflict
     // where pieces of 3 have none; profiles/r04_long_rows_pmc.json: LDS index unit 71 % busy on ldoor-like).  Cap 3 when it costs at most
-    // 3 % more pieces than cap 4 ($CMI_WAVER_CAP=3 / 4 forces).  One walk counts both.
-    static const int cap_env_ = [] { const char *ev = std::getenv("CMI_WAVER_CAP"); return ev ? std::atoi(ev) : 0; }();
-    const int cap_env = (cap_asked == 3 || cap_asked == 4) ? cap_asked : cap_env_; // (a plan that asks: config.threads_per_row)
+    // 3 % more pieces than cap 4, unless `cap_asked` (a plan's config.threads_per_row, else the rule's cap) is 3 or 4.  One walk counts both.
     int cap = kRunCap;
     if (e == hipSuccess) {
         hipLaunchKernelGGL((runs_tile_kernel<false>), dim3(tgrid), dim3(256), 0, s, rows, Ap, Aj, rpb, kRunCap, count, count3, totals, (const int *)nullptr, (uint32_t *)nullptr);
@@ -225,7 +223,7 @@ int csr_runs_build(cmi_plan *p, const int *Ap, const int *Aj, int v, double min_
     }
     if (e == hipSuccess) e = hipMemcpyAsync(host_totals, totals, sizeof(host_totals), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && (cap_env == 3 || (cap_env != 4 && (double)host_totals[1] <= 1.03 * (double)host_totals[0]))) cap = 3;
+    if (e == hipSuccess && (cap_asked == 3 || (cap_asked != 4 && (double)host_totals[1] <= 1.03 * (double)host_totals[0]))) cap = 3;
     if (totals) (void)hipFree(totals);
     int *chosen = cap == 3 ? count3 : count; // the per-row counts that are scanned, in place, into piece offsets
     int st = e == hipSuccess ? (int)CMI_SUCCESS : hip_fail(e, "cmi_plan_create: run-compressed columns");
@@ -312,10 +310,8 @@ __global__ void __launch_bounds__(256)
 csr_waver_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t num_entries, int num_cols, const int *Ap /* not restrict: see csr_wave */,
                  const int *__restrict__ Aj, const uint32_t *__restrict__ pieces, const T *__restrict__ Ax, const unsigned char *__restrict__ packed,
                  const T *__restrict__ x, T *__restrict__ y, int64_t num_tiles, int64_t tiles_per_xcd, int swizzle, int accumulate,
-                 const T *__restrict__ w, double *__restrict__ dot_partial, int ablate = 0)
+                 const T *__restrict__ w, double *__restrict__ dot_partial)
 {
-    // ablate (measurements only, $CMI_WAVER_ABLATE; WRONG results by design): bit 1 -- no product stage (the rows sum the parked x values; the
-    // value loads stay needed: added to lane 0's row); bit 2 -- a row's lane reads only its first slot (no sum phase)
     // f64: E = 2 values per 16-byte load, 2 V loads per lane; f32: E = 4, V loads per lane -- 256 V slots per tile either way
     constexpr int E = 16 / (int)sizeof(T), NL = (V * 4) / E, SLOTS = kWave * V * 4, NPC = V == 4 ? 6 : V == 2 ? 3 : 2;
     typedef T __attribute__((ext_vector_type(E))) val_t;
@@ -413,23 +409,14 @@ csr_waver_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t 
                 asm volatile("" : "+v"(a)); // the row offset was requested in front of the streams
                 __builtin_amdgcn_wave_barrier(); // (compiler only: the hardware runs a wave's LDS instructions in order)
                 // ---- products, in place: lane l owns the slot pairs l, l + 64, ... ----
-                if (ablate & 1) { // (uniform) the values must stay NEEDED, or the compiler drops their loads
-                    T keep = T(0);
 #pragma unroll
-                    for (int k = 0; k < NL; k++)
+                for (int k = 0; k < NL; k++) {
+                    val_t *slot = reinterpret_cast<val_t *>(mine + (k * kWave + lane) * E);
+                    const val_t xs = *slot;
+                    val_t pr;
 #pragma unroll
-                        for (int i = 0; i < E; i++) keep = keep + v[k][i];
-                    if (keep == T(12345.678)) mine[0] = keep;
-                } else {
-#pragma unroll
-                    for (int k = 0; k < NL; k++) {
-                        val_t *slot = reinterpret_cast<val_t *>(mine + (k * kWave + lane) * E);
-                        const val_t xs = *slot;
-                        val_t pr;
-#pragma unroll
-                        for (int i = 0; i < E; i++) pr[i] = v[k][i] * xs[i];
-                        *slot = pr;
-                    }
+                    for (int i = 0; i < E; i++) pr[i] = v[k][i] * xs[i];
+                    *slot = pr;
                 }
                 __builtin_amdgcn_wave_barrier();
             }
@@ -438,8 +425,7 @@ csr_waver_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t 
             for (int r = lane; r < nr; r += kWave) { // (one turn, except over a stretch of very short rows)
                 if (r >= kWave) { a = Ap[rs + r]; b = Ap[rs + r + 1]; }
                 T sum = accumulate ? y[rs + r] : T(0);
-                if (fits && (ablate & 2)) { if (b > a) sum = sum + mine[a - slot0]; }
-                else if (fits) sum = sum_in_order(sum, mine + (a - slot0), b - a);
+                if (fits) sum = sum_in_order(sum, mine + (a - slot0), b - a);
                 else for (int j = a; j < b; j++) sum = sum + Ax[j] * x[Aj[j]]; // (the array's last pair, or an empty tile)
                 st<NTS>(y + rs + r, sum);
                 if constexpr (DOT) d += (double)sum * (double)w[rs + r];
@@ -469,23 +455,16 @@ static int csr_runs_multiply(const cmi_plan *p, const int *Ap, const int *Aj, co
     const int64_t grid64 = padded_grid(tiles, swz);
     if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_waver: grid too large");
     const bool dot = w && dot_partial && tiles <= kPartialCapacity;
-    static const int ablate = [] { const char *e = std::getenv("CMI_WAVER_ABLATE"); return e ? std::atoi(e) : 0; }();
     with_policy(pol, [&](auto P) {
-        constexpr int POL = decltype(P)::value;
-        auto go = [&](auto VV, auto PK) {
-            constexpr int VC = decltype(VV)::value;
-            constexpr bool PKC = decltype(PK)::value;
-            if (dot) hipLaunchKernelGGL((csr_waver_kernel<T, VC, POL, true, PKC>), dim3((unsigned)grid64), dim3(256), 0, s, p->runs_start, p->wave_tiles, p->nnz, (int)p->cols, Ap, Aj, p->runs_pieces, Ax, p->runs_packed, x, y, tiles, tpx, swz, accumulate, w, dot_partial);
-            else     hipLaunchKernelGGL((csr_waver_kernel<T, VC, POL, false, PKC>), dim3((unsigned)grid64), dim3(256), 0, s, p->runs_start, p->wave_tiles, p->nnz, (int)p->cols, Ap, Aj, p->runs_pieces, Ax, p->runs_packed, x, y, tiles, tpx, swz, accumulate, (const T *)nullptr, (double *)nullptr, ablate);
-        };
-        auto by_v = [&](auto PK) {
-            switch (V) {
-            case 1: go(std::integral_constant<int, 1>(), PK); break;
-            case 2: go(std::integral_constant<int, 2>(), PK); break;
-            default: go(std::integral_constant<int, 4>(), PK); break;
-            }
-        };
-        if (packed) by_v(std::true_type()); else by_v(std::false_type());
+        with_int<1, 2, 4>(V, [&](auto VV) {
+            with_bool(packed, [&](auto PK) {
+                with_bool(dot, [&](auto DOT) {
+                    hipLaunchKernelGGL((csr_waver_kernel<T, decltype(VV)::value, decltype(P)::value, decltype(DOT)::value, decltype(PK)::value>),
+                                       dim3((unsigned)grid64), dim3(256), 0, s, p->runs_start, p->wave_tiles, p->nnz, (int)p->cols, Ap, Aj, p->runs_pieces,
+                                       Ax, p->runs_packed, x, y, tiles, tpx, swz, accumulate, w, dot_partial);
+                });
+            });
+        });
     });
     if (dot && dot_partials) *dot_partials = (int)tiles;
     CMI_LAUNCH_CHECK("csr_waver");

@@ -14,16 +14,8 @@
 // Algorithmic bytes per call (f64):
 //   ELL: width*pitch*(4+8) + 16*num_rows        DIA: ndiag*pitch*8 + 4*ndiag + 16*num_rows
 #include "common.h"
-#include <cstdlib>
 
 namespace cmi {
-
-// $CMI_DOT_SWIZZLE: XCD dealing of the fused <y, w> instances with a table shape (measurements; unset: the table's dealing)
-static int dot_swizzle_env(int table_swizzle)
-{
-    static const int env = [] { const char *e = std::getenv("CMI_DOT_SWIZZLE"); return e ? std::atoi(e) : -1; }();
-    return env >= 0 ? env : table_swizzle;
-}
 
 // ---------------------------------------------------------------------------------------------
 // ELL: one lane per row (RPL rows per lane)
@@ -371,54 +363,40 @@ static int spmv_ell(int dtype, int64_t rows, int64_t cols, int64_t width, int64_
         if (g64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_ell: grid too large");
         const int g = (int)g64, wd = (int)width;
         with_policy(pol, [&](auto P) {
-            constexpr int POL = decltype(P)::value;
-            auto go = [&](auto Sc) {
-                constexpr int S = decltype(Sc)::value;
-                if (ellr) hipLaunchKernelGGL((ell_slices_kernel<T, S, true, POL>), dim3(g), dim3(block), 0, s, rows, wd, pitch, Aj, Ax, row_lengths, x, y, accumulate);
-                else      hipLaunchKernelGGL((ell_slices_kernel<T, S, false, POL>), dim3(g), dim3(block), 0, s, rows, wd, pitch, Aj, Ax, row_lengths, x, y, accumulate);
-            };
-            switch (lanes) {
-            case 2: go(std::integral_constant<int, 2>()); break;
-            case 4: go(std::integral_constant<int, 4>()); break;
-            case 8: go(std::integral_constant<int, 8>()); break;
-            default: go(std::integral_constant<int, 16>()); break;
-            }
+            with_int<2, 4, 8, 16>(lanes, [&](auto S) { // (ell_lanes_per_row: a power of two, at most 16)
+                with_bool(ellr, [&](auto ELLR) {
+                    hipLaunchKernelGGL((ell_slices_kernel<T, decltype(S)::value, decltype(ELLR)::value, decltype(P)::value>), dim3(g), dim3(block), 0, s,
+                                       rows, wd, pitch, Aj, Ax, row_lengths, x, y, accumulate);
+                });
+            });
         });
         CMI_LAUNCH_CHECK("ell slices spmv");
         return CMI_SUCCESS;
     }
     const int64_t tiles = ceil_div(rows, (int64_t)block * rpl); // one-shot grid (see spmv_csr.hip grid_for), padded to chunk rounds
-    int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
-    if (wdot && dot_partial && (!user || user->kernel == CMI_KERNEL_AUTO)) swz = dot_swizzle_env(swz); // (experiment knob: $CMI_DOT_SWIZZLE)
+    const int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
     const int64_t tpx = ceil_div(tiles, kXcds);
     const int64_t grid64 = padded_grid(tiles, swz);
     if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_ell: grid too large");
     const int grid = (int)grid64;
     const int w = (int)width;
-#define CMI_ELL_LAUNCH(RPL, ELLR)                                                                             \
-    with_policy(pol, [&](auto P) {                                                                                \
-        hipLaunchKernelGGL((ell_row_kernel<T, RPL, ELLR, decltype(P)::value>), dim3(grid), dim3(block), 0, s, rows, w, \
-                           pitch, Aj, Ax, row_lengths, x, y, accumulate, tiles, tpx, swz);                        \
-    })
-#define CMI_ELL_LAUNCH_DOT(RPL, ELLR)                                                                         \
-    with_policy(pol, [&](auto P) {                                                                                \
-        hipLaunchKernelGGL((ell_row_kernel<T, RPL, ELLR, decltype(P)::value, true>), dim3(grid), dim3(block), 0, s, rows, w, \
-                           pitch, Aj, Ax, row_lengths, x, y, accumulate, tiles, tpx, swz, wdot, dot_partial);     \
-    })
     const bool dot = wdot && dot_partial && tiles <= kPartialCapacity; // one partial per tile (a double, whatever T)
-    {
-        if (dot) {
-            if (rpl == 1) { if (ellr) CMI_ELL_LAUNCH_DOT(1, true); else CMI_ELL_LAUNCH_DOT(1, false); }
-            else          { if (ellr) CMI_ELL_LAUNCH_DOT(2, true); else CMI_ELL_LAUNCH_DOT(2, false); }
-            CMI_LAUNCH_CHECK("ell spmv dot");
-            if (dot_partials) *dot_partials = (int)tiles;
-            return CMI_SUCCESS;
-        }
+    with_policy(pol, [&](auto P) {
+        with_int<1, 2>(rpl, [&](auto RPL) {
+            with_bool(ellr, [&](auto ELLR) {
+                with_bool(dot, [&](auto DOT) {
+                    hipLaunchKernelGGL((ell_row_kernel<T, decltype(RPL)::value, decltype(ELLR)::value, decltype(P)::value, decltype(DOT)::value>),
+                                       dim3(grid), dim3(block), 0, s, rows, w, pitch, Aj, Ax, row_lengths, x, y, accumulate, tiles, tpx, swz, wdot,
+                                       dot_partial);
+                });
+            });
+        });
+    });
+    if (dot) {
+        CMI_LAUNCH_CHECK("ell spmv dot");
+        if (dot_partials) *dot_partials = (int)tiles;
+        return CMI_SUCCESS;
     }
-    if (rpl == 1) { if (ellr) CMI_ELL_LAUNCH(1, true); else CMI_ELL_LAUNCH(1, false); }
-    else          { if (ellr) CMI_ELL_LAUNCH(2, true); else CMI_ELL_LAUNCH(2, false); }
-#undef CMI_ELL_LAUNCH_DOT
-#undef CMI_ELL_LAUNCH
     CMI_LAUNCH_CHECK("ell spmv");
     return CMI_SUCCESS;
 }
@@ -446,24 +424,19 @@ static int spmv_dia(int dtype, int64_t rows, int64_t cols, int64_t ndiag, int64_
     if (wdot && dot_partial) // one partial per workgroup: widen the workgroups until they fit the workspace
         while (block < 1024 && ceil_div(rows, (int64_t)block * rpl) > kPartialCapacity) block *= 2;
     const int64_t tiles = ceil_div(rows, (int64_t)block * rpl);
-    int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
-    if (wdot && dot_partial && (!user || user->kernel == CMI_KERNEL_AUTO)) swz = dot_swizzle_env(swz); // (experiment knob: $CMI_DOT_SWIZZLE)
+    const int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
     const int64_t tpx = ceil_div(tiles, kXcds);
     const int64_t grid64 = padded_grid(tiles, swz);
     if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_dia: grid too large");
     const int grid = (int)grid64, nd = (int)ndiag;
     const bool dot = wdot && dot_partial && tiles <= kPartialCapacity;
     with_policy(pol, [&](auto P) {
-        constexpr int POL = decltype(P)::value;
-        {
-            if (dot) {
-                if (rpl == 1) hipLaunchKernelGGL((dia_row_kernel<T, POL, true>), dim3(grid), dim3(block), 0, s, rows, cols, nd, pitch, offsets, vals, x, y, accumulate, tiles, tpx, swz, wdot, dot_partial);
-                else          hipLaunchKernelGGL((dia_row2_kernel<T, POL, true>), dim3(grid), dim3(block), 0, s, rows, cols, nd, pitch, offsets, vals, x, y, accumulate, tiles, tpx, swz, wdot, dot_partial);
-                return;
-            }
-        }
-        if (rpl == 1) hipLaunchKernelGGL((dia_row_kernel<T, POL>), dim3(grid), dim3(block), 0, s, rows, cols, nd, pitch, offsets, vals, x, y, accumulate, tiles, tpx, swz);
-        else          hipLaunchKernelGGL((dia_row2_kernel<T, POL>), dim3(grid), dim3(block), 0, s, rows, cols, nd, pitch, offsets, vals, x, y, accumulate, tiles, tpx, swz);
+        with_bool(dot, [&](auto DOT) {
+            constexpr int POL = decltype(P)::value;
+            constexpr bool D = decltype(DOT)::value;
+            if (rpl == 1) hipLaunchKernelGGL((dia_row_kernel<T, POL, D>), dim3(grid), dim3(block), 0, s, rows, cols, nd, pitch, offsets, vals, x, y, accumulate, tiles, tpx, swz, wdot, dot_partial);
+            else          hipLaunchKernelGGL((dia_row2_kernel<T, POL, D>), dim3(grid), dim3(block), 0, s, rows, cols, nd, pitch, offsets, vals, x, y, accumulate, tiles, tpx, swz, wdot, dot_partial);
+        });
     });
     CMI_LAUNCH_CHECK("dia spmv");
     if (dot && dot_partials) *dot_partials = (int)tiles;

@@ -1553,8 +1553,8 @@ def test_suitesparse_like_matrices_every_kernel(cmi, torch_cuda, orc, name, scal
 
 
 def test_fold_handoff_is_stable_under_load(cmi, torch_cuda):
-    """The multi-workgroup fold of a long partial list hands its chunk sums to the last-arriving workgroup with write-through
-    stores, a drained counter add and sc1 loads -- no agent-scope fences (blas1.hip dot_fold_final_kernel).  A stale or torn
+    """The multi-workgroup fold of a long partial list hands its chunk sums to the last-arriving workgroup: payload store, agent-scope
+    release fence, relaxed counter add, and an agent-scope acquire fence in the last arriver (blas1.hip fold_handoff).  A stale or torn
     hand-off would change the scalar: thousands of folds, idle and beside a streaming kernel on another stream (uneven load,
     consumer caches warm), must all return the first call's bits; so must the fused SpMV + <y, w> and cg_update."""
     torch = torch_cuda
