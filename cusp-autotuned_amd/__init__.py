@@ -25,6 +25,8 @@ from .binding import (  # noqa: F401
     csr_to_ell, csr_to_hyb_coo, csr_row_indices, coo_row_offsets, coo_sort_by_row, coo_is_sorted, csr_interior_rows, ell_to_csr, dia_to_csr, hyb_to_csr, ell_row_lengths,
     blas_axpy, blas_axpby, blas_copy, blas_fill, blas_dot, blas_dotd, blas_nrm2, blas_workspace,
     cg_update, cg_direction, cg_direction_x, HostScalar,
+    blas_scal, blas_xmy, blas_axpbypcz, blas_asum, blas_amax, blas_axpy_dot, blas_axpy_ratio, csr_diagonal,
+    pcg_update_jacobi, pcg_direction_x_jacobi, bicgstab_s, bicgstab_xr, bicgstab_p, cr_xr, cr_py,
     Comm, OP_SUM, OP_MAX, OP_MIN, csr_column_span,
 )
 from .matrices import (  # noqa: F401

@@ -211,6 +211,23 @@ def _declare(L):
         getattr(L, f"cmi_allgatherv_{suf}").argtypes = [vp, vp, vp, POINTER(c_int64), POINTER(c_int64), c_int, vp]
         getattr(L, f"cmi_halo_exchange_{suf}").argtypes = [vp, vp, c_int, POINTER(c_int), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64),
                                                           POINTER(c_int64), vp]
+    # the rest of BLAS-1 and the fused solver steps (csrc/blas1_extra.hip); scalars by value are c_double / c_float, the rest device pointers
+    for suf, sc in (("f64", c_double), ("f32", c_float)):
+        getattr(L, f"cmi_blas_scal_{suf}").argtypes = [i64, sc, vp, vp]
+        getattr(L, f"cmi_blas_xmy_{suf}").argtypes = [i64, vp, vp, vp, vp]
+        getattr(L, f"cmi_blas_axpbypcz_{suf}").argtypes = [i64, sc, vp, sc, vp, sc, vp, vp, vp]
+        getattr(L, f"cmi_blas_asum_{suf}").argtypes = [i64, vp, vp, vp, vp]
+        getattr(L, f"cmi_blas_amax_{suf}").argtypes = [i64, vp, vp, vp, vp, vp]
+        getattr(L, f"cmi_pcg_update_jacobi_{suf}").argtypes = [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        getattr(L, f"cmi_pcg_direction_x_jacobi_{suf}").argtypes = [i64, vp, vp, vp, vp, vp, vp, vp, vp]
+        getattr(L, f"cmi_bicgstab_s_{suf}").argtypes = [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        getattr(L, f"cmi_bicgstab_xr_{suf}").argtypes = [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        getattr(L, f"cmi_bicgstab_p_{suf}").argtypes = [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        getattr(L, f"cmi_cr_xr_{suf}").argtypes = [i64, vp, vp, vp, vp, vp, vp, c_int, vp, vp, vp, vp]
+        getattr(L, f"cmi_cr_py_{suf}").argtypes = [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        getattr(L, f"cmi_blas_axpy_dot_{suf}").argtypes = [i64, vp, vp, vp, vp, vp, vp, vp]
+        getattr(L, f"cmi_blas_axpy_ratio_{suf}").argtypes = [i64, vp, vp, vp, vp, vp]
+        getattr(L, f"cmi_csr_diagonal_{suf}").argtypes = [i64, vp, vp, vp, vp, c_int, vp]
     L.cmi_csr_column_span.argtypes = [i64, vp, POINTER(ctypes.c_int32), POINTER(ctypes.c_int32), vp]
     L.cmi_csr_rebase_offsets.argtypes = [i64, vp, ctypes.c_int32, vp, vp]
 
@@ -893,6 +910,105 @@ def cg_direction_x_fold(rr_new_out, npartials_rr, rr_old, yp, r, p, x, workspace
                                                                   _ptr(workspace), _stream(stream)))
     if mirror is not None:
         mirror.record(stream)
+
+
+# ------------------------------------------------------------------------------------------------
+# the rest of BLAS-1 and the fused solver steps (csrc/blas1_extra.hip).  Scalars named rz, yp, rho, d1, ... and every
+# reduction result are 1-element float64 device tensors whatever the vectors' dtype; `mirror` is a HostScalar.
+# ------------------------------------------------------------------------------------------------
+def _mirror(mirror):
+    return mirror.ptr if mirror is not None else None
+
+
+def blas_scal(alpha, x, stream=None):
+    """x <- alpha x."""
+    check(getattr(lib(), "cmi_blas_scal_" + _suffix(x))(x.numel(), float(alpha), _ptr(x), _stream(stream)))
+
+
+def blas_xmy(x, y, z, stream=None):
+    """z <- x .* y (z may be x or y)."""
+    check(getattr(lib(), "cmi_blas_xmy_" + _suffix(z))(x.numel(), _ptr(x), _ptr(y), _ptr(z), _stream(stream)))
+
+
+def blas_axpbypcz(alpha, x, beta, y, gamma, z, out, stream=None):
+    """out <- (alpha x + beta y) + gamma z."""
+    check(getattr(lib(), "cmi_blas_axpbypcz_" + _suffix(out))(x.numel(), float(alpha), _ptr(x), float(beta), _ptr(y), float(gamma), _ptr(z),
+                                                               _ptr(out), _stream(stream)))
+
+
+def blas_asum(x, result, workspace, stream=None):
+    """result (1 element of x's dtype) <- sum |x_i|."""
+    check(getattr(lib(), "cmi_blas_asum_" + _suffix(x))(x.numel(), _ptr(x), _ptr(result), _ptr(workspace), _stream(stream)))
+
+
+def blas_amax(x, value, index, workspace, stream=None):
+    """value (1 element of x's dtype) <- max |x_i|, index (1 int64) <- its first position; either may be None."""
+    check(getattr(lib(), "cmi_blas_amax_" + _suffix(x))(x.numel(), _ptr(x), _ptr(value), _ptr(index), _ptr(workspace), _stream(stream)))
+
+
+def pcg_update_jacobi(rz, yp, y, r, dinv, rz_new, rr, workspace, stream=None, mirror=None):
+    """alpha = rz/yp; r -= alpha y; rz_new = <r, dinv r>; rr = <r, r> (also to `mirror`)."""
+    check(getattr(lib(), "cmi_pcg_update_jacobi_" + _suffix(r))(r.numel(), _ptr(rz), _ptr(yp), _ptr(y), _ptr(r), _ptr(dinv), _ptr(rz_new), _ptr(rr),
+                                                                 _mirror(mirror), _ptr(workspace), _stream(stream)))
+    if mirror is not None:
+        mirror.record(stream)
+
+
+def pcg_direction_x_jacobi(rz_new, rz_old, yp, r, dinv, p, x, stream=None):
+    """x += (rz_old/yp) p; p = dinv r + (rz_new/rz_old) p."""
+    check(getattr(lib(), "cmi_pcg_direction_x_jacobi_" + _suffix(r))(r.numel(), _ptr(rz_new), _ptr(rz_old), _ptr(yp), _ptr(r), _ptr(dinv), _ptr(p),
+                                                                      _ptr(x), _stream(stream)))
+
+
+def bicgstab_s(rho, d1, r, AMp, s, ss, workspace, stream=None, mirror=None):
+    """alpha = rho/d1; s = r - alpha AMp; ss = <s, s> (also to `mirror`)."""
+    check(getattr(lib(), "cmi_bicgstab_s_" + _suffix(s))(s.numel(), _ptr(rho), _ptr(d1), _ptr(r), _ptr(AMp), _ptr(s), _ptr(ss), _mirror(mirror),
+                                                          _ptr(workspace), _stream(stream)))
+    if mirror is not None:
+        mirror.record(stream)
+
+
+def bicgstab_xr(rho, d1, d2, d3, p, s, AMs, r_star, x, r, rho_new, rr, workspace, stream=None, mirror=None):
+    """alpha = rho/d1, omega = d2/d3; x += alpha p + omega s; r = s - omega AMs; rho_new = <r_star, r>; rr = <r, r> (also to `mirror`)."""
+    check(getattr(lib(), "cmi_bicgstab_xr_" + _suffix(r))(r.numel(), _ptr(rho), _ptr(d1), _ptr(d2), _ptr(d3), _ptr(p), _ptr(s), _ptr(AMs), _ptr(r_star),
+                                                           _ptr(x), _ptr(r), _ptr(rho_new), _ptr(rr), _mirror(mirror), _ptr(workspace), _stream(stream)))
+    if mirror is not None:
+        mirror.record(stream)
+
+
+def bicgstab_p(rho_new, rho, d1, d2, d3, r, AMp, p, stream=None):
+    """beta = (rho_new/rho) (alpha/omega); p = r + beta (p - omega AMp)."""
+    check(getattr(lib(), "cmi_bicgstab_p_" + _suffix(p))(p.numel(), _ptr(rho_new), _ptr(rho), _ptr(d1), _ptr(d2), _ptr(d3), _ptr(r), _ptr(AMp), _ptr(p),
+                                                          _stream(stream)))
+
+
+def cr_xr(rz, yy, p, y, x, r, rr, workspace, update_r=True, stream=None, mirror=None):
+    """alpha = rz/yy; x += alpha p; with update_r also r -= alpha y and rr = <r, r> (also to `mirror`)."""
+    check(getattr(lib(), "cmi_cr_xr_" + _suffix(x))(x.numel(), _ptr(rz), _ptr(yy), _ptr(p), _ptr(y), _ptr(x), _ptr(r), int(bool(update_r)), _ptr(rr),
+                                                     _mirror(mirror), _ptr(workspace), _stream(stream)))
+    if mirror is not None and update_r:
+        mirror.record(stream)
+
+
+def cr_py(rz_new, rz, r, Ar, p, y, yy_new, workspace, stream=None):
+    """beta = rz_new/rz; p = r + beta p; y = Ar + beta y; yy_new = <y, y>."""
+    check(getattr(lib(), "cmi_cr_py_" + _suffix(p))(p.numel(), _ptr(rz_new), _ptr(rz), _ptr(r), _ptr(Ar), _ptr(p), _ptr(y), _ptr(yy_new), _ptr(workspace),
+                                                     _stream(stream)))
+
+
+def blas_axpy_dot(h, v, w, u, out, workspace, stream=None):
+    """w -= (*h) v; out = <w, u> (u may be w: the norm's square).  h None: the dot alone, v unused."""
+    check(getattr(lib(), "cmi_blas_axpy_dot_" + _suffix(w))(w.numel(), _ptr(h), _ptr(v), _ptr(w), _ptr(u), _ptr(out), _ptr(workspace), _stream(stream)))
+
+
+def blas_axpy_ratio(num, den, x, y, stream=None):
+    """y += (num/den) x."""
+    check(getattr(lib(), "cmi_blas_axpy_ratio_" + _suffix(y))(y.numel(), _ptr(num), _ptr(den), _ptr(x), _ptr(y), _stream(stream)))
+
+
+def csr_diagonal(num_rows, Ap, Aj, Ax, diag, reciprocal=False, stream=None):
+    """diag[i] <- the sum of row i's entries in column i, or its reciprocal."""
+    check(getattr(lib(), "cmi_csr_diagonal_" + _suffix(diag))(num_rows, _ptr(Ap), _ptr(Aj), _ptr(Ax), _ptr(diag), int(bool(reciprocal)), _stream(stream)))
 
 
 class HostScalar:
