@@ -119,6 +119,10 @@ def _declare(L):
         getattr(L, f"cmi_spmv_csr_{suf}").argtypes = [i64, i64, i64, vp, vp, vp, vp, vp, i32, cfgp, vp]
         getattr(L, f"cmi_spmm_csr_{suf}").argtypes = [i64, i64, i64, vp, vp, vp, i64, vp, i64, i64, vp, i64, i64, i32, cfgp, vp]
         getattr(L, f"cmi_spmv_coo_{suf}").argtypes = [i64, i64, i64, vp, vp, vp, vp, vp, i32, cfgp, vp]
+        sc = c_double if suf == "f64" else c_float  # the fused sweeps take their scalars by value, in T
+        getattr(L, f"cmi_spmv_csr_axpby_{suf}").argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, sc, sc, vp, vp, vp]
+        getattr(L, f"cmi_csr_jacobi_sweep_{suf}").argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp, sc, vp, vp]
+        getattr(L, f"cmi_relax_jacobi_update_{suf}").argtypes = [i64, vp, vp, vp, sc, vp, vp]
         getattr(L, f"cmi_spmv_ell_{suf}").argtypes = [i64, i64, i64, i64, vp, vp, vp, vp, vp, i32, cfgp, vp]
         getattr(L, f"cmi_spmv_dia_{suf}").argtypes = [i64, i64, i64, i64, vp, vp, vp, vp, i32, cfgp, vp]
         getattr(L, f"cmi_spmv_hyb_{suf}").argtypes = [i64, i64, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp, i32,
@@ -334,6 +338,49 @@ def spmm_csr(num_rows, num_cols, Ap, Aj, Ax, X, Y, accumulate=False, cfg=None, s
     fn = getattr(lib(), "cmi_spmm_csr_" + _suffix(Y))
     check(fn(num_rows, num_cols, Aj.numel(), _ptr(Ap), _ptr(Aj), _ptr(Ax), X.shape[1], _ptr(X), X.stride(0), X.stride(1),
              _ptr(Y), Y.stride(0), Y.stride(1), int(bool(accumulate)), _cfg(cfg), _stream(stream)))
+
+
+def _plan_handle(plan):
+    return None if plan is None else plan.handle
+
+
+def spmv_csr_axpby(num_rows, num_cols, Ap, Aj, Ax, x, alpha, beta, z, out, plan=None, stream=None):
+    """cmi_spmv_csr_axpby_*: out[i] = alpha * (A x)[i] + beta * z[i] in one launch (out may be z, never x).  alpha = -1,
+    beta = 1, z = b: the residual; alpha = 1, beta = c, z = residual: the polynomial smoother's step."""
+    import torch
+    for t, n in ((Ap, "Ap"), (Aj, "Aj")):
+        _need(t, n, torch.int32)
+    for t, n in ((Ax, "Ax"), (x, "x"), (z, "z"), (out, "out")):
+        _need(t, n, out.dtype)
+    if Ap.numel() != num_rows + 1 or x.numel() != num_cols or z.numel() != num_rows or out.numel() != num_rows or Aj.numel() != Ax.numel():
+        raise ValueError("spmv_csr_axpby: array lengths do not match the matrix shape")
+    fn = getattr(lib(), "cmi_spmv_csr_axpby_" + _suffix(out))
+    check(fn(_plan_handle(plan), num_rows, num_cols, Aj.numel(), _ptr(Ap), _ptr(Aj), _ptr(Ax), _ptr(x), alpha, beta, _ptr(z), _ptr(out),
+             _stream(stream)))
+
+
+def csr_jacobi_sweep(num_rows, Ap, Aj, Ax, diag, b, x, omega, x_out, plan=None, stream=None):
+    """cmi_csr_jacobi_sweep_*: x_out[i] = x[i] + omega * (b[i] - (A x)[i]) / diag[i] in one launch (square A; x_out is not x)."""
+    import torch
+    for t, n in ((Ap, "Ap"), (Aj, "Aj")):
+        _need(t, n, torch.int32)
+    for t, n in ((Ax, "Ax"), (diag, "diag"), (b, "b"), (x, "x"), (x_out, "x_out")):
+        _need(t, n, x_out.dtype)
+    if Ap.numel() != num_rows + 1 or Aj.numel() != Ax.numel() or any(t.numel() != num_rows for t in (diag, b, x, x_out)):
+        raise ValueError("csr_jacobi_sweep: array lengths do not match the matrix shape")
+    fn = getattr(lib(), "cmi_csr_jacobi_sweep_" + _suffix(x_out))
+    check(fn(_plan_handle(plan), num_rows, Aj.numel(), _ptr(Ap), _ptr(Aj), _ptr(Ax), _ptr(diag), _ptr(b), _ptr(x), omega, _ptr(x_out),
+             _stream(stream)))
+
+
+def relax_jacobi_update(diag, b, y, omega, x, stream=None):
+    """cmi_relax_jacobi_update_*: x[i] = x[i] + omega * (b[i] - y[i]) / diag[i], in place (y = A x from any format's multiply)."""
+    for t, n in ((diag, "diag"), (b, "b"), (y, "y"), (x, "x")):
+        _need(t, n, x.dtype)
+    if any(t.numel() != x.numel() for t in (diag, b, y)):
+        raise ValueError("relax_jacobi_update: vectors must have the same length")
+    fn = getattr(lib(), "cmi_relax_jacobi_update_" + _suffix(x))
+    check(fn(x.numel(), _ptr(diag), _ptr(b), _ptr(y), omega, _ptr(x), _stream(stream)))
 
 
 class Plan:

@@ -445,6 +445,40 @@ int cmi_spmm_csr_f32(int64_t num_rows, int64_t num_cols, int64_t num_entries, co
                      const float *Ax, int64_t k, const float *X, int64_t x_row_stride, int64_t x_col_stride,
                      float *Y, int64_t y_row_stride, int64_t y_col_stride, int accumulate,
                      const cmi_config *cfg, void *stream);
+/* A CSR row sweep with a fixed elementwise write-back (spmv_csr_epilogue.hip): the smoothers that are an SpMV followed at
+ * once by passes over the vector it wrote, in one launch.  s_i is row i's sum exactly as cmi_spmv_csr_* forms it: from
+ * T(0), entries in storage order, multiply then add, by one lane; the same lane evaluates the expression once and
+ * stores one value, so the result has the bits of the unfused host sequence.
+ *   cmi_spmv_csr_axpby_*:   out[i] = alpha * s_i + beta * z[i].  out may be z; out must not overlap x; A may be
+ *     rectangular.  alpha = -1, beta = 1, z = b is the residual b - A x (reference relaxation/detail/polynomial.inl:
+ *     125-127: multiply, then axpby(b, r, r, 1, -1)); alpha = 1, beta = c, z = residual is the polynomial smoother's
+ *     step h <- A h + c r (polynomial.inl:133-139).
+ *   cmi_csr_jacobi_sweep_*: x_out[i] = x[i] + omega * (b[i] - s_i) / diag[i], omega * (b - s) first and then the
+ *     division (reference relaxation/detail/jacobi.inl:77-87 with its jacobi_relax_functor, :44); A is square, x_out
+ *     must not overlap x (other rows gather x), nor diag or b; a zero in diag gives what IEEE division gives.
+ *   cmi_relax_jacobi_update_*: x[i] = x[i] + omega * (b[i] - y[i]) / diag[i] in place, the same expression behind a
+ *     multiply of any other format (jacobi.inl:83-87).
+ * plan: NULL or a CSR plan of this value type (any kernel class; the sweep keeps its own tiling of 256 rows per
+ * workgroup).  Rejected with CMI_ERROR_INVALID_VALUE before any device call: negative sizes, sizes beyond the CSR
+ * ceiling (cmi_spmv_csr_*), null arrays with non-zero sizes, out / x_out overlapping x, x_out overlapping diag or b, the
+ * update's x overlapping diag, b or y, a plan of another format or value type.  num_rows == 0 (n == 0): success, nothing launched.  No allocation, no synchronisation, no atomics.
+ * Callers find the feature by the symbol (CMI_VERSION is unchanged). */
+int cmi_spmv_csr_axpby_f64(const cmi_plan *plan, int64_t num_rows, int64_t num_cols, int64_t num_entries, const int32_t *Ap,
+                           const int32_t *Aj, const double *Ax, const double *x, double alpha, double beta, const double *z,
+                           double *out, void *stream);
+int cmi_spmv_csr_axpby_f32(const cmi_plan *plan, int64_t num_rows, int64_t num_cols, int64_t num_entries, const int32_t *Ap,
+                           const int32_t *Aj, const float *Ax, const float *x, float alpha, float beta, const float *z,
+                           float *out, void *stream);
+int cmi_csr_jacobi_sweep_f64(const cmi_plan *plan, int64_t num_rows, int64_t num_entries, const int32_t *Ap, const int32_t *Aj,
+                             const double *Ax, const double *diag, const double *b, const double *x, double omega,
+                             double *x_out, void *stream);
+int cmi_csr_jacobi_sweep_f32(const cmi_plan *plan, int64_t num_rows, int64_t num_entries, const int32_t *Ap, const int32_t *Aj,
+                             const float *Ax, const float *diag, const float *b, const float *x, float omega, float *x_out,
+                             void *stream);
+int cmi_relax_jacobi_update_f64(int64_t n, const double *diag, const double *b, const double *y, double omega, double *x,
+                                void *stream);
+int cmi_relax_jacobi_update_f32(int64_t n, const float *diag, const float *b, const float *y, float omega, float *x,
+                                void *stream);
 /* The same fusion for ELL (ELLR with row_lengths) and DIA: one lane per row owns y[row], so <y, w> costs one  */
 /* extra coalesced read of w and one partial per workgroup.                                                    */
 int cmi_spmv_ell_dot_f64(int64_t num_rows, int64_t num_cols, int64_t num_entries_per_row, int64_t pitch,
