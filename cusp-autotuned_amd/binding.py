@@ -123,6 +123,7 @@ def _declare(L):
         getattr(L, f"cmi_spmv_csr_axpby_{suf}").argtypes = [vp, i64, i64, i64, vp, vp, vp, vp, sc, sc, vp, vp, vp]
         getattr(L, f"cmi_csr_jacobi_sweep_{suf}").argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, vp, sc, vp, vp]
         getattr(L, f"cmi_relax_jacobi_update_{suf}").argtypes = [i64, vp, vp, vp, sc, vp, vp]
+        getattr(L, f"cmi_csr_gauss_seidel_colour_{suf}").argtypes = [i64, i64, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp]
         getattr(L, f"cmi_spmv_ell_{suf}").argtypes = [i64, i64, i64, i64, vp, vp, vp, vp, vp, i32, cfgp, vp]
         getattr(L, f"cmi_spmv_dia_{suf}").argtypes = [i64, i64, i64, i64, vp, vp, vp, vp, i32, cfgp, vp]
         getattr(L, f"cmi_spmv_hyb_{suf}").argtypes = [i64, i64, i64, i64, vp, vp, i64, vp, vp, vp, vp, vp, i32,
@@ -381,6 +382,25 @@ def relax_jacobi_update(diag, b, y, omega, x, stream=None):
         raise ValueError("relax_jacobi_update: vectors must have the same length")
     fn = getattr(lib(), "cmi_relax_jacobi_update_" + _suffix(x))
     check(fn(x.numel(), _ptr(diag), _ptr(b), _ptr(y), omega, _ptr(x), _stream(stream)))
+
+
+def csr_gauss_seidel_colour(num_rows, Ap, Aj, Ax, b, x, ordering, slot_begin, slot_end, scratch=None, stream=None):
+    """cmi_csr_gauss_seidel_colour_*: one colour of a Gauss-Seidel sweep, in place.  For every slot s of [slot_begin, slot_end),
+    i = ordering[s]: x[i] = (b[i] - sum of row i without its diagonal entry) / A(i, i), left as it is where the row stores no
+    non-zero diagonal.  scratch=None: one launch, and no row of the range may hold an off-diagonal column of the range;
+    scratch (at least slot_end - slot_begin values): two launches, every row reads the x from before the call."""
+    import torch
+    for t, n in ((Ap, "Ap"), (Aj, "Aj"), (ordering, "ordering")):
+        _need(t, n, torch.int32)
+    for t, n in ((Ax, "Ax"), (b, "b"), (x, "x"), (scratch, "scratch")):
+        _need(t, n, x.dtype)
+    if Ap.numel() != num_rows + 1 or Aj.numel() != Ax.numel() or b.numel() != num_rows or x.numel() != num_rows:
+        raise ValueError("csr_gauss_seidel_colour: array lengths do not match the matrix shape")
+    if slot_end > ordering.numel() or (scratch is not None and scratch.numel() < slot_end - slot_begin):
+        raise ValueError("csr_gauss_seidel_colour: ordering or scratch is shorter than the slot range")
+    fn = getattr(lib(), "cmi_csr_gauss_seidel_colour_" + _suffix(x))
+    check(fn(num_rows, Aj.numel(), _ptr(Ap), _ptr(Aj), _ptr(Ax), _ptr(b), _ptr(x), _ptr(ordering), int(slot_begin), int(slot_end),
+             _ptr(scratch), _stream(stream)))
 
 
 class Plan:

@@ -479,6 +479,27 @@ int cmi_relax_jacobi_update_f64(int64_t n, const double *diag, const double *b, 
                                 void *stream);
 int cmi_relax_jacobi_update_f32(int64_t n, const float *diag, const float *b, const float *y, float omega, float *x,
                                 void *stream);
+/* One colour of a multicolour Gauss-Seidel sweep (spmv_csr_colour.hip): a CSR row sweep over the rows ordering[slot_begin ..
+ * slot_end) that skips the diagonal and writes x in place (reference sequential/relaxation/gauss_seidel.h).  Per slot s,
+ * i = ordering[s]: rsum = T(0); over row i in storage order an entry in column i sets diag (the last one wins) and adds
+ * nothing -- its product is never formed, so a NaN or inf in x[i] or in the diagonal value does not reach rsum --, any
+ * other entry does rsum = rsum + Ax * x[Aj], multiply then add, by one ordered chain; if diag != 0 then
+ * x[i] = (b[i] - rsum) / diag, otherwise (no diagonal stored, a stored 0 or -0) x[i] keeps its bits.
+ *   scratch == NULL: one launch; the caller promises that no row of the range holds an off-diagonal column that is also
+ *     in the range.
+ *   scratch != NULL: at least slot_end - slot_begin values; two stream-ordered launches, the first parks every slot's
+ *     value (the new one, or the bits x[i] has where there is none) without touching x, the second stores them.  Every
+ *     row then reads the x from before the call, whatever the range holds.
+ * ordering holds row indices in [0, num_rows), each at most once in the range.  Rejected with CMI_ERROR_INVALID_VALUE
+ * before any device call: negative sizes, sizes beyond the CSR ceiling (cmi_spmv_csr_*), a slot range reversed or outside
+ * [0, num_rows], null arrays when there is work, b or scratch overlapping x.  An empty range: success, nothing launched.
+ * No allocation, no synchronisation, no atomics.  Callers find the feature by the symbol (CMI_VERSION is unchanged). */
+int cmi_csr_gauss_seidel_colour_f64(int64_t num_rows, int64_t num_entries, const int32_t *Ap, const int32_t *Aj, const double *Ax,
+                                    const double *b, double *x, const int32_t *ordering, int64_t slot_begin, int64_t slot_end,
+                                    double *scratch, void *stream);
+int cmi_csr_gauss_seidel_colour_f32(int64_t num_rows, int64_t num_entries, const int32_t *Ap, const int32_t *Aj, const float *Ax,
+                                    const float *b, float *x, const int32_t *ordering, int64_t slot_begin, int64_t slot_end,
+                                    float *scratch, void *stream);
 /* The same fusion for ELL (ELLR with row_lengths) and DIA: one lane per row owns y[row], so <y, w> costs one  */
 /* extra coalesced read of w and one partial per workgroup.                                                    */
 int cmi_spmv_ell_dot_f64(int64_t num_rows, int64_t num_cols, int64_t num_entries_per_row, int64_t pitch,
