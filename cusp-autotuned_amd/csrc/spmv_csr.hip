@@ -618,12 +618,20 @@ csr_wavep_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, const in
 // first vector starts at the 16-byte boundary at or below its first entry), so a tile always fits its wave's slots; the partition
 // is wave_partition_kernel's (8 bytes per tile, plan-owned).  Same products, storage-order sums: bit-exact.
 // The last vector of the ARRAYS may reach past num_entries: that one wave sums its rows straight from the arrays.
+// EQUAL-LENGTH tiles read no row offset (round 8): with L the matrix's longest row (the plan's exact figure, passed as uniform_len), a
+// tile of nr rows and cnt = nz1 - nz0 entries has only rows of length L iff cnt == nr L -- every row is at most L long, so the sum
+// reaches nr L only when each one equals L -- and then row r of the tile is [nz0 + r L, nz0 + (r + 1) L): nothing is fetched, in any
+// turn of the row loop and on the arrays' last vector too.  Both sides of the test are in the partition entry the wave already holds;
+// no flag, no plan memory, and no new way to go stale (L comes from the row offsets the partition was built from, at the same time).
+// On a stencil that is every tile without a boundary row: the row offsets (4 of the ~80 bytes per row) leave the stream.  Any other
+// tile, and every tile when uniform_len is 0, reads them as before.
 // Four wave tiles per workgroup.
 template <typename T, int V, int POL, bool DOT>
 __global__ void __launch_bounds__(256)
 csr_wavev_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t num_entries, const int *Ap /* not restrict: see csr_wave */,
                  const int *__restrict__ Aj, const T *__restrict__ Ax, const T *__restrict__ x, T *__restrict__ y, int64_t num_tiles,
-                 int64_t tiles_per_xcd, int swizzle, int accumulate, const T *__restrict__ w, double *__restrict__ dot_partial)
+                 int64_t tiles_per_xcd, int swizzle, int accumulate, const T *__restrict__ w, double *__restrict__ dot_partial,
+                 int uniform_len)
 {
     // Request shape: every load instruction of the wave covers ONE contiguous span and every 128-byte line of the streams is requested
     // by exactly one instruction (csr_stream's f64 body asks for a lane's four values with two 16-byte loads 16 bytes apart: both
@@ -647,8 +655,16 @@ csr_wavev_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t 
         const int nr = re - rs;
         if (nr > 0) { // (uniform per wave)
             const int fbase = nz0 & ~(E - 1);
-            const int first_turn_end = Ap[rs + (nr < kWave ? nr : kWave)]; // (scalar) where the 64th row of the tile ends
-            int a = Ap[rs + (lane < nr ? lane : nr)], b = 0;
+            // Every row of the tile has the longest row's length (64-bit product: a stretch of empty rows makes nr large): row r is
+            // [nz0 + r uniform_len, nz0 + (r + 1) uniform_len) and nothing is read from Ap.  (uniform per wave: a scalar branch)
+            const bool uni = uniform_len > 0 && (int64_t)(nz1 - nz0) == (int64_t)nr * uniform_len;
+            int first_turn_end = 0, a, b = 0;
+            if (uni) {
+                a = nz0 + (lane < nr ? lane : nr) * uniform_len;
+            } else {
+                first_turn_end = Ap[rs + (nr < kWave ? nr : kWave)]; // (scalar) where the 64th row of the tile ends
+                a = Ap[rs + (lane < nr ? lane : nr)];
+            }
             T *mine = prod[wave];
             const bool fits = nz1 > nz0 && (int64_t)((nz1 + E - 1) & ~(E - 1)) <= num_entries && nz1 - fbase <= SLOTS; // (uniform)
             if (fits) {
@@ -684,9 +700,13 @@ csr_wavev_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t 
                 }
                 __builtin_amdgcn_wave_barrier(); // (compiler only: the hardware runs a wave's LDS instructions in order)
             }
-            b = __builtin_amdgcn_update_dpp(first_turn_end, a, 0x130 /* wave_shl:1: the next lane's start; lane 63 keeps the 64th row's end */, 0xf, 0xf, false);
+            if (uni) b = a + uniform_len;
+            else b = __builtin_amdgcn_update_dpp(first_turn_end, a, 0x130 /* wave_shl:1: the next lane's start; lane 63 keeps the 64th row's end */, 0xf, 0xf, false);
             for (int r = lane; r < nr; r += kWave) { // (one turn, except over a stretch of very short rows)
-                if (r >= kWave) { a = Ap[rs + r]; b = Ap[rs + r + 1]; }
+                if (r >= kWave) {
+                    if (uni) { a = nz0 + r * uniform_len; b = a + uniform_len; }
+                    else { a = Ap[rs + r]; b = Ap[rs + r + 1]; }
+                }
                 T sum = accumulate ? y[rs + r] : T(0);
                 if (fits) sum = sum_in_order(sum, mine + (a - fbase), b - a);
                 else for (int j = a; j < b; j++) sum = sum + Ax[j] * x[Aj[j]]; // (the array's last vector, or an empty tile)
@@ -1470,12 +1490,15 @@ static int launch_wavev(const cmi_config &c, const cmi_plan *plan, int pol, hipS
     const int64_t grid64 = padded_grid(tiles, swz);
     if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_wavev: grid too large");
     const bool dot = w && dot_partial && tiles <= kPartialCapacity;
+    // the exact longest row (max_row_length_kernel, measured with the partition): a tile of nr rows and nr * that many entries has only
+    // rows of that length and takes its row bounds from the partition entry; 0 = every tile reads the row offsets
+    const int uniform_len = plan->prof.max_len >= 1 && plan->prof.max_len <= INT32_MAX ? (int)plan->prof.max_len : 0;
     with_policy(pol, [&](auto P) {
         with_int<1, 2, 4>(V, [&](auto VV) {
             with_bool(dot, [&](auto DOT) {
                 hipLaunchKernelGGL((csr_wavev_kernel<T, decltype(VV)::value, decltype(P)::value, decltype(DOT)::value>), dim3((unsigned)grid64),
                                    dim3(256), 0, s, plan->wave_row_start, plan->wave_tiles, nnz, Ap, Aj, Ax, x, y, tiles, tpx, swz, accumulate, w,
-                                   dot_partial);
+                                   dot_partial, uniform_len);
             });
         });
     });

@@ -344,7 +344,7 @@ int cmi_tuning_set_waver_rule(int dtype, const cmi_waver_rule *rule); /* layered
 /*   row indices, and for a plan made by cmi_plan_create_csr* the column indices --  MUST NOT     */
 /*   CHANGE IN PLACE while the plan is used.  A plan caches structure derived from     */
 /*   them (a sorted-COO plan its row offsets, a C16 plan the 16-bit columns, a WAVER plan the pieces of   */
-/*   consecutive columns, a wave partition the tile bounds): after an in-place edit the multiplies read that stale  */
+/*   consecutive columns, a wave partition the tile bounds and the longest row): after an in-place edit the multiplies read that stale  */
 /*   structure and y is WRONG (never a fault: every kernel bounds its LDS tile by what   */
 /*   it reads).  Destroy the plan and make a new one when the structure changes;         */
 /*   cmi_plan_validate (below) tells whether that has happened.  cmi_plan_create also      */
