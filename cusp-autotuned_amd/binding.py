@@ -16,6 +16,7 @@ F64, F32 = 0, 1
 KERNEL_AUTO = 0
 CSR_SCALAR, CSR_VECTOR, CSR_STREAM, CSR_STREAM_PIPE, CSR_BALANCED, CSR_STREAM_C16, CSR_STREAM_WAVE, CSR_STREAM_WAVEV, CSR_STREAM_WAVEX = 1, 2, 3, 4, 5, 6, 7, 8, 9
 CSR_STREAM_WAVER, CSR_STREAM_PACKED = 11, 12  # round 4: run-compressed column copy on wave tiles; ... with the values packed beside it (opt-in)
+POLICY_COLS16 = 8  # Config.nontemporal bit: CSR_STREAM_WAVEV reads the plan's 16-bit column copy (Plan.csr; in plan.config() only when granted)
 ELL_ROW, DIA_ROW, COO_SEGMENTED, COO_LANE4, COO_TILE = 10, 20, 30, 31, 32
 CSR_SPMM_ROWS, CSR_SPMM_COLS = 40, 41  # cmi_spmm_csr_*: lane groups per row (row-major blocks) / one lane per row (column-major)
 

@@ -220,6 +220,7 @@ constexpr int kPolLoadNT = 1, kPolStoreNT = 2;
 constexpr int64_t kInfinityCacheBytes = 256ll << 20; // MALL, shared by the 8 XCDs
 constexpr int kWaveTileMaxK = 10; // csr_wave: entries per lane (= the longest row of the matrix)
 constexpr int kPolStrided = 4; // csr_stream only: entry streams requested lane-strided (a dword / a value per lane per instruction), not as 16-byte vectors
+constexpr int kPolCols16 = 8;  // csr_wavev only: the columns are read from the plan's 16-bit copy (wavev_cols16); in a plan's config only when the copy was granted
 
 template <bool NT, typename V> __device__ __forceinline__ V ld(const V *p)
 {
@@ -305,6 +306,10 @@ struct cmi_plan {
                                        // entry lies in [t wave_q, (t + 1) wave_q) (plan.hip wave_partition); null: 64 rows per wave
     int64_t wave_tiles = 0;
     int wave_q = 0;
+    // csr_wavev with cfg.nontemporal & 8 (spmv_csr.hip wavev_cols16_build): per wave tile of the partition above the smallest column of its
+    // entries, and per entry the 16-bit offset from its tile's base.  Both or neither (every tile spans at most 65535 columns, or nothing is kept).
+    int32_t *wavev_base = nullptr;    // device, wave_tiles entries
+    uint16_t *wavev_cols16 = nullptr; // device, nnz + 8 entries (zero padding), 16-byte aligned
     // order-sensitive 64-bit checksums of the arrays the plan was made from (cmi_plan_validate): the index array (CSR row offsets, COO /
     // HYB-COO row indices) and -- when the plan owns data derived from them (the 16-bit copy) -- the CSR column indices
     uint64_t fp_index = 0, fp_columns = 0;
@@ -335,6 +340,7 @@ constexpr double kHybFusedMaxPerRow = 3.0;
 constexpr int kHybFusedMaxInTile = 4096;
 // spmv_csr16.hip: the plan's 16-bit column copy (built only if every tile qualifies) and the multiply that reads it
 int wave_partition_build(cmi_plan *p, const int *Ap, int k, hipStream_t s, int q_override = 0); // spmv_csr.hip (q_override: entries per tile, csr_wavev)
+int wavev_cols16_build(cmi_plan *p, const int *Aj, hipStream_t s); // spmv_csr.hip: the 16-bit column copy on that partition (sets cfg.nontemporal & 8 when granted)
 int csr16_build(cmi_plan *p, const int *Ap, const int *Aj, hipStream_t s, int wave_k = 0);
 // spmv_csr_runs.hip: the plan's run-compressed column copy (+ the packed tiles when `values` is given) and the multiply that reads it
 int csr_runs_build(cmi_plan *p, const int *Ap, const int *Aj, int v, double min_mean_piece, const void *values, hipStream_t s, double *mean_piece, int cap = 0);

@@ -153,6 +153,18 @@ static int stencil_vector_tiles(int64_t nnz, const row_profile &prof, int dtype,
     const int v = dtype == CMI_F64 ? 1 : 2;
     return nnz <= (int64_t)1024 * v * kPartialCapacity ? v : 0;
 }
+// Round 9: an AUTO plan of that rule made WITH the columns reads them from a plan-owned 16-bit copy (csr_wavev's C16 variant, spmv_csr.hip
+// wavev_cols16_build; cfg.nontemporal bit 8) -- f64 only.  Measured on the headline matrix against the parent build, the driver's full line,
+// one process per run, alternated (profiles/r09_cols16_ab.txt): counted traffic 810.5 -> 711.8 MB per launch, replayed 111.7 -> 103.2 us,
+// cold 122.9 -> 112.0 us, each more than twice the session's parent-to-parent spread; in one process, explicit configs 3 against 11: 114.1 ->
+// 101.5 us replayed, 119.3 -> 105.6 cold, 123.9 -> 115.4 with the fused dot.  The copy costs 2 bytes per entry of plan memory and two more
+// passes over the columns at plan creation; a plan from the row offsets alone, or an explicit config without the bit, does without.
+// A matrix with a tile that spans more than 65535 columns (the 7-point 215^3 stencil: +-46225 around the diagonal) is refused by the builder
+// and runs the 32-bit kernel as before.  f32 (V = 2) was not measured and does not take the copy by itself; bit 8 asks for it explicitly.
+static bool stencil_cols16(int dtype)
+{
+    return dtype == CMI_F64;
+}
 // ... and csr_wave on a plan-built partition (spmv_csr.hip wave_partition_build) for IRREGULAR short rows: K entries per lane with
 // K = floor(mean + longest / 64), so that a wave tile of Q = 64 K - longest entries holds about Q / mean <= 64 rows; the longest row
 // small enough for the tiles to fill 90 % of the wave's request slots.  OPT-IN: asked for per plan (cfg.kernel = CMI_CSR_STREAM_WAVE
@@ -375,6 +387,7 @@ CMI_API int cmi_plan_device_bytes(const cmi_plan *plan, int64_t *bytes)
     if (plan->hyb_tile_start) b += (ceil_div(plan->rows, kHybTileRows) + 1) * 4;
     if (plan->coo_offsets) b += (plan->rows + 1) * 4;
     if (plan->wave_row_start) b += (plan->wave_tiles + 1) * 8;
+    if (plan->wavev_cols16) b += (plan->nnz + 8) * 2 + plan->wave_tiles * 4;
     if (plan->csr16_cols) b += (plan->nnz + 8) * 2;
     if (plan->csr16_base) b += ceil_div(plan->rows, plan->cfg.rows_per_block > 0 ? plan->cfg.rows_per_block : 1) * 4;
     if (plan->runs_start) b += (plan->wave_tiles + 1) * 16;
@@ -448,6 +461,10 @@ static int plan_create(int format, int dtype, int64_t num_rows, int64_t num_cols
     cmi_config wavev_shape;
     bool want_wavev = false, want_wavex = false;
     int wavev_v = 0, wavex_window = 0;
+    // nontemporal bit 8 (kPolCols16) on a CMI_CSR_STREAM_WAVEV config asks for the plan-owned 16-bit column copy (spmv_csr.hip
+    // wavev_cols16_build); it needs the columns (cmi_plan_create_csr).  The bit is not a cache policy: it is taken off here and put back
+    // into the plan's config only when the copy was granted.
+    const bool want_cols16 = format == CMI_FORMAT_CSR && cfg && cfg->kernel == CMI_CSR_STREAM_WAVEV && (cfg->nontemporal & kPolCols16) && csr_columns;
     if (format == CMI_FORMAT_CSR && cfg && (cfg->kernel == CMI_CSR_STREAM_WAVEV || cfg->kernel == CMI_CSR_STREAM_WAVEX)) {
         want_wavev = true;
         want_wavex = cfg->kernel == CMI_CSR_STREAM_WAVEX; // the same partition; the multiply adds an x window in LDS (rows_per_block = its length)
@@ -461,6 +478,7 @@ static int plan_create(int format, int dtype, int64_t num_rows, int64_t num_cols
         wavev_shape.items_per_thread = 0;
         wavev_shape.block_size = 0;
         wavev_shape.threads_per_row = 0;
+        wavev_shape.nontemporal &= ~kPolCols16;
         cfg = &wavev_shape;
         p->cfg_explicit = false;
     }
@@ -486,6 +504,7 @@ static int plan_create(int format, int dtype, int64_t num_rows, int64_t num_cols
     p->kernel_asked = want_partition || want_wavev || want_waver;
     // HYB's table key is its ELL part's (the COO part looks its own shape up per call)
     select_config(format == CMI_FORMAT_HYB ? CMI_FORMAT_ELL : format, dtype, num_rows, num_cols, num_entries, cfg, &p->cfg);
+    if (format == CMI_FORMAT_CSR) p->cfg.nontemporal &= ~kPolCols16; // (only a granted copy sets it, below)
     hipStream_t s = as_stream(stream);
     const size_t vbytes = dtype == CMI_F64 ? 8 : 4;
     int st = CMI_SUCCESS;
@@ -556,6 +575,10 @@ static int plan_create(int format, int dtype, int64_t num_rows, int64_t num_cols
                 p->cfg.threads_per_row = 0;
                 p->cfg.nontemporal &= ~kPolStrided;
                 p->cfg.nontemporal |= kPolLoadNT | kPolStoreNT; // (beyond the cache by the rule: every line of the streams is requested once)
+                // ... and a plan made with the columns reads them from its own 16-bit copy (2 of the 12 / 8 bytes per entry leave the stream; see
+                // stencil_cols16 above for what was measured).  Only this branch: the other AUTO routes into csr_wavev below keep the 32-bit
+                // columns until a regret run over their matrices says otherwise.
+                if (csr_columns && stencil_cols16(dtype)) st = wavev_cols16_build(p, csr_columns, s);
             }
         } else if (st == CMI_SUCCESS && !gather_bound && auto_kernel && !want_wavev && !want_waver && p->cfg.kernel == CMI_CSR_STREAM && p->cfg.threads_per_row <= 1 &&
             wave_tiles_fit(num_rows, num_entries, p->prof.max_len)) {
@@ -643,6 +666,7 @@ static int plan_create(int format, int dtype, int64_t num_rows, int64_t num_cols
                 // ... and so is a caller's XCD dealing (< 0: launch order) -- select_config takes only block size and policy from an AUTO-kernel
                 // config, so until session 29 of round 4 an asked-for dealing was silently the table's (the "sweeps" of it measured nothing)
                 if (want_wavev && wavev_shape.xcd_swizzle != 0) p->cfg.xcd_swizzle = wavev_shape.xcd_swizzle < 0 ? 0 : wavev_shape.xcd_swizzle;
+                if (want_cols16 && p->cfg.kernel == CMI_CSR_STREAM_WAVEV) st = wavev_cols16_build(p, csr_columns, s); // (asked for; not granted: the bit stays clear)
             }
         } else if (st == CMI_SUCCESS && want_wavev) {
             st = fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_create: CMI_CSR_STREAM_WAVEV needs items_per_thread 0, 1, 2 or 4, no row of 512+ entries and the longest row at most half of the 256 x items_per_thread slots of a wave tile");
@@ -704,7 +728,7 @@ static int plan_create(int format, int dtype, int64_t num_rows, int64_t num_cols
         p->fp_columns = p->coo_csr_plan->fp_columns;
         p->has_fp_columns = true;
     }
-    if (st == CMI_SUCCESS && (p->csr16_cols || p->runs_pieces || p->csr16_packed) && csr_columns) {
+    if (st == CMI_SUCCESS && (p->csr16_cols || p->runs_pieces || p->csr16_packed || p->wavev_cols16) && csr_columns) {
         st = fingerprint(num_entries, csr_columns, s, &p->fp_columns);
         p->has_fp_columns = st == CMI_SUCCESS;
     }
@@ -798,6 +822,8 @@ CMI_API int cmi_plan_destroy(cmi_plan *plan)
     if (plan && plan->coo_csr_plan) (void)cmi_plan_destroy(plan->coo_csr_plan);
     if (plan && plan->coo_offsets) (void)hipFree(plan->coo_offsets);
     if (plan && plan->wave_row_start) (void)hipFree(plan->wave_row_start);
+    if (plan && plan->wavev_base) (void)hipFree(plan->wavev_base);
+    if (plan && plan->wavev_cols16) (void)hipFree(plan->wavev_cols16);
     if (plan && plan->csr16_base) (void)hipFree(plan->csr16_base);
     if (plan && plan->csr16_cols) (void)hipFree(plan->csr16_cols);
     if (plan && plan->runs_start) (void)hipFree(plan->runs_start);

@@ -547,6 +547,96 @@ int wave_partition_build(cmi_plan *p, const int *Ap, int k, hipStream_t s, int q
     return CMI_SUCCESS;
 }
 
+// ---------------------------------------------------------------------------------------------
+// csr_wavev's 16-bit column copy on that partition (round 9)
+// ---------------------------------------------------------------------------------------------
+// The entries of wave tile t are [start[2 t + 1], start[2 t + 3]): inside one tile of a banded / stencil matrix the columns span a few
+// thousand, so base[t] = the tile's smallest column (4 bytes per tile) and cols16[e] = Aj[e] - base[tile of e] (2 bytes per entry) say
+// what the 32-bit index says.  One wave per tile, as in the multiply: min / max (any tile with max - min > 65535, or a negative column,
+// refuses the whole copy), then the encoding.  An empty tile gets base 0.
+__global__ void __launch_bounds__(256)
+wavev_cols16_scan_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, const int *__restrict__ Aj, int32_t *__restrict__ base,
+                         int *__restrict__ bad)
+{
+    const int64_t wt = (int64_t)blockIdx.x * 4 + threadIdx.x / kWave;
+    if (wt >= wave_tiles) return; // (whole wave)
+    const int lane = threadIdx.x & (kWave - 1);
+    const int nz0 = start[2 * wt + 1], nz1 = start[2 * wt + 3];
+    int lo = INT32_MAX, hi = INT32_MIN;
+    for (int e = nz0 + lane; e < nz1; e += kWave) {
+        const int c = Aj[e];
+        lo = c < lo ? c : lo;
+        hi = c > hi ? c : hi;
+    }
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) {
+        const int l2 = __shfl_down(lo, o), h2 = __shfl_down(hi, o);
+        lo = l2 < lo ? l2 : lo;
+        hi = h2 > hi ? h2 : hi;
+    }
+    if (lane == 0) {
+        const bool empty = nz1 <= nz0;
+        base[wt] = empty ? 0 : lo;
+        if (!empty && ((int64_t)hi - lo > 65535 || lo < 0)) atomicOr(bad, 1);
+    }
+}
+
+__global__ void __launch_bounds__(256)
+wavev_cols16_encode_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, const int *__restrict__ Aj,
+                           const int32_t *__restrict__ base, uint16_t *__restrict__ cols16)
+{
+    const int64_t wt = (int64_t)blockIdx.x * 4 + threadIdx.x / kWave;
+    if (wt >= wave_tiles) return;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int nz0 = start[2 * wt + 1], nz1 = start[2 * wt + 3], b = base[wt];
+    for (int e = nz0 + lane; e < nz1; e += kWave) cols16[e] = (uint16_t)(Aj[e] - b);
+}
+
+// Tries to give `p` (a CSR plan that has its wave partition and runs csr_wavev) the 16-bit column copy.  Granted: the plan owns wavev_base /
+// wavev_cols16 and p->cfg.nontemporal carries kPolCols16.  Not granted (a tile spans more than 65535 columns, or no memory): nothing is kept,
+// the bit stays clear, the 32-bit kernel runs -- not an error.  Synchronises `s`.
+int wavev_cols16_build(cmi_plan *p, const int *Aj, hipStream_t s)
+{
+    p->cfg.nontemporal &= ~kPolCols16;
+    if (!p->wave_row_start || p->wave_tiles <= 0 || p->nnz <= 0 || !Aj) return CMI_SUCCESS;
+    const int64_t tiles = p->wave_tiles, nnz = p->nnz;
+    const unsigned grid = (unsigned)ceil_div(tiles, (int64_t)4);
+    const size_t cols_bytes = ((size_t)nnz + 8) * sizeof(uint16_t); // (zero padding: a vector load at the last entry stays inside the allocation)
+    int32_t *base = nullptr;
+    uint16_t *cols16 = nullptr;
+    int *flag = nullptr;
+    int host = 1;
+    hipError_t e = hipMalloc((void **)&base, (size_t)tiles * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc((void **)&flag, sizeof(int));
+    if (e == hipSuccess) e = hipMemsetAsync(flag, 0, sizeof(int), s);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(wavev_cols16_scan_kernel, dim3(grid), dim3(256), 0, s, p->wave_row_start, tiles, Aj, base, flag);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess && host == 0) {
+        e = hipMalloc((void **)&cols16, cols_bytes);
+        if (e == hipSuccess) e = hipMemsetAsync(cols16 + nnz, 0, 8 * sizeof(uint16_t), s);
+        if (e == hipSuccess) {
+            hipLaunchKernelGGL(wavev_cols16_encode_kernel, dim3(grid), dim3(256), 0, s, p->wave_row_start, tiles, Aj, base, cols16);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+    }
+    if (flag) (void)hipFree(flag);
+    if (e != hipSuccess || host != 0) {
+        if (base) (void)hipFree(base);
+        if (cols16) (void)hipFree(cols16);
+        if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return CMI_SUCCESS; } // (no room for the copy: the 32-bit kernel runs)
+        return e != hipSuccess ? hip_fail(e, "cmi_plan_create: csr_wavev 16-bit column copy") : (int)CMI_SUCCESS;
+    }
+    p->wavev_base = base;
+    p->wavev_cols16 = cols16;
+    p->cfg.nontemporal |= kPolCols16;
+    return CMI_SUCCESS;
+}
+
 template <typename T, int K, int POL, bool DOT>
 __global__ void __launch_bounds__(256)
 csr_wavep_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, const int *Ap /* not restrict: see the asm below */,
@@ -625,13 +715,20 @@ csr_wavep_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, const in
 // no flag, no plan memory, and no new way to go stale (L comes from the row offsets the partition was built from, at the same time).
 // On a stencil that is every tile without a boundary row: the row offsets (4 of the ~80 bytes per row) leave the stream.  Any other
 // tile, and every tile when uniform_len is 0, reads them as before.
+// C16 (round 9): the columns come from the plan's 16-bit copy (wavev_cols16_build above) -- E uint16 per load at the same entry positions,
+// a 4-byte (f64) / 8-byte (f32) request per lane instead of 8 / 16, and the tile's base with a scalar load whose address depends on wt
+// alone (issued with the partition entry: no extra dependent hop).  column = base + offset, clamped to the last column: the tile's first
+// vector may begin up to E - 1 entries before nz0 and the re-read last vector may end up to E - 1 entries past nz1 -- entries of the
+// neighbouring tiles, encoded against THEIR bases, whose products are parked and never read but whose gather address must stay inside
+// x.  One v_min per entry covers both ends (selecting the foreign positions costs a compare and a select per candidate position: more).
+// The !fits path (the arrays' last vector, an empty tile) reads the caller's 32-bit Aj, as before.
 // Four wave tiles per workgroup.
-template <typename T, int V, int POL, bool DOT>
+template <typename T, int V, int POL, bool DOT, bool C16>
 __global__ void __launch_bounds__(256)
 csr_wavev_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t num_entries, const int *Ap /* not restrict: see csr_wave */,
                  const int *__restrict__ Aj, const T *__restrict__ Ax, const T *__restrict__ x, T *__restrict__ y, int64_t num_tiles,
                  int64_t tiles_per_xcd, int swizzle, int accumulate, const T *__restrict__ w, double *__restrict__ dot_partial,
-                 int uniform_len)
+                 int uniform_len, const uint16_t *__restrict__ cols16, const int32_t *__restrict__ tile_base, int last_col)
 {
     // Request shape: every load instruction of the wave covers ONE contiguous span and every 128-byte line of the streams is requested
     // by exactly one instruction (csr_stream's f64 body asks for a lane's four values with two 16-byte loads 16 bytes apart: both
@@ -641,6 +738,8 @@ csr_wavev_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t 
     constexpr int E = sizeof(T) == 8 ? 2 : 4, NL = (V * 4) / E, SLOTS = kWave * V * 4;
     typedef int __attribute__((ext_vector_type(E))) idx_t;
     typedef T __attribute__((ext_vector_type(E))) val_t;
+    typedef unsigned __attribute__((ext_vector_type(2))) uint2v;
+    typedef std::conditional_t<E == 2, unsigned, uint2v> idx16_t; // E 16-bit offsets
     __shared__ __attribute__((aligned(16))) T prod[4][SLOTS];
     __shared__ double dot_slots[DOT ? 4 : 1];
     constexpr bool NT = (POL & kPolLoadNT) != 0, NTS = (POL & kPolStoreNT) != 0;
@@ -652,6 +751,8 @@ csr_wavev_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t 
     if (wt < wave_tiles) {
         const int2v lo = *reinterpret_cast<const int2v *>(start + 2 * wt), hi = *reinterpret_cast<const int2v *>(start + 2 * wt + 2);
         const int rs = lo.x, nz0 = lo.y, re = hi.x, nz1 = hi.y; // {first row, first entry} of this tile and of the next: one scalar hop
+        unsigned cbase = 0;
+        if constexpr (C16) cbase = (unsigned)tile_base[wt]; // (scalar, beside the partition entry)
         const int nr = re - rs;
         if (nr > 0) { // (uniform per wave)
             const int fbase = nz0 & ~(E - 1);
@@ -671,12 +772,14 @@ csr_wavev_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t 
                 const int last = (nz1 - 1) & ~(E - 1); // the last load position that holds an entry of the tile; lanes past it re-read it (and
                                                        // park products in their OWN slots, which nobody reads): no branch between the requests
                 idx_t c[NL];
+                idx16_t c16[NL];
                 val_t v[NL];
 #pragma unroll
                 for (int k = 0; k < NL; k++) {
                     int e = fbase + (k * kWave + lane) * E;
                     e = e < last ? e : last;
-                    c[k] = ld<NT>(reinterpret_cast<const idx_t *>(Aj + e));
+                    if constexpr (C16) c16[k] = ld<NT>(reinterpret_cast<const idx16_t *>(cols16 + e));
+                    else c[k] = ld<NT>(reinterpret_cast<const idx_t *>(Aj + e));
                 }
 #pragma unroll
                 for (int k = 0; k < NL; k++) {
@@ -685,6 +788,18 @@ csr_wavev_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t 
                     v[k] = ld<NT>(reinterpret_cast<const val_t *>(Ax + e));
                 }
                 __builtin_amdgcn_sched_barrier(0); // every stream request is out before the first gather address is formed
+                if constexpr (C16) {
+#pragma unroll
+                    for (int k = 0; k < NL; k++)
+#pragma unroll
+                        for (int i = 0; i < E; i++) {
+                            unsigned word;
+                            if constexpr (E == 2) word = c16[k];
+                            else word = c16[k][i / 2];
+                            const unsigned col = cbase + ((i & 1) ? word >> 16 : word & 0xffffu);
+                            c[k][i] = (int)(col < (unsigned)last_col ? col : (unsigned)last_col);
+                        }
+                }
                 val_t xv[NL];
 #pragma unroll
                 for (int k = 0; k < NL; k++)
@@ -1477,7 +1592,7 @@ static int launch_wave(const cmi_config &c, const cmi_plan *plan, int pol, hipSt
 
 // wave-private tiles, 16-byte-vector body, on the plan's row partition
 template <typename T>
-static int launch_wavev(const cmi_config &c, const cmi_plan *plan, int pol, hipStream_t s, int64_t nnz, const int *Ap, const int *Aj,
+static int launch_wavev(const cmi_config &c, const cmi_plan *plan, int pol, hipStream_t s, int64_t cols, int64_t nnz, const int *Ap, const int *Aj,
                         const T *Ax, const T *x, T *y, int accumulate, const T *w, double *dot_partial, int *dot_partials)
 {
     const int V = c.items_per_thread;
@@ -1493,12 +1608,16 @@ static int launch_wavev(const cmi_config &c, const cmi_plan *plan, int pol, hipS
     // the exact longest row (max_row_length_kernel, measured with the partition): a tile of nr rows and nr * that many entries has only
     // rows of that length and takes its row bounds from the partition entry; 0 = every tile reads the row offsets
     const int uniform_len = plan->prof.max_len >= 1 && plan->prof.max_len <= INT32_MAX ? (int)plan->prof.max_len : 0;
+    // the plan's 16-bit column copy: only where the plan was granted it (its config then carries the bit) and there is a column to clamp to
+    const bool c16 = (c.nontemporal & kPolCols16) && plan->wavev_cols16 && plan->wavev_base && cols > 0;
     with_policy(pol, [&](auto P) {
         with_int<1, 2, 4>(V, [&](auto VV) {
             with_bool(dot, [&](auto DOT) {
-                hipLaunchKernelGGL((csr_wavev_kernel<T, decltype(VV)::value, decltype(P)::value, decltype(DOT)::value>), dim3((unsigned)grid64),
-                                   dim3(256), 0, s, plan->wave_row_start, plan->wave_tiles, nnz, Ap, Aj, Ax, x, y, tiles, tpx, swz, accumulate, w,
-                                   dot_partial, uniform_len);
+                with_bool(c16, [&](auto C16) {
+                    hipLaunchKernelGGL((csr_wavev_kernel<T, decltype(VV)::value, decltype(P)::value, decltype(DOT)::value, decltype(C16)::value>),
+                                       dim3((unsigned)grid64), dim3(256), 0, s, plan->wave_row_start, plan->wave_tiles, nnz, Ap, Aj, Ax, x, y, tiles, tpx,
+                                       swz, accumulate, w, dot_partial, uniform_len, plan->wavev_cols16, plan->wavev_base, (int)(cols - 1));
+                });
             });
         });
     });
@@ -1704,7 +1823,7 @@ static int spmv_csr(int dtype, int64_t rows, int64_t cols, int64_t nnz, const in
         st = launch_stream(c, user, plan, known_max_len, pol, s, rows, nnz, Ap, Aj, Ax, x, y, accumulate, w, dot_partial, dot_partials);
         break;
     case CMI_CSR_STREAM_WAVE: st = launch_wave(c, plan, pol, s, rows, Ap, Aj, Ax, x, y, accumulate, w, dot_partial, dot_partials); break;
-    case CMI_CSR_STREAM_WAVEV: st = launch_wavev(c, plan, pol, s, nnz, Ap, Aj, Ax, x, y, accumulate, w, dot_partial, dot_partials); break;
+    case CMI_CSR_STREAM_WAVEV: st = launch_wavev(c, plan, pol, s, cols, nnz, Ap, Aj, Ax, x, y, accumulate, w, dot_partial, dot_partials); break;
     case CMI_CSR_STREAM_WAVEX:
         st = launch_wavex(c, plan, pol, s, rows, cols, nnz, Ap, Aj, Ax, x, y, accumulate, w, dot_partial, dot_partials);
         break;

@@ -246,7 +246,16 @@ typedef struct cmi_config {
                                  vectors per lane: faster for short rows (about 5 per row: 128 -> 124 us
                                  on the headline matrix), slower from ~25 per row; same bits either way.
                                  A table entry's bit 1 is dropped for a CSR matrix whose streams fit the
-                                 256 MiB Infinity Cache (it is then served from there when loaded plainly) */
+                                 256 MiB Infinity Cache (it is then served from there when loaded plainly);
+                                 8 (CMI_CSR_STREAM_WAVEV through cmi_plan_create_csr) = read the columns
+                                 from a plan-owned 16-bit copy -- per wave tile its smallest column, per
+                                 entry the offset from it -- instead of the caller's 32-bit array: 2 bytes
+                                 per entry less in the stream, 2 bytes per entry of plan memory, same bits.
+                                 Granted only when every tile spans at most 65535 columns and the plan was
+                                 made with the columns; otherwise the bit is cleared in cmi_plan_config's
+                                 answer and the 32-bit kernel runs.  Such a plan is stale after an in-place
+                                 edit of the columns (cmi_plan_validate tells).  Not a cache policy: ignored
+                                 everywhere else                                                        */
     int32_t xcd_swizzle;      /* CSR stream, ELL, DIA, COO tile: 0 = tiles (a workgroup's rows / entries) in
                                  launch order, 1 = one contiguous eighth of the tiles per XCD, C >= 2 =
                                  chunks of C tiles dealt round the XCDs (a chunk's x window is fetched into

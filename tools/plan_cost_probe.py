@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What a plan costs to make (one synchronising call per matrix) against the multiply it steers: headline matrix, every plan kind.
 
-    python tools/plan_cost_probe.py
+    python tools/plan_cost_probe.py [--headline-only]
 """
 import os
 import sys
@@ -48,6 +48,8 @@ def mult_us(fn, iters=200):
 rows = [
     ("CSR (row-length profile)", lambda: cmi.Plan(cmi.FORMAT_CSR, torch.float64, N, N, nnz, A.row_offsets), lambda: cmi.multiply(A, x, y)),
     ("CSR with the columns (what the containers make: + partition, + a look at the columns)", lambda: cmi.Plan.csr(torch.float64, N, N, A.row_offsets, A.column_indices), lambda: cmi.multiply(A, x, y)),
+    ("CSR csr_wavev V = 1 asked for, 32-bit columns", lambda: cmi.Plan.csr(torch.float64, N, N, A.row_offsets, A.column_indices, cfg=cmi.Config(kernel=cmi.CSR_STREAM_WAVEV, items_per_thread=1, nontemporal=3)), None),
+    ("CSR csr_wavev V = 1 asked for, + its 16-bit column copy (nontemporal bit 8)", lambda: cmi.Plan.csr(torch.float64, N, N, A.row_offsets, A.column_indices, cfg=cmi.Config(kernel=cmi.CSR_STREAM_WAVEV, items_per_thread=1, nontemporal=11)), None),
     ("CSR + 16-bit column copy", lambda: cmi.Plan.csr(torch.float64, N, N, A.row_offsets, A.column_indices, cfg=cmi.Config(kernel=cmi.CSR_STREAM_C16)), None),
     ("COO sorted (row offsets + CSR sub-plan)", lambda: cmi.Plan(cmi.FORMAT_COO, torch.float64, N, N, nnz, C.row_indices), lambda: cmi.multiply(C, x, y)),
     ("HYB K=4 (order check + tile ranges)", lambda: cmi.Plan.hyb(torch.float64, N, N, 4, H.coo.row_indices), lambda: cmi.multiply(H, x, y)),
@@ -60,7 +62,11 @@ for name, make, mult in rows:
         p = make()
         mult = lambda p=p: cmi.spmv_csr_plan(p, A.row_offsets, A.column_indices, A.values, x, y)  # noqa: E731
     m = mult_us(mult)
-    print(f"  {name:42s} {t:9.0f} us to create   {m:7.1f} us per multiply   = {t / m:5.1f} multiplies")
+    pb = make()
+    print(f"  {name:42s} {t:9.0f} us to create   {m:7.1f} us per multiply   = {t / m:5.1f} multiplies   (kernel {pb.config().kernel}, nontemporal {pb.config().nontemporal}, owns {pb.device_bytes() / 1e6:.1f} MB)")
+    del pb
+if "--headline-only" in sys.argv:
+    sys.exit(0)
 
 # round 4: the plans that own a copy derived from the columns / the values, on the matrices they are made for
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
