@@ -27,10 +27,11 @@ from .binding import (  # noqa: F401
     cg_update, cg_direction, cg_direction_x, HostScalar,
     blas_scal, blas_xmy, blas_axpbypcz, blas_asum, blas_amax, blas_axpy_dot, blas_axpy_ratio, csr_diagonal,
     pcg_update_jacobi, pcg_direction_x_jacobi, bicgstab_s, bicgstab_xr, bicgstab_p, cr_xr, cr_py,
+    csr_abs_row_sums, ell_abs_row_sums, dia_abs_row_sums, random_fill, blas_scal_recip,
     Comm, OP_SUM, OP_MAX, OP_MIN, csr_column_span,
 )
 from .matrices import (  # noqa: F401
-    CsrMatrix, CooMatrix, EllMatrix, DiaMatrix, HybMatrix, multiply, poisson5pt, convert,
+    CsrMatrix, CooMatrix, EllMatrix, DiaMatrix, HybMatrix, multiply, poisson5pt, convert, abs_row_sums, disks_spectral_radius,
     csr_bytes, ell_bytes, dia_bytes, coo_bytes, fill_x,
 )
 from . import binding, distributed, krylov  # noqa: F401,E402

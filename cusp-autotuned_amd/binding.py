@@ -234,6 +234,16 @@ def _declare(L):
         getattr(L, f"cmi_blas_axpy_dot_{suf}").argtypes = [i64, vp, vp, vp, vp, vp, vp, vp]
         getattr(L, f"cmi_blas_axpy_ratio_{suf}").argtypes = [i64, vp, vp, vp, vp, vp]
         getattr(L, f"cmi_csr_diagonal_{suf}").argtypes = [i64, vp, vp, vp, vp, c_int, vp]
+        # cusp::eigen's kernels (csrc/eigen.hip)
+        getattr(L, f"cmi_csr_abs_row_sums_{suf}").argtypes = [i64, vp, vp, vp, c_int, vp]
+        getattr(L, f"cmi_ell_abs_row_sums_{suf}").argtypes = [i64, i64, i64, i64, vp, vp, vp, vp, c_int, vp]
+        getattr(L, f"cmi_dia_abs_row_sums_{suf}").argtypes = [i64, i64, i64, i64, vp, vp, vp, c_int, vp]
+        getattr(L, f"cmi_random_fill_{suf}").argtypes = [i64, ctypes.c_uint64, vp, vp]
+        getattr(L, f"cmi_blas_scal_recip_{suf}").argtypes = [i64, vp, c_int, vp, vp, vp]
+    # host functions: the values cmi_random_fill_* writes
+    L.cmi_random_hash.restype, L.cmi_random_hash.argtypes = ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64]
+    L.cmi_random_unit_f64.restype, L.cmi_random_unit_f64.argtypes = c_double, [ctypes.c_uint64]
+    L.cmi_random_unit_f32.restype, L.cmi_random_unit_f32.argtypes = c_float, [ctypes.c_uint64]
     L.cmi_csr_column_span.argtypes = [i64, vp, POINTER(ctypes.c_int32), POINTER(ctypes.c_int32), vp]
     L.cmi_csr_rebase_offsets.argtypes = [i64, vp, ctypes.c_int32, vp, vp]
 
@@ -1077,6 +1087,60 @@ def blas_axpy_ratio(num, den, x, y, stream=None):
 def csr_diagonal(num_rows, Ap, Aj, Ax, diag, reciprocal=False, stream=None):
     """diag[i] <- the sum of row i's entries in column i, or its reciprocal."""
     check(getattr(lib(), "cmi_csr_diagonal_" + _suffix(diag))(num_rows, _ptr(Ap), _ptr(Aj), _ptr(Ax), _ptr(diag), int(bool(reciprocal)), _stream(stream)))
+
+
+# ------------------------------------------------------------------------------------------------
+# cusp::eigen's kernels (csrc/eigen.hip): absolute row sums per format, the start vector, the normalise step
+# ------------------------------------------------------------------------------------------------
+def csr_abs_row_sums(num_rows, Ap, Ax, row_sums, accumulate=False, stream=None):
+    """row_sums[i] (+)= sum of |Ax[Ap[i] .. Ap[i + 1])|: reads the row offsets and the values, never the columns."""
+    import torch
+    _need(Ap, "Ap", torch.int32)
+    _need(Ax, "Ax", row_sums.dtype)
+    _need(row_sums, "row_sums")
+    if Ap.numel() < num_rows + 1 or row_sums.numel() < num_rows:
+        raise ValueError("csr_abs_row_sums: array lengths do not match num_rows")
+    check(getattr(lib(), "cmi_csr_abs_row_sums_" + _suffix(row_sums))(num_rows, _ptr(Ap), _ptr(Ax), _ptr(row_sums), int(bool(accumulate)), _stream(stream)))
+
+
+def ell_abs_row_sums(num_rows, num_cols, width, pitch, Ax, row_sums, row_lengths=None, accumulate=False, stream=None):
+    """row_sums[i] (+)= sum over the row's slots of |Ax[n * pitch + i]| (padding holds 0; the column indices are not read)."""
+    import torch
+    _need(Ax, "Ax", row_sums.dtype)
+    _need(row_lengths, "row_lengths", torch.int32)
+    _need(row_sums, "row_sums")
+    if Ax.numel() < width * pitch or row_sums.numel() < num_rows:
+        raise ValueError("ell_abs_row_sums: array lengths do not match the matrix shape")
+    check(getattr(lib(), "cmi_ell_abs_row_sums_" + _suffix(row_sums))(num_rows, num_cols, width, pitch, None, _ptr(Ax), _ptr(row_lengths), _ptr(row_sums),
+                                                                     int(bool(accumulate)), _stream(stream)))
+
+
+def dia_abs_row_sums(num_rows, num_cols, num_diagonals, pitch, offsets, values, row_sums, accumulate=False, stream=None):
+    """row_sums[i] (+)= sum of |values[d * pitch + i]| over the diagonals whose column i + offsets[d] lies inside the matrix."""
+    import torch
+    _need(offsets, "offsets", torch.int32)
+    _need(values, "values", row_sums.dtype)
+    _need(row_sums, "row_sums")
+    if offsets.numel() != num_diagonals or values.numel() < num_diagonals * pitch or row_sums.numel() < num_rows:
+        raise ValueError("dia_abs_row_sums: array lengths do not match the matrix shape")
+    check(getattr(lib(), "cmi_dia_abs_row_sums_" + _suffix(row_sums))(num_rows, num_cols, num_diagonals, pitch, _ptr(offsets), _ptr(values), _ptr(row_sums),
+                                                                     int(bool(accumulate)), _stream(stream)))
+
+
+def random_fill(x, seed=0, stream=None):
+    """x[i] <- uniform in [0, 1), a function of (i, seed) alone (cusp::random_array's values)."""
+    _need(x, "x")
+    check(getattr(lib(), "cmi_random_fill_" + _suffix(x))(x.numel(), int(seed), _ptr(x), _stream(stream)))
+
+
+def blas_scal_recip(s, x, squared_norm=False, s_out=None, stream=None):
+    """x <- (1 / s) x with s in device memory: 1 element of x's dtype, or (squared_norm) a float64 holding a norm's square.
+    s_out (1 float64, optional) receives s."""
+    import torch
+    _need(s, "s", torch.float64 if squared_norm else x.dtype)
+    _need(x, "x")
+    _need(s_out, "s_out", torch.float64)
+    check(getattr(lib(), "cmi_blas_scal_recip_" + _suffix(x))(x.numel(), _ptr(s), int(bool(squared_norm)), _ptr(x), _ptr(s_out), _stream(stream)))
 
 
 class HostScalar:

@@ -12,6 +12,7 @@
 #include <iterator>
 #include <vector>
 
+#include "detail/random_hash.h"
 #include "format.h"
 #include "memory.h"
 
@@ -302,6 +303,47 @@ template <typename Src, typename Dst> void copy_array(const Src &src, Dst &dst)
     typedef typename Dst::value_type T;
     dst.resize(src.size());
     detail::raw_copy<T, typename Dst::memory_space, typename Src::memory_space>::run(dst.data(), reinterpret_cast<const T *>(src.data()), src.size());
+}
+
+// cusp::random_array<T>(n, seed = 0): n values that are a function of (position, seed) alone, uniform in [0, 1) for float / double (reference
+// cusp/array1d.h random_array, a view over cusp::random_iterator).  Nothing is stored: cusp::copy(random_array<T>(n), x) fills x where it lives --
+// a host array with the inline hash of cusp/detail/random_hash.h, a device array with cmi_random_fill_* (the same definition compiled for the device: no
+// host staging, the same bits).  The hash is the library's own (splitmix64's output function), NOT the reference's: its values differ.
+template <typename T> class random_array {
+public:
+    typedef T value_type;
+    typedef host_memory memory_space;
+    typedef array1d_format format;
+
+    explicit random_array(size_t n, size_t seed = 0) : size_(n), seed_(seed) {}
+    size_t size() const { return size_; }
+    size_t seed() const { return seed_; }
+    T operator[](size_t i) const { return value(detail::random_hash(i, seed_), static_cast<T *>(nullptr)); }
+
+private:
+    static double value(uint64_t h, double *p) { return detail::random_unit(h, p); }
+    static float value(uint64_t h, float *p) { return detail::random_unit(h, p); }
+    template <typename U> static U value(uint64_t h, U *) { return static_cast<U>(h); } // integer types: the hash itself, as in the reference
+    size_t size_, seed_;
+};
+namespace detail {
+template <typename T, typename Dst> void fill_random(const random_array<T> &src, Dst &dst, host_memory)
+{
+    for (size_t i = 0; i < src.size(); i++) dst[i] = static_cast<typename Dst::value_type>(src[i]);
+}
+inline int random_fill(size_t n, size_t seed, double *x) { return cmi_random_fill_f64(static_cast<int64_t>(n), seed, x, nullptr); }
+inline int random_fill(size_t n, size_t seed, float *x) { return cmi_random_fill_f32(static_cast<int64_t>(n), seed, x, nullptr); }
+template <typename T, typename Dst> void fill_random(const random_array<T> &src, Dst &dst, device_memory)
+{
+    static_assert(std::is_same<T, typename Dst::value_type>::value && (std::is_same<T, double>::value || std::is_same<T, float>::value),
+                  "cusp::copy(random_array<T>, x) into device_memory is implemented for x of the same type T = float or double");
+    check(random_fill(src.size(), src.seed(), dst.data()));
+}
+} // namespace detail
+template <typename T, typename Dst> void copy_array(const random_array<T> &src, Dst &dst)
+{
+    dst.resize(src.size());
+    detail::fill_random(src, dst, typename Dst::memory_space());
 }
 
 template <typename T> T *raw_pointer_cast(T *p) { return p; }

@@ -9,9 +9,10 @@
 //   nrm2(x) == 0                  the residual is b itself, no multiply (polynomial.inl:119-122).
 //
 // NOT declared: the one-argument polynomial(A), which estimates the spectral radius with
-// cusp::eigen::ritz_spectral_radius -- this library has no eigensolver.  Using it is a compile-time error; compute the
-// coefficients with detail::chebyshev_polynomial_coefficients(rho, coefficients) from a spectral radius of your own and
-// pass them to polynomial(A, coefficients).
+// cusp::eigen::ritz_spectral_radius.  Using it is a compile-time error with this header: the class stays free of the
+// eigensolver.  The reference constructor's recipe is the free factory of cusp/relaxation/chebyshev.h,
+// make_chebyshev_polynomial<ValueType, MemorySpace>(A); with a spectral radius of your own, compute the coefficients with
+// detail::chebyshev_polynomial_coefficients(rho, coefficients) and pass them to polynomial(A, coefficients).
 //
 //   host_memory and device_memory, all five formats: the reference's sequence through cusp::multiply and
 //                   cusp::blas::axpby / axpy -- on the device the matrix's planned multiply and one elementwise launch per step.

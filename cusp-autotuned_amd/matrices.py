@@ -221,6 +221,50 @@ def multiply(A, x, y, accumulate=False, cfg=None, stream=None):
     return y
 
 
+def abs_row_sums(A, row_sums=None, accumulate=False, stream=None):
+    """row_sums[i] (+)= row i of |A| 1 for any of the five containers (cmi_{csr,ell,dia}_abs_row_sums_*).  COO, and HYB's COO
+    part, go through the row offsets their row-sorted indices imply (cmi_coo_row_offsets) and the CSR kernel; entries
+    that are not sorted by row are an error here (sort_by_row() first)."""
+    import torch
+    values = A.ell.values if isinstance(A, HybMatrix) else A.values
+    if row_sums is None:
+        row_sums = torch.empty(A.num_rows, dtype=values.dtype, device=values.device)
+        accumulate = False
+    if isinstance(A, CsrMatrix):
+        B.csr_abs_row_sums(A.num_rows, A.row_offsets, A.values, row_sums, accumulate, stream)
+    elif isinstance(A, CooMatrix):
+        if A.num_entries == 0:
+            if not accumulate:
+                row_sums.zero_()
+            return row_sums
+        Ap = torch.empty(A.num_rows + 1, dtype=torch.int32, device=values.device)
+        if not B.coo_row_offsets(A.num_rows, A.row_indices, Ap, stream):
+            raise ValueError("abs_row_sums: the COO entries are not sorted by row (sort_by_row() first)")
+        B.csr_abs_row_sums(A.num_rows, Ap, A.values, row_sums, accumulate, stream)
+    elif isinstance(A, EllMatrix):
+        B.ell_abs_row_sums(A.num_rows, A.num_cols, A.num_entries_per_row, A.pitch, A.values, row_sums, A.row_lengths, accumulate, stream)
+    elif isinstance(A, DiaMatrix):
+        B.dia_abs_row_sums(A.num_rows, A.num_cols, A.diagonal_offsets.numel(), A.pitch, A.diagonal_offsets, A.values, row_sums, accumulate, stream)
+    elif isinstance(A, HybMatrix):
+        abs_row_sums(A.ell, row_sums, accumulate, stream)
+        abs_row_sums(A.coo, row_sums, True, stream)
+    else:
+        raise TypeError(f"abs_row_sums: unsupported matrix type {type(A).__name__}")
+    return row_sums
+
+
+def disks_spectral_radius(A, stream=None):
+    """cusp::eigen::disks_spectral_radius(A): the Gershgorin bound on rho(A), the largest absolute row sum -- the row-sum
+    kernel of A's format, cmi_blas_amax_* on the sums, one read."""
+    import torch
+    if A.num_rows == 0:
+        return 0.0
+    sums = abs_row_sums(A, stream=stream)
+    value = torch.empty(1, dtype=sums.dtype, device=sums.device)
+    B.blas_amax(sums, value, None, B.blas_workspace(sums.device), stream)
+    return float(value.item())
+
+
 # ------------------------------------------------------------------------------------------------
 # builders (setup, not the hot path)
 # ------------------------------------------------------------------------------------------------

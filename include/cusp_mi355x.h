@@ -853,6 +853,51 @@ int cmi_blas_axpy_dot_f32(int64_t n, const double *h_dev, const float *v, float 
 int cmi_blas_axpy_ratio_f64(int64_t n, const double *num_dev, const double *den_dev, const double *x, double *y, void *stream);
 int cmi_blas_axpy_ratio_f32(int64_t n, const double *num_dev, const double *den_dev, const float *x, float *y, void *stream);
 
+/* ------------------------------------------------------------------------- */
+/* What cusp::eigen's spectral-radius estimators need beside the multiply and BLAS-1 (csrc/eigen.hip; reference
+ * cusp/eigen/detail/spectral_radius.inl, arnoldi.inl).  No call below allocates or synchronises; n == 0 / num_rows == 0 is a no-op.
+ *
+ * Absolute row sums: row_sums[i] <- row i of |A| 1 as that format's multiply defines the row (accumulate != 0: added to what row_sums
+ * holds).  The Gershgorin radius (disks_spectral_radius: a COO view + thrust::reduce_by_key + max_element) is cmi_blas_amax_* of them.
+ *   CSR  the entries Ap[i] .. Ap[i + 1]; reads Ap and Ax and nothing else.  A row longer than a lane's share is summed by its wave.
+ *        A row-sorted COO matrix: cmi_coo_row_offsets, then this.  HYB: the ELL part, then the COO part with accumulate.
+ *   ELL  arguments in cmi_spmv_ell_*'s order without x and y; every slot of the row (padding holds 0, which the multiply relies on
+ *        too: Aj is not read and may be NULL), or the leading row_lengths[i] slots when row_lengths is given.
+ *   DIA  arguments in cmi_spmv_dia_*'s order without x and y; only positions whose column lies in [0, num_cols) are read.
+ * Sums are formed in the value type, in an order fixed by the arrays' shape (same arrays, same bits).                           */
+int cmi_csr_abs_row_sums_f64(int64_t num_rows, const int32_t *Ap, const double *Ax, double *row_sums, int accumulate, void *stream);
+int cmi_csr_abs_row_sums_f32(int64_t num_rows, const int32_t *Ap, const float *Ax, float *row_sums, int accumulate, void *stream);
+int cmi_ell_abs_row_sums_f64(int64_t num_rows, int64_t num_cols, int64_t num_entries_per_row, int64_t pitch, const int32_t *Aj, const double *Ax,
+                             const int32_t *row_lengths, double *row_sums, int accumulate, void *stream);
+int cmi_ell_abs_row_sums_f32(int64_t num_rows, int64_t num_cols, int64_t num_entries_per_row, int64_t pitch, const int32_t *Aj, const float *Ax,
+                             const int32_t *row_lengths, float *row_sums, int accumulate, void *stream);
+int cmi_dia_abs_row_sums_f64(int64_t num_rows, int64_t num_cols, int64_t num_diagonals, int64_t pitch, const int32_t *diagonal_offsets,
+                             const double *values, double *row_sums, int accumulate, void *stream);
+int cmi_dia_abs_row_sums_f32(int64_t num_rows, int64_t num_cols, int64_t num_diagonals, int64_t pitch, const int32_t *diagonal_offsets,
+                             const float *values, float *row_sums, int accumulate, void *stream);
+
+/* The start vector of the estimators (reference cusp::random_array behind cusp::copy): x[i] is a function of (i, seed) alone, uniform in
+ * [0, 1).  The hash is the splitmix64 output function (Steele, Lea, Flood 2014) of the state seed + (i + 1) * 0x9E3779B97F4A7C15 -- NOT
+ * the reference's integer hash, whose values are not reproduced.  f64: (h >> 11) * 2^-53, f32: (h >> 40) * 2^-24; both conversions are
+ * exact, so 1.0 never comes out.  cmi_random_hash / cmi_random_unit_* are HOST functions (no device call) that return what the kernel
+ * computes, for hosts that need the values without a device; C++ callers have the same definition inline (cusp/detail/random_hash.h,
+ * the one the kernel is compiled from).                                                                                         */
+uint64_t cmi_random_hash(uint64_t i, uint64_t seed);
+double cmi_random_unit_f64(uint64_t hash);
+float cmi_random_unit_f32(uint64_t hash);
+int cmi_random_fill_f64(int64_t n, uint64_t seed, double *x, void *stream);
+int cmi_random_fill_f32(int64_t n, uint64_t seed, float *x, void *stream);
+
+/* x <- (T(1) / T(s)) x with s taken from DEVICE memory: the normalise step without a host read in front of it.
+ *   s_is_squared_norm == 0: s = *(const T *)s_dev                    -- cmi_blas_amax_*'s value_dev (the power iteration)
+ *   s_is_squared_norm != 0: s = (T)sqrt(*(const double *)s_dev)      -- cmi_blas_axpy_dot_*'s out_dev with u = w; the root is taken in double
+ *                                                                       and rounded to T once
+ * The reciprocal is formed once in T and every element is multiplied by it: the bits of `beta = nrm2(w); scal(w, T(1) / beta)`.
+ * s_out_dev (may be NULL; not s_dev): receives s as a double -- exactly -- so that the next cmi_blas_axpy_dot_* can take it as its
+ * coefficient (Lanczos: w <- w - beta v_prev).                                                                                     */
+int cmi_blas_scal_recip_f64(int64_t n, const void *s_dev, int s_is_squared_norm, double *x, double *s_out_dev, void *stream);
+int cmi_blas_scal_recip_f32(int64_t n, const void *s_dev, int s_is_squared_norm, float *x, double *s_out_dev, void *stream);
+
 /* Fused steps of unpreconditioned CG (identity M, so z == r), scalars taken from DEVICE memory:
  * replaces dotc -> host -> axpy -> axpy -> copy -> dotc -> host -> axpby of
  * cusp/krylov/detail/cg.inl:83-103 (seven vector passes, three host syncs per iteration) by
