@@ -246,6 +246,15 @@ def _declare(L):
     L.cmi_random_unit_f32.restype, L.cmi_random_unit_f32.argtypes = c_float, [ctypes.c_uint64]
     L.cmi_csr_column_span.argtypes = [i64, vp, POINTER(ctypes.c_int32), POINTER(ctypes.c_int32), vp]
     L.cmi_csr_rebase_offsets.argtypes = [i64, vp, ctypes.c_int32, vp, vp]
+    # CSR x CSR (csrc/spgemm_csr.hip): the product comes back as a handle
+    for suf in ("f64", "f32"):
+        getattr(L, f"cmi_spgemm_csr_{suf}").argtypes = [i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, POINTER(c_void_p), vp]
+        getattr(L, f"cmi_spgemm_take_{suf}").argtypes = [vp, vp, vp, vp, i64, vp]
+    L.cmi_spgemm_num_entries.argtypes = [vp, POINTER(c_int64)]
+    L.cmi_spgemm_info.argtypes = [vp, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]
+    L.cmi_spgemm_destroy.argtypes = [vp]
+    L.cmi_spgemm_limits.argtypes = [POINTER(c_int64), POINTER(c_int64)]
+    L.cmi_spgemm_set_workspace.argtypes = [i64]
 
 
 def lib():
@@ -350,6 +359,51 @@ def spmm_csr(num_rows, num_cols, Ap, Aj, Ax, X, Y, accumulate=False, cfg=None, s
     fn = getattr(lib(), "cmi_spmm_csr_" + _suffix(Y))
     check(fn(num_rows, num_cols, Aj.numel(), _ptr(Ap), _ptr(Aj), _ptr(Ax), X.shape[1], _ptr(X), X.stride(0), X.stride(1),
              _ptr(Y), Y.stride(0), Y.stride(1), int(bool(accumulate)), _cfg(cfg), _stream(stream)))
+
+
+def spgemm_limits():
+    """cmi_spgemm_limits: (tile_products, workspace_products) in force now."""
+    t, w = c_int64(0), c_int64(0)
+    check(lib().cmi_spgemm_limits(byref(t), byref(w)))
+    return int(t.value), int(w.value)
+
+
+def spgemm_set_workspace(products):
+    """cmi_spgemm_set_workspace: products per slab of every later cmi_spgemm_csr_* (process-wide); 0: the default."""
+    check(lib().cmi_spgemm_set_workspace(int(products)))
+
+
+def spgemm_csr(m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, stream=None):
+    """cmi_spgemm_csr_* + cmi_spgemm_take_*: C = A B for CSR arrays on the device.  Returns (Cp, Cj, Cx, info) with new
+    tensors and info = what cmi_spgemm_info reported."""
+    import torch
+    for t, nm in ((Ap, "Ap"), (Aj, "Aj"), (Bp, "Bp"), (Bj, "Bj")):
+        _need(t, nm, torch.int32)
+    for t, nm in ((Ax, "Ax"), (Bx, "Bx")):
+        _need(t, nm, Ax.dtype)
+    if Ap.numel() != m + 1 or Bp.numel() != k + 1 or Aj.numel() != Ax.numel() or Bj.numel() != Bx.numel():
+        raise ValueError("spgemm_csr: array lengths do not match the matrix shapes")
+    suf = _suffix(Ax)
+    L = lib()
+    h = c_void_p()
+    check(getattr(L, "cmi_spgemm_csr_" + suf)(m, k, n, Aj.numel(), _ptr(Ap), _ptr(Aj), _ptr(Ax), Bj.numel(), _ptr(Bp), _ptr(Bj), _ptr(Bx),
+                                             byref(h), _stream(stream)))
+    try:
+        nnz, v = c_int64(0), [c_int64(0) for _ in range(4)]
+        check(L.cmi_spgemm_num_entries(h, byref(nnz)))
+        check(L.cmi_spgemm_info(h, *[byref(x) for x in v]))
+        Cp = torch.empty(m + 1, dtype=torch.int32, device=Ax.device)
+        Cj = torch.empty(nnz.value, dtype=torch.int32, device=Ax.device)
+        Cx = torch.empty(nnz.value, dtype=Ax.dtype, device=Ax.device)
+        check(getattr(L, "cmi_spgemm_take_" + suf)(h, _ptr(Cp), _ptr(Cj), _ptr(Cx), nnz.value, _stream(stream)))
+        if stream is None:
+            torch.cuda.current_stream().synchronize()  # the handle's pieces are read by the copies: finish before it goes
+        else:
+            stream.synchronize()
+    finally:
+        check(L.cmi_spgemm_destroy(h))
+    info = dict(zip(("products", "slabs", "rows_in_tiles", "rows_in_slabs"), (int(x.value) for x in v)))
+    return Cp, Cj, Cx, info
 
 
 def _plan_handle(plan):

@@ -26,10 +26,22 @@
 //                   way, cuda/detail/multiply/csr_block_spmv.h:198-201).
 // Other sparse formats with an array2d X, and mixed array1d / array2d arguments, are compile-time errors.
 //
+// Sparse products (SpGEMM): multiply(A, B, C) with three sparse matrices computes C = A B and resizes C (reference
+// generalized_spgemm; section "sparse x sparse" below).  csr x csr -> csr and coo x coo -> coo; every other combination is a
+// compile-time error naming cusp::convert.  Structure: one entry per (i, c) with a structural product, every row's columns ascending.
+// Values: s = 0; the products of the entry in expansion order (A's row in storage order, then B's row in storage order):
+// s = s + a * b -- the chain of sequential/multiply/csr_spgemm.h:102-131.
+//   host_memory   : that loop, generic in (combine, reduce); entries whose sum compares equal to zero are DROPPED, as the reference
+//                   drops them, and each row's columns are sorted (the reference leaves them in reverse first-touch order).
+//   device_memory : cmi_spgemm_csr_{f64,f32}; exact-zero sums are KEPT, as the reference's device path keeps them: the host
+//                   result is the device result with its zeros removed, bit for bit.  COO operands are converted to CSR on the
+//                   device (stable sort by row, row offsets) and the product back.  Standard functors only.
+//
 // Execution policies: multiply(exec, A, x, y) with cusp::hip::par.on(stream) selects the stream.  A
 // user-derived policy reaches a user-provided multiply overload by ADL without being copied
 // (testing/multiply.cu:792-858): see cusp/execution_policy.h.
 #pragma once
+#include <algorithm>
 #include <utility>
 #include <vector>
 #include "array1d.h"
@@ -370,11 +382,130 @@ template <typename A, typename X, typename Y> void device_block_multiply(const A
                    data_of(x), xrs, xcs, const_cast<V *>(data_of(y)), yrs, ycs, acc, stream));
 }
 
+// ---- sparse x sparse: C = A B with three sparse matrices (SpGEMM) ---------------------------------------------
+template <typename T, typename = void> struct is_sparse : std::false_type {};
+template <typename T> struct is_sparse<T, typename std::enable_if<std::is_base_of<sparse_format, typename T::format>::value>::type> : std::true_type {};
+struct sparse_product {}; // the third route tag beside std::false_type (vectors) and std::true_type (dense blocks)
+
+template <typename A, typename B, typename C> void require_spgemm_formats()
+{
+    typedef typename A::format FA;
+    static_assert(std::is_same<FA, typename B::format>::value && std::is_same<FA, typename C::format>::value &&
+                      (std::is_same<FA, csr_format>::value || std::is_same<FA, coo_format>::value),
+                  "cusp::multiply(A, B, C) with three sparse matrices is implemented for csr x csr -> csr and coo x coo -> coo only: bring A, B and C "
+                  "to one of these formats with cusp::convert first");
+}
+
+template <typename A, typename B> void check_product_shapes(const A &a, const B &b)
+{
+    if (a.num_cols != b.num_rows) throw cusp::invalid_input_exception("cusp::multiply: A.num_cols != B.num_rows in the sparse product C = A B");
+}
+
+// sequential/multiply/csr_spgemm.h:102-131 restated: one dense accumulator per column of B, reset after every row; a row's touched
+// columns are then SORTED (the reference emits them in reverse first-touch order) and sums that compare equal to zero are dropped.
+// `initialize` is not applied, as in the reference: every chain starts at V(0).
+template <typename A, typename B, typename C, typename Comb, typename Red>
+void host_spgemm(const A &a, const B &b, C &c, Comb combine, Red reduce, csr_format)
+{
+    typedef typename C::index_type I;
+    typedef typename C::value_type V;
+    std::vector<V> sums(b.num_cols, V(0)), Cx;
+    std::vector<char> seen(b.num_cols, 0);
+    std::vector<I> touched, Cp(a.num_rows + 1, I(0)), Cj;
+    for (size_t i = 0; i < a.num_rows; i++) {
+        touched.clear();
+        for (auto jj = a.row_offsets[i]; jj < a.row_offsets[i + 1]; jj++) {
+            const auto j = a.column_indices[jj];
+            const V v = a.values[jj];
+            for (auto kk = b.row_offsets[j]; kk < b.row_offsets[j + 1]; kk++) {
+                const I col = b.column_indices[kk];
+                sums[col] = reduce(sums[col], combine(v, V(b.values[kk])));
+                if (!seen[col]) {
+                    seen[col] = 1;
+                    touched.push_back(col);
+                }
+            }
+        }
+        std::sort(touched.begin(), touched.end());
+        for (const I col : touched) {
+            if (sums[col] != V(0)) {
+                Cj.push_back(col);
+                Cx.push_back(sums[col]);
+            }
+            sums[col] = V(0);
+            seen[col] = 0;
+        }
+        Cp[i + 1] = static_cast<I>(Cj.size());
+    }
+    c.resize(a.num_rows, b.num_cols, Cj.size()); // (after the loops: C may be A or B)
+    for (size_t i = 0; i <= c.num_rows; i++) c.row_offsets[i] = Cp[i];
+    for (size_t q = 0; q < Cj.size(); q++) {
+        c.column_indices[q] = Cj[q];
+        c.values[q] = Cx[q];
+    }
+}
+// COO: entries in any order -> CSR (stable by row: the chains are those of the storage order), the loop above, and back
+template <typename A, typename B, typename C, typename Comb, typename Red>
+void host_spgemm(const A &a, const B &b, C &c, Comb combine, Red reduce, coo_format)
+{
+    csr_matrix<typename A::index_type, typename A::value_type, host_memory> ca, cb, cc;
+    cusp::convert(a, ca);
+    cusp::convert(b, cb);
+    host_spgemm(ca, cb, cc, combine, reduce, csr_format());
+    cusp::convert(cc, c);
+}
+
+inline int spgemm_csr(int64_t m, int64_t k, int64_t n, int64_t na, const int *Ap, const int *Aj, const double *Ax, int64_t nb, const int *Bp, const int *Bj,
+                      const double *Bx, cmi_spgemm **r, void *s)
+{ return cmi_spgemm_csr_f64(m, k, n, na, Ap, Aj, Ax, nb, Bp, Bj, Bx, r, s); }
+inline int spgemm_csr(int64_t m, int64_t k, int64_t n, int64_t na, const int *Ap, const int *Aj, const float *Ax, int64_t nb, const int *Bp, const int *Bj,
+                      const float *Bx, cmi_spgemm **r, void *s)
+{ return cmi_spgemm_csr_f32(m, k, n, na, Ap, Aj, Ax, nb, Bp, Bj, Bx, r, s); }
+inline int spgemm_take(cmi_spgemm *r, int *Cp, int *Cj, double *Cx, int64_t cap, void *s) { return cmi_spgemm_take_f64(r, Cp, Cj, Cx, cap, s); }
+inline int spgemm_take(cmi_spgemm *r, int *Cp, int *Cj, float *Cx, int64_t cap, void *s) { return cmi_spgemm_take_f32(r, Cp, Cj, Cx, cap, s); }
+
+template <typename A, typename B, typename C> void device_spgemm(const A &a, const B &b, C &c, void *stream, csr_format)
+{
+    require_int_index<A>();
+    require_int_index<B>();
+    require_int_index<C>();
+    static_assert(std::is_same<typename A::value_type, typename B::value_type>::value && std::is_same<typename A::value_type, typename C::value_type>::value,
+                  "cusp::multiply(A, B, C) on device_memory: A, B and C must have the same value type");
+    struct handle { // the product lives in the library until it has been copied into C
+        cmi_spgemm *p = nullptr;
+        ~handle() { cmi_spgemm_destroy(p); }
+    } h;
+    check(spgemm_csr((int64_t)a.num_rows, (int64_t)a.num_cols, (int64_t)b.num_cols, (int64_t)a.num_entries, a.row_offsets.data(), a.column_indices.data(),
+                     a.values.data(), (int64_t)b.num_entries, b.row_offsets.data(), b.column_indices.data(), b.values.data(), &h.p, stream));
+    int64_t entries = 0;
+    check(cmi_spgemm_num_entries(h.p, &entries));
+    c.resize(a.num_rows, b.num_cols, (size_t)entries); // (A and B have been read: C may be one of them)
+    check(spgemm_take(h.p, c.row_offsets.data(), c.column_indices.data(), c.values.data(), entries, stream));
+    check(cmi_stream_synchronize(stream)); // the copies read the handle's arrays
+}
+// COO on the device: the existing device conversions around the CSR product (stable sort by row + row offsets in, row indices out)
+template <typename A, typename B, typename C> void device_spgemm(const A &a, const B &b, C &c, void *stream, coo_format)
+{
+    csr_matrix<int, typename A::value_type, device_memory> ca, cb, cc;
+    cusp::convert(a, ca);
+    cusp::convert(b, cb);
+    device_spgemm(ca, cb, cc, stream, csr_format());
+    cusp::convert(cc, c);
+}
+
+
 // the route every public overload takes: vectors -> the SpMV paths above, unchanged; array2d blocks -> SpMM
 template <typename X, typename Y> struct block_route {
     static_assert(is_block<X>::value == is_block<Y>::value,
                   "cusp::multiply: x and y must both be vectors (array1d) or both be dense blocks (array2d); mixed array1d / array2d arguments are not supported");
     typedef std::integral_constant<bool, is_block<X>::value> type;
+};
+// ... and two sparse matrices in the places of x and y -> the sparse product
+template <typename X, typename Y, bool Sparse = is_sparse<X>::value || is_sparse<Y>::value> struct operand_route : block_route<X, Y> {};
+template <typename X, typename Y> struct operand_route<X, Y, true> {
+    static_assert(is_sparse<X>::value && is_sparse<Y>::value,
+                  "cusp::multiply(A, B, C): B and C must both be sparse matrices (C = A B); a sparse matrix cannot stand for a vector or a dense block");
+    typedef sparse_product type;
 };
 
 template <typename A, typename X, typename Y, typename I, typename C, typename R, typename Space>
@@ -400,6 +531,21 @@ void multiply_route(const A &a, const X &x, Y &y, I init, C comb, R red, void *s
     if (a.num_rows == 0 || x.num_cols == 0) return;
     device_block_multiply(a, x, y, acc, stream);
 }
+template <typename A, typename B, typename C, typename I, typename Comb, typename R>
+void multiply_route(const A &a, const B &b, C &c, I, Comb comb, R red, void *, host_memory, sparse_product)
+{
+    require_spgemm_formats<A, B, C>();
+    check_product_shapes(a, b);
+    host_spgemm(a, b, c, comb, red, typename A::format());
+}
+template <typename A, typename B, typename C, typename I, typename Comb, typename R>
+void multiply_route(const A &a, const B &b, C &c, I init, Comb, R, void *stream, device_memory, sparse_product)
+{
+    require_spgemm_formats<A, B, C>();
+    check_product_shapes(a, b);
+    (void)device_functors<typename C::value_type, I, Comb, R>::accumulate(init); // plus / multiplies or cusp::not_implemented_exception
+    device_spgemm(a, b, c, stream, typename A::format());
+}
 
 } // namespace detail
 
@@ -414,7 +560,7 @@ void multiply(const LinearOperator &A, const Vector1 &x, Vector2 &y, UnaryFuncti
                       std::is_same<typename Vector1::memory_space, typename Vector2::memory_space>::value,
                   "cusp::multiply: A, x and y must live in the same memory space");
     detail::multiply_route(A, x, y, initialize, combine, reduce, nullptr, typename LinearOperator::memory_space(),
-                           typename detail::block_route<Vector1, Vector2>::type());
+                           typename detail::operand_route<Vector1, Vector2>::type());
 }
 
 // y = A*x (initialize = 0, combine = *, reduce = +: generic/multiply.inl:104-110)
@@ -447,7 +593,7 @@ void multiply(const cusp::hip::execution_policy &exec, const LinearOperator &A, 
               BinaryFunction1 combine, BinaryFunction2 reduce)
 {
     detail::multiply_route(A, x, y, initialize, combine, reduce, exec.stream(), typename LinearOperator::memory_space(),
-                           typename detail::block_route<Vector1, Vector2>::type());
+                           typename detail::operand_route<Vector1, Vector2>::type());
 }
 template <typename LinearOperator, typename Vector1, typename Vector2>
 void multiply(const cusp::hip::execution_policy &exec, const LinearOperator &A, const Vector1 &x, Vector2 &y)
@@ -491,6 +637,13 @@ void omp_route(const A &a, const X &x, Y &y, Init i, Comb c, Red r, std::true_ty
     check_block_shapes(a, x, y);
     host_block_multiply(a, x, y, i, c, r, true);
 }
+template <typename A, typename B, typename C, typename Init, typename Comb, typename Red>
+void omp_route(const A &a, const B &b, C &c, Init, Comb comb, Red red, sparse_product) // (the sequential loop: the reference's omp backend has no SpGEMM of its own)
+{
+    require_spgemm_formats<A, B, C>();
+    check_product_shapes(a, b);
+    host_spgemm(a, b, c, comb, red, typename A::format());
+}
 } // namespace detail
 
 template <typename LinearOperator, typename Vector1, typename Vector2, typename UnaryFunction, typename BinaryFunction1, typename BinaryFunction2>
@@ -498,7 +651,7 @@ void multiply(const cusp::omp::execution_policy &, const LinearOperator &A, cons
               BinaryFunction1 combine, BinaryFunction2 reduce)
 {
     static_assert(std::is_same<typename LinearOperator::memory_space, host_memory>::value, "cusp::omp::par runs on host_memory containers");
-    detail::omp_route(A, x, y, initialize, combine, reduce, typename detail::block_route<Vector1, Vector2>::type());
+    detail::omp_route(A, x, y, initialize, combine, reduce, typename detail::operand_route<Vector1, Vector2>::type());
 }
 template <typename LinearOperator, typename Vector1, typename Vector2>
 void multiply(const cusp::omp::execution_policy &exec, const LinearOperator &A, const Vector1 &x, Vector2 &y)

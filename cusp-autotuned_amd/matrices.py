@@ -221,6 +221,35 @@ def multiply(A, x, y, accumulate=False, cfg=None, stream=None):
     return y
 
 
+def spgemm(A, B_, stream=None):
+    """C = A B for two sparse matrices (the three-matrix cusp::multiply; cmi_spgemm_csr_*): CSR operands on the device, or on
+    the host (copied to the current device and the product copied back); COO operands go through convert(.., "csr").
+    Returns a new CsrMatrix with sorted rows; `.info` carries what cmi_spgemm_info reported (products, slabs,
+    rows_in_tiles, rows_in_slabs).  Exact-zero sums are kept as entries."""
+    import torch
+    ops = []
+    for M in (A, B_):
+        if isinstance(M, CooMatrix):
+            M = convert(M, "csr")
+        if not isinstance(M, CsrMatrix):
+            raise TypeError(f"spgemm: a CSR (or COO) matrix is needed, got {type(M).__name__}; convert(A, 'csr') first")
+        ops.append(M)
+    A, B_ = ops
+    if A.num_cols != B_.num_rows:
+        raise ValueError(f"spgemm: A has {A.num_cols} columns, B has {B_.num_rows} rows")
+    if A.values.dtype != B_.values.dtype:
+        raise TypeError("spgemm: A and B must have the same value type")
+    on_host = not A.values.is_cuda
+    dev = torch.device("cuda", torch.cuda.current_device()) if on_host else A.values.device
+    arrays = [t.to(dev).contiguous() for t in (A.row_offsets, A.column_indices, A.values, B_.row_offsets, B_.column_indices, B_.values)]
+    Cp, Cj, Cx, info = B.spgemm_csr(A.num_rows, A.num_cols, B_.num_cols, *arrays, stream=stream)
+    if on_host:
+        Cp, Cj, Cx = Cp.cpu(), Cj.cpu(), Cx.cpu()
+    C = CsrMatrix(A.num_rows, B_.num_cols, int(Cj.numel()), Cp, Cj, Cx)
+    C.info = info
+    return C
+
+
 def abs_row_sums(A, row_sums=None, accumulate=False, stream=None):
     """row_sums[i] (+)= row i of |A| 1 for any of the five containers (cmi_{csr,ell,dia}_abs_row_sums_*).  COO, and HYB's COO
     part, go through the row offsets their row-sorted indices imply (cmi_coo_row_offsets) and the CSR kernel; entries

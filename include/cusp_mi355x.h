@@ -454,6 +454,47 @@ int cmi_spmm_csr_f32(int64_t num_rows, int64_t num_cols, int64_t num_entries, co
                      const float *Ax, int64_t k, const float *X, int64_t x_row_stride, int64_t x_col_stride,
                      float *Y, int64_t y_row_stride, int64_t y_col_stride, int accumulate,
                      const cmi_config *cfg, void *stream);
+/* C = A B with A (m x k), B (k x n) and C in CSR (SpGEMM; spgemm_csr.hip).  Replaces the reference's generalized_spgemm
+ * (cusp/multiply.h; device path cuda/detail/multiply/spgemm.h); host-order oracle: sequential/multiply/csr_spgemm.h:102-131.
+ * Rows of A and B may be unsorted, may hold a column twice and may hold explicit zeros; B may have empty rows A points at.
+ *   Structure: one entry of C per distinct (i, c) with at least one structural product A(i,j) B(j,c); every row's columns
+ *     strictly ascending; it depends on the two patterns only -- an entry whose sum is exactly zero is KEPT.
+ *   Values: s = T(0); for jj over row i of A in storage order, for kk over row Aj[jj] of B in storage order with
+ *     Bj[kk] == c: s = s + (Ax[jj] * Bx[kk]); multiply and add rounded separately, one lane per entry, no atomics and no
+ *     re-association: bit for bit the host loop's chain (a lone product of -0.0 is stored as +0.0; NaN and Inf propagate).
+ * The size of C is not known in advance and the work is done once, so cmi_spgemm_csr_* returns a HANDLE that owns C on
+ * the device: read its size with cmi_spgemm_num_entries, copy it into arrays of your own with cmi_spgemm_take_* (Cp has
+ * m + 1 elements, Cj and Cx `capacity` >= num_entries; device to device on `stream`, may be called several times), free
+ * it with cmi_spgemm_destroy (NULL: a no-op).
+ * cmi_spgemm_csr_* allocates scratch (about 40 + sizeof(value) bytes per product of a slab, 8 bytes per entry of A and
+ * per row, all released on every path out) and synchronises the stream, as cmi_coo_sort_by_row_* does.  Method: the
+ * products are expanded in slabs of consecutive rows with at most W products (the workspace), sorted by (row, column)
+ * with a stable radix sort, and every (row, column) segment is summed in order by one lane.  A single row with more than
+ * W products: CMI_ERROR_NOT_SUPPORTED (the message names the row and its product count).  W: cmi_spgemm_set_workspace
+ * (process-wide, like cmi_set_index_compression; 0: back to the default = the lesser of the product count, 2^26 products
+ * and what a third of the free device memory holds).  cmi_spgemm_limits reports what is in force: tile_products (0: this
+ * build has no LDS tile path) and workspace_products (the value set, or the default's cap).
+ * Sizes: m, k, n <= INT32_MAX; entries of A, B and C <= INT32_MAX - 65536 (the CSR ceiling); the number of PRODUCTS may
+ * exceed 2^31 (counted in 64 bits).  Rejected with CMI_ERROR_INVALID_VALUE before any device call: negative sizes, sizes
+ * beyond the ceilings, null arrays with non-zero sizes, result == NULL, and in cmi_spgemm_take_* a capacity below
+ * num_entries.  m == 0 or no products at all: success, an all-zero Cp.  A column index of A outside [0, k) or of B outside
+ * [0, n) is the caller's error (garbage out), but no such index addresses scratch unclamped.
+ * cmi_spgemm_info: products expanded, slabs run, rows that went through LDS tiles (0 in this build) and through slabs.
+ * Callers find the feature by the symbol (CMI_VERSION is unchanged). */
+typedef struct cmi_spgemm cmi_spgemm;
+int cmi_spgemm_csr_f64(int64_t m, int64_t k, int64_t n, int64_t a_entries, const int32_t *Ap, const int32_t *Aj,
+                       const double *Ax, int64_t b_entries, const int32_t *Bp, const int32_t *Bj, const double *Bx,
+                       cmi_spgemm **result, void *stream);
+int cmi_spgemm_csr_f32(int64_t m, int64_t k, int64_t n, int64_t a_entries, const int32_t *Ap, const int32_t *Aj,
+                       const float *Ax, int64_t b_entries, const int32_t *Bp, const int32_t *Bj, const float *Bx,
+                       cmi_spgemm **result, void *stream);
+int cmi_spgemm_num_entries(const cmi_spgemm *r, int64_t *num_entries);
+int cmi_spgemm_take_f64(cmi_spgemm *r, int32_t *Cp, int32_t *Cj, double *Cx, int64_t capacity, void *stream);
+int cmi_spgemm_take_f32(cmi_spgemm *r, int32_t *Cp, int32_t *Cj, float *Cx, int64_t capacity, void *stream);
+int cmi_spgemm_info(const cmi_spgemm *r, int64_t *products, int64_t *slabs, int64_t *rows_in_tiles, int64_t *rows_in_slabs);
+int cmi_spgemm_destroy(cmi_spgemm *r);
+int cmi_spgemm_limits(int64_t *tile_products, int64_t *workspace_products);
+int cmi_spgemm_set_workspace(int64_t products);
 /* A CSR row sweep with a fixed elementwise write-back (spmv_csr_epilogue.hip): the smoothers that are an SpMV followed at
  * once by passes over the vector it wrote, in one launch.  s_i is row i's sum exactly as cmi_spmv_csr_* forms it: from
  * T(0), entries in storage order, multiply then add, by one lane; the same lane evaluates the expression once and
