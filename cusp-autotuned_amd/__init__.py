@@ -28,6 +28,7 @@ from .binding import (  # noqa: F401
     blas_scal, blas_xmy, blas_axpbypcz, blas_asum, blas_amax, blas_axpy_dot, blas_axpy_ratio, csr_diagonal,
     pcg_update_jacobi, pcg_direction_x_jacobi, bicgstab_s, bicgstab_xr, bicgstab_p, cr_xr, cr_py,
     csr_abs_row_sums, ell_abs_row_sums, dia_abs_row_sums, random_fill, blas_scal_recip,
+    csr_strength_symmetric, csr_scale_rows, aggregates_fit, csr_elementwise, relax_jacobi_presmooth,
     Comm, OP_SUM, OP_MAX, OP_MIN, csr_column_span,
 )
 from .matrices import (  # noqa: F401

@@ -255,6 +255,13 @@ def _declare(L):
     L.cmi_spgemm_destroy.argtypes = [vp]
     L.cmi_spgemm_limits.argtypes = [POINTER(c_int64), POINTER(c_int64)]
     L.cmi_spgemm_set_workspace.argtypes = [i64]
+    # smoothed aggregation's set-up kernels (csrc/amg.hip)
+    for suf, real in (("f64", c_double), ("f32", c_float)):
+        getattr(L, f"cmi_csr_strength_symmetric_{suf}").argtypes = [i64, i64, i64, vp, vp, vp, c_double, vp, vp, vp, i64, vp]
+        getattr(L, f"cmi_csr_scale_rows_{suf}").argtypes = [i64, i64, vp, vp, vp, real, vp, vp]
+        getattr(L, f"cmi_aggregates_fit_{suf}").argtypes = [i64, i64, vp, vp, vp, vp, vp, i64, vp, vp]
+        getattr(L, f"cmi_csr_elementwise_{suf}").argtypes = [i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, c_int, vp, vp, vp, i64, POINTER(c_int), vp]
+        getattr(L, f"cmi_relax_jacobi_presmooth_{suf}").argtypes = [i64, vp, vp, real, vp, vp]
 
 
 def lib():
@@ -404,6 +411,95 @@ def spgemm_csr(m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, stream=None):
         check(L.cmi_spgemm_destroy(h))
     info = dict(zip(("products", "slabs", "rows_in_tiles", "rows_in_slabs"), (int(x.value) for x in v)))
     return Cp, Cj, Cx, info
+
+
+# ------------------------------------------------------------------------------------------------
+# smoothed aggregation's set-up kernels (csrc/amg.hip).  Outputs are new tensors cut to the entry count.
+# ------------------------------------------------------------------------------------------------
+def csr_strength_symmetric(num_rows, Ap, Aj, Ax, theta=0.0, stream=None):
+    """cmi_csr_strength_symmetric_*: the entries of the square CSR matrix A with |A_ij| >= theta * sqrt(|A_ii| |A_jj|), in
+    storage order.  Returns (Sp, Sj, Sx)."""
+    import torch
+    for t, nm in ((Ap, "Ap"), (Aj, "Aj")):
+        _need(t, nm, torch.int32)
+    _need(Ax, "Ax")
+    if Ap.numel() != num_rows + 1 or Aj.numel() != Ax.numel():
+        raise ValueError("csr_strength_symmetric: array lengths do not match the matrix shape")
+    nnz = Aj.numel()
+    Sp = torch.empty(num_rows + 1, dtype=torch.int32, device=Ax.device)
+    Sj = torch.empty(nnz, dtype=torch.int32, device=Ax.device)
+    Sx = torch.empty(nnz, dtype=Ax.dtype, device=Ax.device)
+    check(getattr(lib(), "cmi_csr_strength_symmetric_" + _suffix(Ax))(num_rows, num_rows, nnz, _ptr(Ap), _ptr(Aj), _ptr(Ax), float(theta), _ptr(Sp),
+                                                                      _ptr(Sj), _ptr(Sx), nnz, _stream(stream)))
+    kept = int(Sp[num_rows].item())
+    return Sp, Sj[:kept].clone(), Sx[:kept].clone()
+
+
+def csr_scale_rows(num_rows, Ap, Ax, d, lam, out=None, stream=None):
+    """cmi_csr_scale_rows_*: out[e] = (Ax[e] / d[row(e)]) * lam; out=None: a new tensor, out=Ax: in place."""
+    import torch
+    _need(Ap, "Ap", torch.int32)
+    if out is None:
+        out = torch.empty_like(Ax)
+    for t, nm in ((Ax, "Ax"), (d, "d"), (out, "out")):
+        _need(t, nm, Ax.dtype)
+    if Ap.numel() != num_rows + 1 or d.numel() != num_rows or out.numel() != Ax.numel():
+        raise ValueError("csr_scale_rows: array lengths do not match the matrix shape")
+    check(getattr(lib(), "cmi_csr_scale_rows_" + _suffix(Ax))(num_rows, Ax.numel(), _ptr(Ap), _ptr(Ax), _ptr(d), float(lam), _ptr(out), _stream(stream)))
+    return out
+
+
+def aggregates_fit(aggregates, B_, num_aggregates, stream=None):
+    """cmi_aggregates_fit_*: the tentative prolongator of one candidate vector.  Returns (Tp, Tj, Tx, R); aggregates[i] == -1
+    leaves row i empty, an id outside [-1, num_aggregates) raises CmiError."""
+    import torch
+    _need(aggregates, "aggregates", torch.int32)
+    _need(B_, "B")
+    n = aggregates.numel()
+    if B_.numel() != n:
+        raise ValueError("aggregates_fit: aggregates and B must have the same length")
+    Tp = torch.empty(n + 1, dtype=torch.int32, device=B_.device)
+    Tj = torch.empty(n, dtype=torch.int32, device=B_.device)
+    Tx = torch.empty(n, dtype=B_.dtype, device=B_.device)
+    R = torch.empty(num_aggregates, dtype=B_.dtype, device=B_.device)
+    check(getattr(lib(), "cmi_aggregates_fit_" + _suffix(B_))(n, num_aggregates, _ptr(aggregates), _ptr(B_), _ptr(Tp), _ptr(Tj), _ptr(Tx), n, _ptr(R),
+                                                              _stream(stream)))
+    kept = int(Tp[n].item())
+    return Tp, Tj[:kept].clone(), Tx[:kept].clone(), R
+
+
+def csr_elementwise(num_rows, num_cols, Ap, Aj, Ax, Bp, Bj, Bx, op="add", stream=None):
+    """cmi_csr_elementwise_*: C = A + B (op "add") or A - B ("subtract") for CSR operands with rows sorted by column.  Returns
+    (Cp, Cj, Cx), or None when an operand is not sorted (nothing was computed: sort it first)."""
+    import torch
+    for t, nm in ((Ap, "Ap"), (Aj, "Aj"), (Bp, "Bp"), (Bj, "Bj")):
+        _need(t, nm, torch.int32)
+    for t, nm in ((Ax, "Ax"), (Bx, "Bx")):
+        _need(t, nm, Ax.dtype)
+    if op not in ("add", "subtract"):
+        raise ValueError("csr_elementwise: op is 'add' or 'subtract'")
+    if Ap.numel() != num_rows + 1 or Bp.numel() != num_rows + 1 or Aj.numel() != Ax.numel() or Bj.numel() != Bx.numel():
+        raise ValueError("csr_elementwise: array lengths do not match the matrix shape")
+    cap = Aj.numel() + Bj.numel()
+    Cp = torch.empty(num_rows + 1, dtype=torch.int32, device=Ax.device)
+    Cj = torch.empty(cap, dtype=torch.int32, device=Ax.device)
+    Cx = torch.empty(cap, dtype=Ax.dtype, device=Ax.device)
+    ok = c_int(0)
+    check(getattr(lib(), "cmi_csr_elementwise_" + _suffix(Ax))(num_rows, num_cols, Aj.numel(), _ptr(Ap), _ptr(Aj), _ptr(Ax), Bj.numel(), _ptr(Bp), _ptr(Bj),
+                                                               _ptr(Bx), int(op == "subtract"), _ptr(Cp), _ptr(Cj), _ptr(Cx), cap, byref(ok), _stream(stream)))
+    if not ok.value:
+        return None
+    kept = int(Cp[num_rows].item())
+    return Cp, Cj[:kept].clone(), Cx[:kept].clone()
+
+
+def relax_jacobi_presmooth(diag, b, omega, x, stream=None):
+    """cmi_relax_jacobi_presmooth_*: x[i] = (omega * b[i]) / diag[i] -- a Jacobi sweep from x = 0."""
+    for t, n in ((diag, "diag"), (b, "b"), (x, "x")):
+        _need(t, n, x.dtype)
+    if diag.numel() != x.numel() or b.numel() != x.numel():
+        raise ValueError("relax_jacobi_presmooth: vectors must have the same length")
+    check(getattr(lib(), "cmi_relax_jacobi_presmooth_" + _suffix(x))(x.numel(), _ptr(diag), _ptr(b), float(omega), _ptr(x), _stream(stream)))
 
 
 def _plan_handle(plan):

@@ -33,6 +33,22 @@ inline void indices_to_offsets(const array1d<int, device_memory> &indices, array
     offsets = ho;
 }
 
+namespace detail {
+// c <- the device CSR matrix t whose arrays were allocated at their bound and filled from the front: the entry count is the last row offset
+template <typename V, typename C> void take_compacted(const csr_matrix<int, V, device_memory> &t, C &c)
+{
+    int entries = 0;
+    check(cmi_memcpy_d2h(&entries, t.row_offsets.data() + t.num_rows, sizeof(int), nullptr));
+    c.resize(t.num_rows, t.num_cols, (size_t)entries);
+    check(cmi_memcpy_d2d(c.row_offsets.data(), t.row_offsets.data(), (t.num_rows + 1) * sizeof(int), nullptr));
+    if (entries) {
+        check(cmi_memcpy_d2d(c.column_indices.data(), t.column_indices.data(), (size_t)entries * sizeof(int), nullptr));
+        check(cmi_memcpy_d2d(c.values.data(), t.values.data(), (size_t)entries * sizeof(V), nullptr));
+    }
+    check(cmi_stream_synchronize(nullptr));
+}
+} // namespace detail
+
 // extract_diagonal(A, output): output[i] = A(i, i) -- 0 where the diagonal entry is not stored, the SUM where it is stored more than once
 // (reference cusp/format_utils.h:184, generic/format_utils.inl extract_diagonal per format).  Set-up work (the Jacobi preconditioner's
 // constructor): on a host copy of the matrix in CSR form, whatever A's format and memory space; `output` may live in either space.

@@ -495,6 +495,59 @@ int cmi_spgemm_info(const cmi_spgemm *r, int64_t *products, int64_t *slabs, int6
 int cmi_spgemm_destroy(cmi_spgemm *r);
 int cmi_spgemm_limits(int64_t *tile_products, int64_t *workspace_products);
 int cmi_spgemm_set_workspace(int64_t products);
+/* The set-up kernels of smoothed-aggregation multigrid (amg.hip).  Each returns the bits of the sequential loop
+ * stated with it: every value is produced by one lane in a fixed order, without atomics, each operation rounded on its own.
+ * Every output is bounded by its inputs: the caller allocates the bound (`capacity` elements) and the call compacts into
+ * it; the entry count is the last row offset.  Rejected with CMI_ERROR_INVALID_VALUE before any device call: negative
+ * sizes, sizes beyond the ceilings (rows and columns < INT32_MAX, entries <= INT32_MAX - 65536), null arrays with non-zero
+ * sizes, a capacity below the bound.  Row offsets that decrease or leave [0, entries] are the caller's error (garbage out),
+ * but they are clamped before they address anything, and nothing is written at or beyond `capacity`.
+ * strength, fit and elementwise allocate scratch (released on every path out) and synchronise the stream; scale_rows and
+ * jacobi_presmooth allocate nothing and do not synchronise.
+ *
+ * cmi_csr_strength_symmetric_*: S = the entries of the square matrix A with |A_ij| >= theta * sqrt(|A_ii| * |A_jj|), in
+ *   storage order (reference precond/aggregation symmetric_strength_of_connection, its sequential loop).  The product and
+ *   the correctly rounded square root are formed in the value type, the product with theta and the comparison in double;
+ *   a NaN on either side drops the entry.  A_ii is what cmi_csr_diagonal_* gives: 0 where no diagonal is stored, the
+ *   storage-order sum where it is stored more than once; a column outside the matrix has A_jj = 0.  Rows of up to 64
+ *   entries are filtered by one lane, longer rows by their wave (ballot and popcount).  capacity >= num_entries.
+ * cmi_csr_scale_rows_*: out[e] = (Ax[e] / d[row(e)]) * lambda, the division first (smooth_prolongator's two host loops);
+ *   out may be Ax.  Ap[0] == 0 and Ap[num_rows] == num_entries are assumed.
+ * cmi_aggregates_fit_*: the reference's fit_candidates for one candidate vector B.  aggregates[i] in [0, num_aggregates) or
+ *   -1 (row i is in no aggregate).  T (n x num_aggregates, CSR) has one entry B[i] / R[aggregates[i]] in every aggregated
+ *   row and an empty row otherwise; R[a] = sqrt(sum of B[i] * B[i] over the rows of aggregate a), added in ascending row
+ *   order starting from the first square (not from +0); an id that no row uses gets R[a] = 0.  An id >= num_aggregates or
+ *   < -1 is refused (CMI_ERROR_INVALID_VALUE, nothing written; a device flag read once).  capacity >= n.
+ * cmi_csr_elementwise_*: C = A + B (op 0) or C = A - B (op 1) for operands of one shape whose rows are sorted by column
+ *   (a column may repeat).  C(i,j) is the left-to-right sum of A's entries at (i,j) in storage order, then B's, starting
+ *   from the first of them; for op 1 every value of B is negated and then added.  A result that compares equal to zero is
+ *   dropped (NaN is kept); C's columns are strictly ascending.  *sorted_host = 1 when both operands met the ordering
+ *   contract (offsets from 0 to the entry count without a decrease, columns inside the matrix and not decreasing in a row;
+ *   found on the device, read once); 0: nothing was written.  capacity >= a_entries + b_entries <= INT32_MAX - 65536.
+ *   One lane merges a row: long rows are a known gap.
+ * cmi_relax_jacobi_presmooth_*: x[i] = (omega * b[i]) / d[i], the product first (the reference's jacobi_presmooth_functor:
+ *   one Jacobi sweep from x = 0 without the multiply).  x may be b.
+ * Callers find the feature by the symbols (CMI_VERSION is unchanged). */
+int cmi_csr_strength_symmetric_f64(int64_t num_rows, int64_t num_cols, int64_t num_entries, const int32_t *Ap, const int32_t *Aj,
+                                   const double *Ax, double theta, int32_t *Sp, int32_t *Sj, double *Sx, int64_t capacity, void *stream);
+int cmi_csr_strength_symmetric_f32(int64_t num_rows, int64_t num_cols, int64_t num_entries, const int32_t *Ap, const int32_t *Aj,
+                                   const float *Ax, double theta, int32_t *Sp, int32_t *Sj, float *Sx, int64_t capacity, void *stream);
+int cmi_csr_scale_rows_f64(int64_t num_rows, int64_t num_entries, const int32_t *Ap, const double *Ax, const double *d, double lambda,
+                           double *out, void *stream);
+int cmi_csr_scale_rows_f32(int64_t num_rows, int64_t num_entries, const int32_t *Ap, const float *Ax, const float *d, float lambda,
+                           float *out, void *stream);
+int cmi_aggregates_fit_f64(int64_t n, int64_t num_aggregates, const int32_t *aggregates, const double *B, int32_t *Tp, int32_t *Tj,
+                           double *Tx, int64_t capacity, double *R, void *stream);
+int cmi_aggregates_fit_f32(int64_t n, int64_t num_aggregates, const int32_t *aggregates, const float *B, int32_t *Tp, int32_t *Tj,
+                           float *Tx, int64_t capacity, float *R, void *stream);
+int cmi_csr_elementwise_f64(int64_t num_rows, int64_t num_cols, int64_t a_entries, const int32_t *Ap, const int32_t *Aj, const double *Ax,
+                            int64_t b_entries, const int32_t *Bp, const int32_t *Bj, const double *Bx, int op, int32_t *Cp, int32_t *Cj,
+                            double *Cx, int64_t capacity, int *sorted_host, void *stream);
+int cmi_csr_elementwise_f32(int64_t num_rows, int64_t num_cols, int64_t a_entries, const int32_t *Ap, const int32_t *Aj, const float *Ax,
+                            int64_t b_entries, const int32_t *Bp, const int32_t *Bj, const float *Bx, int op, int32_t *Cp, int32_t *Cj,
+                            float *Cx, int64_t capacity, int *sorted_host, void *stream);
+int cmi_relax_jacobi_presmooth_f64(int64_t n, const double *d, const double *b, double omega, double *x, void *stream);
+int cmi_relax_jacobi_presmooth_f32(int64_t n, const float *d, const float *b, float omega, float *x, void *stream);
 /* A CSR row sweep with a fixed elementwise write-back (spmv_csr_epilogue.hip): the smoothers that are an SpMV followed at
  * once by passes over the vector it wrote, in one launch.  s_i is row i's sum exactly as cmi_spmv_csr_* forms it: from
  * T(0), entries in storage order, multiply then add, by one lane; the same lane evaluates the expression once and
