@@ -191,6 +191,7 @@ def _declare(L):
     L.cmi_plan_create_csr_values.argtypes = [c_int, i64, i64, i64, vp, vp, vp, cfgp, vp, POINTER(c_void_p)]
     L.cmi_plan_validate_values.argtypes = [vp, vp, vp, POINTER(c_int)]
     L.cmi_plan_device_bytes.argtypes = [vp, POINTER(c_int64)]
+    L.cmi_plan_wavev_shift_tiles.argtypes = [vp, POINTER(c_int64)]
     L.cmi_set_index_compression.argtypes = [c_int]
     L.cmi_plan_hyb_launches.argtypes = [vp, POINTER(c_int)]
     L.cmi_plan_create_hyb.argtypes = [c_int, i64, i64, i64, i64, vp, cfgp, cfgp, vp, POINTER(c_void_p)]
@@ -639,6 +640,13 @@ class Plan:
     def device_bytes(self):
         n = c_int64()
         check(lib().cmi_plan_device_bytes(self._h, byref(n)))
+        return n.value
+
+    def shifted_tiles(self):
+        """cmi_plan_wavev_shift_tiles: the wave tiles a csr_wavev plan with the 16-bit column copy multiplies without reading a column
+        (rows of the tile = its first row's columns moved along with the row); 0 when the plan keeps no such table."""
+        n = c_int64()
+        check(lib().cmi_plan_wavev_shift_tiles(self._h, byref(n)))
         return n.value
 
     @classmethod

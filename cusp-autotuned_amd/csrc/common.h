@@ -310,6 +310,12 @@ struct cmi_plan {
     // entries, and per entry the 16-bit offset from its tile's base.  Both or neither (every tile spans at most 65535 columns, or nothing is kept).
     int32_t *wavev_base = nullptr;    // device, wave_tiles entries
     uint16_t *wavev_cols16 = nullptr; // device, nnz + 8 entries (zero padding), 16-byte aligned
+    // ... and, part of that copy (round 13), the SHIFT-INVARIANT tiles' table: int32 [wave_tiles][8], 32-byte aligned.  A tile of nr >= 1
+    // rows of the longest row's length L <= 8 in which row r has row 0's columns plus r is MARKED: entry k < L holds Aj[nz0 + k] minus the
+    // tile's first row, and the multiply forms its columns from these and reads none.  Entry 0 == INT32_MIN: not marked.  Kept only with the
+    // copy and only when at least a quarter of the tiles that have entries are marked (wavev_cols16_build); null otherwise.
+    int32_t *wavev_shift = nullptr;
+    int64_t wavev_shift_marked = 0;   // marked tiles (0 without the table)
     // order-sensitive 64-bit checksums of the arrays the plan was made from (cmi_plan_validate): the index array (CSR row offsets, COO /
     // HYB-COO row indices) and -- when the plan owns data derived from them (the 16-bit copy) -- the CSR column indices
     uint64_t fp_index = 0, fp_columns = 0;

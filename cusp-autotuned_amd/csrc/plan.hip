@@ -388,6 +388,7 @@ CMI_API int cmi_plan_device_bytes(const cmi_plan *plan, int64_t *bytes)
     if (plan->coo_offsets) b += (plan->rows + 1) * 4;
     if (plan->wave_row_start) b += (plan->wave_tiles + 1) * 8;
     if (plan->wavev_cols16) b += (plan->nnz + 8) * 2 + plan->wave_tiles * 4;
+    if (plan->wavev_shift) b += plan->wave_tiles * 32;
     if (plan->csr16_cols) b += (plan->nnz + 8) * 2;
     if (plan->csr16_base) b += ceil_div(plan->rows, plan->cfg.rows_per_block > 0 ? plan->cfg.rows_per_block : 1) * 4;
     if (plan->runs_start) b += (plan->wave_tiles + 1) * 16;
@@ -815,6 +816,13 @@ CMI_API int cmi_plan_hyb_launches(const cmi_plan *plan, int *launches)
     return CMI_SUCCESS;
 }
 
+CMI_API int cmi_plan_wavev_shift_tiles(const cmi_plan *plan, int64_t *marked)
+{
+    if (!plan || !marked) return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_wavev_shift_tiles: null argument");
+    *marked = plan->wavev_shift ? plan->wavev_shift_marked : 0;
+    return CMI_SUCCESS;
+}
+
 CMI_API int cmi_plan_destroy(cmi_plan *plan)
 {
     if (plan && plan->hyb_tile_start) (void)hipFree(plan->hyb_tile_start);
@@ -824,6 +832,7 @@ CMI_API int cmi_plan_destroy(cmi_plan *plan)
     if (plan && plan->wave_row_start) (void)hipFree(plan->wave_row_start);
     if (plan && plan->wavev_base) (void)hipFree(plan->wavev_base);
     if (plan && plan->wavev_cols16) (void)hipFree(plan->wavev_cols16);
+    if (plan && plan->wavev_shift) (void)hipFree(plan->wavev_shift);
     if (plan && plan->csr16_base) (void)hipFree(plan->csr16_base);
     if (plan && plan->csr16_cols) (void)hipFree(plan->csr16_cols);
     if (plan && plan->runs_start) (void)hipFree(plan->runs_start);

@@ -554,19 +554,43 @@ int wave_partition_build(cmi_plan *p, const int *Ap, int k, hipStream_t s, int q
 // thousand, so base[t] = the tile's smallest column (4 bytes per tile) and cols16[e] = Aj[e] - base[tile of e] (2 bytes per entry) say
 // what the 32-bit index says.  One wave per tile, as in the multiply: min / max (any tile with max - min > 65535, or a negative column,
 // refuses the whole copy), then the encoding.  An empty tile gets base 0.
+// SHIFT-INVARIANT tiles (round 13), in the same pass over Aj: with L the longest row (1..8), a tile of nr >= 1 rows and nr L entries (every
+// row L long: csr_wavev's uniform test) in which Aj[nz0 + r L + k] == Aj[nz0 + k] + r for every row r and k < L is MARKED -- the columns
+// of its first row say all of them.  shift[t][k] = Aj[nz0 + k] - (the tile's first row) for k < L, 0 above; shift[t][0] = INT32_MIN on
+// every other tile (no column minus row reaches it: both lie in [0, INT32_MAX]).  Sorted or not, duplicates or not: entry positions are
+// not touched.  r = p / L as (p mul) >> 16 with mul = ceil(65536 / L), exact for p < 4096 (a wavev tile holds fewer than 1024 entries).
+constexpr int kShiftMaxLen = 8;
+__host__ __device__ inline unsigned shift_div_mul(int L) { return (65536u + (unsigned)L - 1u) / (unsigned)L; }
+
 __global__ void __launch_bounds__(256)
 wavev_cols16_scan_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, const int *__restrict__ Aj, int32_t *__restrict__ base,
-                         int *__restrict__ bad)
+                         int *__restrict__ bad, int32_t *__restrict__ shift, int L, unsigned mul)
 {
     const int64_t wt = (int64_t)blockIdx.x * 4 + threadIdx.x / kWave;
     if (wt >= wave_tiles) return; // (whole wave)
     const int lane = threadIdx.x & (kWave - 1);
-    const int nz0 = start[2 * wt + 1], nz1 = start[2 * wt + 3];
+    const int rs = start[2 * wt], nz0 = start[2 * wt + 1], re = start[2 * wt + 2], nz1 = start[2 * wt + 3];
+    const int nr = re - rs, cnt = nz1 - nz0;
+    // (uniform per wave) a candidate: rows of L entries only, and few enough for the multiplier
+    const bool cand = shift != nullptr && nr >= 1 && cnt < 4096 && (int64_t)cnt == (int64_t)nr * L;
+    int first = 0; // lanes k < L: the first row's k-th column
+    if (cand && lane < L) first = Aj[nz0 + lane];
     int lo = INT32_MAX, hi = INT32_MIN;
-    for (int e = nz0 + lane; e < nz1; e += kWave) {
-        const int c = Aj[e];
-        lo = c < lo ? c : lo;
-        hi = c > hi ? c : hi;
+    bool same = true;
+    for (int e0 = nz0; e0 < nz1; e0 += kWave) { // (uniform bound: every lane of the wave takes part in the shuffle of every turn)
+        const int e = e0 + lane;
+        const bool in = e < nz1;
+        int c = 0;
+        if (in) {
+            c = Aj[e];
+            lo = c < lo ? c : lo;
+            hi = c > hi ? c : hi;
+        }
+        if (cand) {
+            const unsigned p = (unsigned)(e - nz0), r = (p * mul) >> 16, k = p - r * (unsigned)L;
+            const int f = __shfl(first, (int)(k & (kShiftMaxLen - 1)));
+            same = same && (!in || (int64_t)c == (int64_t)f + (int64_t)r);
+        }
     }
 #pragma unroll
     for (int o = kWave / 2; o > 0; o >>= 1) {
@@ -574,10 +598,29 @@ wavev_cols16_scan_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, 
         lo = l2 < lo ? l2 : lo;
         hi = h2 > hi ? h2 : hi;
     }
+    if (shift != nullptr) {
+        const bool marked = cand && __all(same);
+        if (lane < kShiftMaxLen) shift[8 * wt + lane] = marked ? (lane < L ? first - rs : 0) : (lane == 0 ? INT32_MIN : 0);
+    }
     if (lane == 0) {
         const bool empty = nz1 <= nz0;
         base[wt] = empty ? 0 : lo;
         if (!empty && ((int64_t)hi - lo > 65535 || lo < 0)) atomicOr(bad, 1);
+    }
+}
+
+// counts[0] += marked tiles, counts[1] += tiles that have entries: one thread per tile, one pair of atomics per workgroup
+__global__ void __launch_bounds__(256)
+wavev_shift_count_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, const int32_t *__restrict__ shift,
+                         unsigned long long *__restrict__ counts)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool in = t < wave_tiles;
+    const int marked = __syncthreads_count(in && shift[8 * t] != INT32_MIN);
+    const int with_entries = __syncthreads_count(in && start[2 * t + 3] > start[2 * t + 1]);
+    if (threadIdx.x == 0) {
+        if (marked) atomicAdd(counts, (unsigned long long)marked);
+        if (with_entries) atomicAdd(counts + 1, (unsigned long long)with_entries);
     }
 }
 
@@ -595,6 +638,10 @@ wavev_cols16_encode_kernel(const int32_t *__restrict__ start, int64_t wave_tiles
 // Tries to give `p` (a CSR plan that has its wave partition and runs csr_wavev) the 16-bit column copy.  Granted: the plan owns wavev_base /
 // wavev_cols16 and p->cfg.nontemporal carries kPolCols16.  Not granted (a tile spans more than 65535 columns, or no memory): nothing is kept,
 // the bit stays clear, the 32-bit kernel runs -- not an error.  Synchronises `s`.
+// The shift-invariant tiles' table comes with a granted copy (no bit, no switch of its own): filled by the scan when the longest row has
+// 1..8 entries, kept iff marked tiles >= 1/4 of the tiles that have entries -- the table costs 32 bytes for EVERY tile and a marked tile
+// stops fetching about 2 x 256 V bytes of columns, so the bytes break even near 1/16; 1/4 leaves room for the extra scalar load and the
+// ALU work (a condition, not a measurement).  Below that, or without memory for it: freed, and the plan is the plan of the copy alone.
 int wavev_cols16_build(cmi_plan *p, const int *Aj, hipStream_t s)
 {
     p->cfg.nontemporal &= ~kPolCols16;
@@ -602,15 +649,27 @@ int wavev_cols16_build(cmi_plan *p, const int *Aj, hipStream_t s)
     const int64_t tiles = p->wave_tiles, nnz = p->nnz;
     const unsigned grid = (unsigned)ceil_div(tiles, (int64_t)4);
     const size_t cols_bytes = ((size_t)nnz + 8) * sizeof(uint16_t); // (zero padding: a vector load at the last entry stays inside the allocation)
-    int32_t *base = nullptr;
+    const int L = p->prof.max_len >= 1 && p->prof.max_len <= kShiftMaxLen ? (int)p->prof.max_len : 0;
+    int32_t *base = nullptr, *shift = nullptr;
     uint16_t *cols16 = nullptr;
     int *flag = nullptr;
+    unsigned long long *counts = nullptr;
     int host = 1;
+    unsigned long long host_counts[2] = {0, 0};
     hipError_t e = hipMalloc((void **)&base, (size_t)tiles * sizeof(int32_t));
     if (e == hipSuccess) e = hipMalloc((void **)&flag, sizeof(int));
     if (e == hipSuccess) e = hipMemsetAsync(flag, 0, sizeof(int), s);
+    if (e == hipSuccess && L > 0) {
+        if (hipMalloc((void **)&shift, (size_t)tiles * 8 * sizeof(int32_t)) != hipSuccess || hipMalloc((void **)&counts, sizeof(host_counts)) != hipSuccess ||
+            hipMemsetAsync(counts, 0, sizeof(host_counts), s) != hipSuccess) { // (no room for the table: the copy alone)
+            (void)hipGetLastError();
+            if (shift) (void)hipFree(shift);
+            shift = nullptr;
+        }
+    }
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(wavev_cols16_scan_kernel, dim3(grid), dim3(256), 0, s, p->wave_row_start, tiles, Aj, base, flag);
+        hipLaunchKernelGGL(wavev_cols16_scan_kernel, dim3(grid), dim3(256), 0, s, p->wave_row_start, tiles, Aj, base, flag, shift, L > 0 ? L : 1,
+                           shift_div_mul(L > 0 ? L : 1));
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, s);
@@ -622,17 +681,30 @@ int wavev_cols16_build(cmi_plan *p, const int *Aj, hipStream_t s)
             hipLaunchKernelGGL(wavev_cols16_encode_kernel, dim3(grid), dim3(256), 0, s, p->wave_row_start, tiles, Aj, base, cols16);
             e = hipGetLastError();
         }
+        if (e == hipSuccess && shift) {
+            hipLaunchKernelGGL(wavev_shift_count_kernel, dim3((unsigned)ceil_div(tiles, (int64_t)256)), dim3(256), 0, s, p->wave_row_start, tiles, shift, counts);
+            e = hipGetLastError();
+            if (e == hipSuccess) e = hipMemcpyAsync(host_counts, counts, sizeof(host_counts), hipMemcpyDeviceToHost, s);
+        }
         if (e == hipSuccess) e = hipStreamSynchronize(s);
     }
     if (flag) (void)hipFree(flag);
+    if (counts) (void)hipFree(counts);
     if (e != hipSuccess || host != 0) {
         if (base) (void)hipFree(base);
         if (cols16) (void)hipFree(cols16);
+        if (shift) (void)hipFree(shift);
         if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return CMI_SUCCESS; } // (no room for the copy: the 32-bit kernel runs)
         return e != hipSuccess ? hip_fail(e, "cmi_plan_create: csr_wavev 16-bit column copy") : (int)CMI_SUCCESS;
     }
+    if (shift && !(host_counts[0] >= 1 && 4 * host_counts[0] >= host_counts[1])) { // (too few marked tiles to pay for 32 bytes per tile)
+        (void)hipFree(shift);
+        shift = nullptr;
+    }
     p->wavev_base = base;
     p->wavev_cols16 = cols16;
+    p->wavev_shift = shift;
+    p->wavev_shift_marked = shift ? (int64_t)host_counts[0] : 0;
     p->cfg.nontemporal |= kPolCols16;
     return CMI_SUCCESS;
 }
@@ -722,14 +794,26 @@ csr_wavep_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, const in
 // neighbouring tiles, encoded against THEIR bases, whose products are parked and never read but whose gather address must stay inside
 // x.  One v_min per entry covers both ends (selecting the foreign positions costs a compare and a select per candidate position: more).
 // The !fits path (the arrays' last vector, an empty tile) reads the caller's 32-bit Aj, as before.
+// SH (round 13; only with C16): the plan also holds the shift-invariant tiles' table (wavev_cols16_scan_kernel above).  Its first word is
+// fetched with a scalar load beside the partition entry and the base (address from wt alone); a MARKED tile -- always an equal-length one,
+// so uniform_len is its row length L -- then takes a wave-uniform branch in front of the stream requests and asks for NO column at all:
+// lane l picks up shift[wt][l & 7] with one vector load (32 bytes per wave, issued first), the value requests go out as ever, and behind
+// the barrier position p = e + i - nz0 of the lane's vectors gives r = p / L = (p div_mul) >> 16 (24-bit multiplies: full rate; exact for
+// p < 4096, a tile has fewer than 1024), k = p - r L and column = min(rs + r + shift[k], last column) with shift[k] read from lane k by a
+// ds_bpermute -- one LDS-crossbar instruction per entry, no LDS memory, where a compare / select chain over eight SGPRs costs 2 (L - 1)
+// VALU instructions per entry.  Positions before nz0 (p wraps) and past nz1 form some column that the same unsigned minimum keeps inside
+// x; their products are parked and never read.  Everything else -- row bounds, parking, sums, epilogues -- is shared with the other tiles;
+// an unmarked tile runs the C16 path above.
 // Four wave tiles per workgroup.
-template <typename T, int V, int POL, bool DOT, bool C16>
+template <typename T, int V, int POL, bool DOT, bool C16, bool SH = false>
 __global__ void __launch_bounds__(256)
 csr_wavev_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t num_entries, const int *Ap /* not restrict: see csr_wave */,
                  const int *__restrict__ Aj, const T *__restrict__ Ax, const T *__restrict__ x, T *__restrict__ y, int64_t num_tiles,
                  int64_t tiles_per_xcd, int swizzle, int accumulate, const T *__restrict__ w, double *__restrict__ dot_partial,
-                 int uniform_len, const uint16_t *__restrict__ cols16, const int32_t *__restrict__ tile_base, int last_col)
+                 int uniform_len, const uint16_t *__restrict__ cols16, const int32_t *__restrict__ tile_base, int last_col,
+                 const int32_t *__restrict__ shift, unsigned div_mul)
 {
+    static_assert(C16 || !SH, "the shift-invariant tiles' table belongs to the 16-bit column copy");
     // Request shape: every load instruction of the wave covers ONE contiguous span and every 128-byte line of the streams is requested
     // by exactly one instruction (csr_stream's f64 body asks for a lane's four values with two 16-byte loads 16 bytes apart: both
     // instructions touch every line, which is why the nt hint COSTS that body 13-17 %, profiles/r03_long_rows_policy_sweep.txt).
@@ -753,6 +837,12 @@ csr_wavev_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t 
         const int rs = lo.x, nz0 = lo.y, re = hi.x, nz1 = hi.y; // {first row, first entry} of this tile and of the next: one scalar hop
         unsigned cbase = 0;
         if constexpr (C16) cbase = (unsigned)tile_base[wt]; // (scalar, beside the partition entry)
+        bool marked = false;
+        if constexpr (SH) { // (scalar, beside them: this tile's columns are its first row's plus the row)
+            int first_shift = shift[8 * wt];
+            asm volatile("" : "+s"(first_shift)); // requested HERE, with the partition entry, not where the branch on it stands
+            marked = first_shift != INT32_MIN;
+        }
         const int nr = re - rs;
         if (nr > 0) { // (uniform per wave)
             const int fbase = nz0 & ~(E - 1);
@@ -774,12 +864,17 @@ csr_wavev_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t 
                 idx_t c[NL];
                 idx16_t c16[NL];
                 val_t v[NL];
+                int shl = 0;
+                if (SH && marked) { // (uniform per wave) no column request: lane l holds shift[wt][l & 7]
+                    shl = shift[8 * wt + (lane & 7)];
+                } else {
 #pragma unroll
-                for (int k = 0; k < NL; k++) {
-                    int e = fbase + (k * kWave + lane) * E;
-                    e = e < last ? e : last;
-                    if constexpr (C16) c16[k] = ld<NT>(reinterpret_cast<const idx16_t *>(cols16 + e));
-                    else c[k] = ld<NT>(reinterpret_cast<const idx_t *>(Aj + e));
+                    for (int k = 0; k < NL; k++) {
+                        int e = fbase + (k * kWave + lane) * E;
+                        e = e < last ? e : last;
+                        if constexpr (C16) c16[k] = ld<NT>(reinterpret_cast<const idx16_t *>(cols16 + e));
+                        else c[k] = ld<NT>(reinterpret_cast<const idx_t *>(Aj + e));
+                    }
                 }
 #pragma unroll
                 for (int k = 0; k < NL; k++) {
@@ -788,7 +883,19 @@ csr_wavev_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t 
                     v[k] = ld<NT>(reinterpret_cast<const val_t *>(Ax + e));
                 }
                 __builtin_amdgcn_sched_barrier(0); // every stream request is out before the first gather address is formed
-                if constexpr (C16) {
+                if (SH && marked) {
+#pragma unroll
+                    for (int k = 0; k < NL; k++) {
+                        int e = fbase + (k * kWave + lane) * E;
+                        e = e < last ? e : last;
+#pragma unroll
+                        for (int i = 0; i < E; i++) {
+                            const unsigned p = (unsigned)(e + i - nz0), r = __umul24(p, div_mul) >> 16, kk = p - __umul24(r, (unsigned)uniform_len);
+                            const unsigned col = (unsigned)(rs + (int)r + __builtin_amdgcn_ds_bpermute((int)(kk << 2), shl));
+                            c[k][i] = (int)(col < (unsigned)last_col ? col : (unsigned)last_col);
+                        }
+                    }
+                } else if constexpr (C16) {
 #pragma unroll
                     for (int k = 0; k < NL; k++)
 #pragma unroll
@@ -1610,13 +1717,17 @@ static int launch_wavev(const cmi_config &c, const cmi_plan *plan, int pol, hipS
     const int uniform_len = plan->prof.max_len >= 1 && plan->prof.max_len <= INT32_MAX ? (int)plan->prof.max_len : 0;
     // the plan's 16-bit column copy: only where the plan was granted it (its config then carries the bit) and there is a column to clamp to
     const bool c16 = (c.nontemporal & kPolCols16) && plan->wavev_cols16 && plan->wavev_base && cols > 0;
+    // 0: the caller's 32-bit columns; 1: the plan's 16-bit copy; 2: ... and its shift-invariant tiles' table (only ever built for rows of 1..8)
+    const int columns_from = !c16 ? 0 : (plan->wavev_shift && uniform_len >= 1 && uniform_len <= kShiftMaxLen) ? 2 : 1;
     with_policy(pol, [&](auto P) {
         with_int<1, 2, 4>(V, [&](auto VV) {
             with_bool(dot, [&](auto DOT) {
-                with_bool(c16, [&](auto C16) {
-                    hipLaunchKernelGGL((csr_wavev_kernel<T, decltype(VV)::value, decltype(P)::value, decltype(DOT)::value, decltype(C16)::value>),
+                with_int<0, 1, 2>(columns_from, [&](auto CF) {
+                    constexpr int cf = decltype(CF)::value;
+                    hipLaunchKernelGGL((csr_wavev_kernel<T, decltype(VV)::value, decltype(P)::value, decltype(DOT)::value, cf >= 1, cf == 2>),
                                        dim3((unsigned)grid64), dim3(256), 0, s, plan->wave_row_start, plan->wave_tiles, nnz, Ap, Aj, Ax, x, y, tiles, tpx,
-                                       swz, accumulate, w, dot_partial, uniform_len, plan->wavev_cols16, plan->wavev_base, (int)(cols - 1));
+                                       swz, accumulate, w, dot_partial, uniform_len, plan->wavev_cols16, plan->wavev_base, (int)(cols - 1),
+                                       plan->wavev_shift, shift_div_mul(uniform_len > 0 ? uniform_len : 1));
                 });
             });
         });

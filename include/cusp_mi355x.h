@@ -385,6 +385,12 @@ int cmi_plan_create_csr_values(int dtype, int64_t num_rows, int64_t num_cols, in
 int cmi_plan_validate_values(const cmi_plan *plan, const void *values, void *stream, int *valid_host);
 /* Bytes of device memory the plan owns (partitions, offsets, column copies, packed tiles).                                           */
 int cmi_plan_device_bytes(const cmi_plan *plan, int64_t *bytes);
+/* How many wave tiles of a csr_wavev plan that owns the 16-bit column copy (cfg.nontemporal bit 8 in cmi_plan_config) are multiplied   */
+/* WITHOUT reading any column: tiles of equal-length rows (1..8 entries) in which every row has the first row's columns moved by the   */
+/* row's distance from it -- constant stencils, Toeplitz / multi-diagonal matrices, a rank block with global columns.  The plan keeps   */
+/* the first row's shifts of every tile (32 bytes per tile, counted by cmi_plan_device_bytes, guarded by cmi_plan_validate with the     */
+/* copy) when at least a quarter of the tiles that have entries qualify; *marked = 0 for every plan that keeps no such table.            */
+int cmi_plan_wavev_shift_tiles(const cmi_plan *plan, int64_t *marked);
 int cmi_set_index_compression(int on);
 int cmi_get_index_compression(void);
 /* HYB: launch shapes of both parts (cfg_* may be NULL) and, when the COO part's row indices are sorted (what every     */
