@@ -60,6 +60,9 @@ struct row_profile { int64_t max_len = -1, in_long = 0; }; // max_len < 0: not m
 int measure_row_lengths(int64_t rows, const int *Ap, hipStream_t s, int64_t *max_len, int64_t *entries_in_long_rows, int64_t *ends = nullptr); // ends: {Ap[0], Ap[rows]}
 int measure_column_locality(int64_t rows, int64_t cols, const int *Ap, const int *Aj, int halfwin, hipStream_t s, int64_t *inside, int64_t *jumps); // spmv_csr.hip
 bool prefers_balanced(int64_t rows, int64_t nnz, const row_profile &pr, size_t value_bytes, bool strict_order);
+// plan.hip: *c takes a wave-tile kernel's launch shape (block 256, the kernel's own request shape) and, unless keep_policy, the cache policy of
+// streams read once: nt loads when nnz * bytes_per_entry lies beyond 1.25 x the Infinity Cache, nt stores
+void adopt_wave_shape(cmi_config *c, int64_t nnz, int kernel, int rows_per_block, int items_per_thread, int64_t bytes_per_entry, bool keep_policy);
 // are the row indices of a COO matrix non-decreasing and inside [0, rows)?  (spmv_coo_hyb.hip; synchronises the stream)
 int coo_rows_sorted(int64_t rows, int64_t nnz, const int *Ai, hipStream_t s, int *sorted, int *long_runs = nullptr); // long_runs: a row of > 1024 entries
 // ELL lanes per row (spmv_ell_dia.hip): 1 = the row kernel (storage-order sums), 2..16 = the slices kernel.  Auto rule,

@@ -215,7 +215,7 @@ static bool wavev_auto(int64_t rows, int64_t nnz, const row_profile &prof, int v
 //   f64, fewer than 8 entries per row, jumps < 0.5: V = 1.
 //   inside < 0.05 with jumps >= 0.6 (scattered): csr_stream stays (wave tiles 0.97-1.06x: a wash).
 //   f32 rows of 16+ entries with jumps < 0.5 -- or columns unknown -- : csr_stream stays (27-point-like / nlpkkt120-like f32: wave tiles 1.05-1.06x).
-struct column_profile { double jumps = -1.0, inside = -1.0; }; // < 0: not measured
+struct column_profile { double jumps = -1.0, inside = -1.0; int64_t jump_count = 0; bool measured = false; }; // < 0: not measured (jump_count: jumps as counted)
 static int wavev_env()
 {
     static const int env = [] { const char *e = std::getenv("CMI_CSR_WAVEV"); return e ? std::atoi(e) : -1; }();
@@ -262,6 +262,26 @@ static int wavev_vectors(int64_t rows, int64_t nnz, const row_profile &prof, boo
     return wavev_auto(rows, nnz, prof, v, vbytes) ? v : 0;
 }
 
+// Adopts a wave-tile launch shape (declared in common.h: the plan-less stencil rule of spmv_csr.hip uses it too): 256 lanes, no lane groups,
+// the kernel's own request shape and -- unless a caller's policy bits are kept as given -- the cache policy of streams read once.
+// bytes_per_entry: what one entry adds to the streams this kernel reads (index + value, or the plan-owned copy that replaces the index).
+void cmi::adopt_wave_shape(cmi_config *c, int64_t nnz, int kernel, int rows_per_block, int items_per_thread, int64_t bytes_per_entry, bool keep_policy)
+{
+    c->kernel = kernel;
+    c->block_size = 256;
+    c->rows_per_block = rows_per_block;
+    c->items_per_thread = items_per_thread;
+    c->threads_per_row = 0;
+    c->nontemporal &= ~kPolStrided; // (the request shape is the kernel's own)
+    if (keep_policy) return;
+    // every line of its streams is requested exactly once: beyond the Infinity Cache the streaming hint is right whatever
+    // the table's csr_stream entry of this bucket says (its 16-byte-vector shapes measured the other way) -- the top twelve of
+    // 96 swept shapes on the headline matrix all carry it, a tridiagonal matrix of 10^7 rows 91.8 -> 83 us
+    // (archive/profiles/r02_wave_shape_sweep.txt, r02_wave_ab.txt); below it, plain loads keep the matrix resident (tuning.hip)
+    if (nnz * bytes_per_entry > kInfinityCacheBytes + kInfinityCacheBytes / 4) c->nontemporal |= kPolLoadNT;
+    c->nontemporal |= kPolStoreNT;
+}
+
 // csr_waver (CMI_CSR_STREAM_WAVER): wave tiles on the run-compressed column copy.  Asked for: built whenever the tile can hold the longest
 // row.  AUTO plans made with the columns ($CMI_CSR_WAVER=0: never, =1: whenever the rows qualify): at least 4096 rows of 8+ entries on
 // average, no row of 512+, and the tuning table's "waver_rule" (tools/autotune_waver.py; tuning.hip has the built-in copy): at least
@@ -299,17 +319,9 @@ static bool waver_try(cmi_plan *p, const int *Ap, const int *Aj, bool asked, int
     double mean_piece = 0.0;
     *st = csr_runs_build(p, Ap, Aj, v, asked ? 0.0 : rule.min_piece, values, s, &mean_piece, asked && asked_cap ? asked_cap : rule.cap);
     if (*st != CMI_SUCCESS || !p->runs_start) return false;
-    p->cfg.kernel = values ? CMI_CSR_STREAM_PACKED : CMI_CSR_STREAM_WAVER;
-    p->cfg.block_size = 256;
-    p->cfg.rows_per_block = 0;
-    p->cfg.items_per_thread = v;
-    p->cfg.threads_per_row = 0;
-    p->cfg.nontemporal &= ~kPolStrided;
+    // (the residency rule counts the 12 / 8 bytes per entry of the caller's streams; a caller's policy bits are kept as given)
+    adopt_wave_shape(&p->cfg, nnz, values ? CMI_CSR_STREAM_PACKED : CMI_CSR_STREAM_WAVER, 0, v, p->dtype == CMI_F64 ? 12 : 8, keep_policy);
     p->cfg.xcd_swizzle = rule.xcd_swizzle; // (16: chunks of 16 workgroups = 64 wave tiles per XCD: 0.99 of launch order's time on both configs[3] matrices, twice, profiles/r04_waver_xcd_dealing.txt)
-    if (!keep_policy) { // (a caller's policy bits are kept as given)
-        if (nnz * (int64_t)(p->dtype == CMI_F64 ? 12 : 8) > kInfinityCacheBytes + kInfinityCacheBytes / 4) p->cfg.nontemporal |= kPolLoadNT;
-        p->cfg.nontemporal |= kPolStoreNT;
-    }
     return true;
 }
 
@@ -320,12 +332,8 @@ static bool packed16_try(cmi_plan *p, const int *Ap, const int *Aj, const void *
     *st = csr16_build(p, Ap, Aj, s, (int)p->prof.max_len); // granted only if every tile of 64 rows spans fewer than 65536 columns
     if (*st == CMI_SUCCESS && p->cfg.kernel == CMI_CSR_STREAM_C16 && p->csr16_wave_k > 0) *st = csr16_pack(p, Ap, values, s);
     if (*st != CMI_SUCCESS || !p->csr16_packed) { if (*st == CMI_SUCCESS) p->cfg = before; return false; }
-    p->cfg.nontemporal &= ~kPolStrided;
-    if (!keep_policy) {
-        const int64_t vb = p->dtype == CMI_F64 ? 8 : 4;
-        if (p->nnz * (2 + vb) > kInfinityCacheBytes + kInfinityCacheBytes / 4) p->cfg.nontemporal |= kPolLoadNT;
-        p->cfg.nontemporal |= kPolStoreNT;
-    }
+    // (the shape csr16_build / csr16_pack gave the tiles: 64 rows per wave, the longest row per lane; 2 bytes of column + the value per entry)
+    adopt_wave_shape(&p->cfg, p->nnz, CMI_CSR_STREAM_PACKED, kWave, p->csr16_wave_k, 2 + (p->dtype == CMI_F64 ? 8 : 4), keep_policy);
     return true;
 }
 
@@ -402,6 +410,316 @@ CMI_API int cmi_plan_device_bytes(const cmi_plan *plan, int64_t *bytes)
     return CMI_SUCCESS;
 }
 
+// the config is the table's csr_stream entry (or a caller's AUTO-kernel shape of it) with one lane per row: what the plan-built kernels replace
+static bool table_stream(const cmi_config &c) { return c.kernel == CMI_CSR_STREAM && c.threads_per_row <= 1; }
+
+// a plan with its header filled in and nothing measured yet (null: out of host memory)
+static cmi_plan *plan_new(int format, int dtype, int64_t rows, int64_t cols, int64_t nnz)
+{
+    cmi_plan *p = new (std::nothrow) cmi_plan;
+    if (!p) return nullptr;
+    p->format = format;
+    p->dtype = dtype;
+    p->rows = rows;
+    p->cols = cols;
+    p->nnz = nnz;
+    p->coo_sorted = -1; // (prof: "not measured" by its own initialisers)
+    return p;
+}
+
+// What the caller asked a CSR plan for by naming a plan-only kernel: the kernel, its own use of the launch-shape fields, and the rest of
+// the caller's config stripped to a table look-up (`lookup`: cache policy and XCD dealing if set, everything else the table's).
+struct csr_ask {
+    int kernel = CMI_KERNEL_AUTO; // CMI_CSR_STREAM_WAVE (rows_per_block < 0), _WAVEV, _WAVEX, _WAVER, _PACKED; AUTO: none of them
+    int v = 0;           // WAVE: entries per lane; the others: index vectors per lane (0 = the rule's)
+    int cap = 0;         // WAVER / PACKED: entries per piece at most (0 = the rule, 3 or 4)
+    int window = 0;      // WAVEX: length of the x window (0 = the default)
+    bool cols16 = false; // WAVEV with nontemporal bit 8 and the columns at hand: the plan-owned 16-bit column copy
+    cmi_config lookup = {}; // ... whose nontemporal is the caller's cache policy (kept as given when any bit is set) and whose xcd_swizzle the
+                         // caller's XCD dealing (kept as given when not 0; < 0: launch order)
+    bool partition() const { return kernel == CMI_CSR_STREAM_WAVE; }
+    bool wavev() const { return kernel == CMI_CSR_STREAM_WAVEV || kernel == CMI_CSR_STREAM_WAVEX; }
+    bool waver() const { return kernel == CMI_CSR_STREAM_WAVER || kernel == CMI_CSR_STREAM_PACKED; }
+    bool packed() const { return kernel == CMI_CSR_STREAM_PACKED; }
+};
+// the caller's config stripped to a table look-up: select_config takes the block size (none here) and the policy bits from an AUTO-kernel config
+static cmi_config table_lookup_of(const cmi_config &cfg)
+{
+    cmi_config c = cfg;
+    c.kernel = CMI_KERNEL_AUTO;
+    c.block_size = c.threads_per_row = c.rows_per_block = c.items_per_thread = 0;
+    return c;
+}
+// fills `a` from a config that names a plan-only kernel and returns the config to look the table up with (cfg itself otherwise):
+//   CMI_CSR_STREAM_WAVE with rows_per_block < 0: wave tiles on a partition the plan builds (irregular short rows); launch policy from
+//       the table, entries per lane from the caller (items_per_thread) or the rule
+//   CMI_CSR_STREAM_WAVEV: wave-private tiles with the 16-byte-vector body on a partition the plan builds (rows of ~16-250 entries);
+//       cache policy / XCD dealing from the caller's fields if set, else the table's; index vectors per lane from the caller or the rule.
+//       nontemporal bit 8 (kPolCols16) asks for the plan-owned 16-bit column copy (spmv_csr.hip wavev_cols16_build); it needs the columns
+//       (cmi_plan_create_csr).  The bit is not a cache policy: it is taken off here and put back into the plan's config only when the
+//       copy was granted.
+//   CMI_CSR_STREAM_WAVEX: the same partition; the multiply adds an x window in LDS (rows_per_block = its length)
+//   CMI_CSR_STREAM_WAVER / _PACKED: wave tiles on the run-compressed column copy (spmv_csr_runs.hip); policy / dealing as for WAVEV
+static const cmi_config *csr_ask_from(const cmi_config *cfg, bool have_columns, csr_ask *a)
+{
+    csr_ask named;
+    named.kernel = cfg ? cfg->kernel : CMI_KERNEL_AUTO;
+    if (!(named.partition() && cfg->rows_per_block < 0) && !named.wavev() && !named.waver()) return cfg;
+    a->kernel = cfg->kernel;
+    a->v = cfg->items_per_thread;
+    if (a->kernel == CMI_CSR_STREAM_WAVEX) {
+        a->window = cfg->rows_per_block > 0 ? cfg->rows_per_block : 0;
+        if (a->v == 0) a->v = 4;
+        if (a->v == 1) a->v = 2;
+    }
+    if (a->waver()) a->cap = cfg->threads_per_row; // (this kernel's use of the field: entries per piece at most, 0 = the rule, 3 or 4)
+    a->cols16 = a->kernel == CMI_CSR_STREAM_WAVEV && (cfg->nontemporal & kPolCols16) && have_columns;
+    a->lookup = table_lookup_of(*cfg);
+    if (a->wavev()) a->lookup.nontemporal &= ~kPolCols16;
+    return &a->lookup;
+}
+
+// the column profile of a plan made with the columns, measured when the first rule asks for it and at most once per plan (a full device
+// pass over the columns)
+static int column_profile_of(const cmi_plan *p, const int *Ap, const int *Aj, hipStream_t s, column_profile *cp)
+{
+    if (cp->measured || !Aj) return CMI_SUCCESS;
+    int64_t inside = 0;
+    if (int st = measure_column_locality(p->rows, p->cols, Ap, Aj, 1536, s, &inside, &cp->jump_count)) return st;
+    cp->inside = (double)inside / (double)p->nnz;
+    cp->jumps = (double)cp->jump_count / (double)p->nnz;
+    cp->measured = true;
+    return CMI_SUCCESS;
+}
+
+// stencil rows of 5..8 entries beyond the Infinity Cache: wave tiles of 256 (f64) / 512 (f32) entries on a plan-built partition
+// (8 bytes per tile), entries fetched as 16-byte vectors (csr_wavev, V = 1 / 2) -- see stencil_vector_tiles above
+static int route_stencil_vector_tiles(cmi_plan *p, const int *Ap, const int *Aj, int sv, hipStream_t s)
+{
+    int st = wave_partition_build(p, Ap, sv, s, 256 * sv - (int)p->prof.max_len - 3);
+    if (st != CMI_SUCCESS || !p->wave_row_start) return st;
+    // (beyond the cache by the rule: every line of the streams is requested once -- stencil_vector_tiles' gate is the helper's residency
+    //  bound, so nt loads and nt stores are set whatever the table's entry says)
+    adopt_wave_shape(&p->cfg, p->nnz, CMI_CSR_STREAM_WAVEV, 0, sv, sizeof(int) + (p->dtype == CMI_F64 ? 8 : 4), false);
+    // ... and a plan made with the columns reads them from its own 16-bit copy (2 of the 12 / 8 bytes per entry leave the stream; see
+    // stencil_cols16 above for what was measured).  Only this branch: the other AUTO routes into csr_wavev below keep the 32-bit
+    // columns until a regret run over their matrices says otherwise.
+    if (Aj && stencil_cols16(p->dtype)) st = wavev_cols16_build(p, Aj, s);
+    return st;
+}
+
+// what an AUTO plan's csr_wavev route runs: index vectors per lane, with the x window (and its length) or without, or csr_stream after all
+struct wavev_choice { int v; bool wavex = false, keep_stream = false; int window = 0; };
+// an AUTO plan: refine by the value type and -- made with the columns -- by where the columns lie
+static void wavev_refine(const cmi_plan *p, const column_profile &cp, bool small_only, bool short_rule, bool band_rule, wavev_choice *c)
+{
+    const double mean = (double)p->nnz / (double)p->rows;
+    const char *wx = std::getenv("CMI_CSR_WAVEX");
+    if (small_only) {
+        if (band_rule && cp.jumps >= 0.6 && cp.inside >= 0.25) c->v = p->dtype == CMI_F64 ? 2 : 4; // (plain tiles: no window inside the cache)
+        else if (!(short_rule && cp.jumps >= 0.0 && cp.jumps < 0.5)) c->keep_stream = true;
+    } else if (cp.jumps >= 0.6 && cp.inside >= 0.25 && !(wx && wx[0] == '0')) {
+        c->wavex = true;
+        c->window = (p->dtype == CMI_F32 && mean >= 15.0) ? 4096 : 2048;
+    } else if (cp.inside >= 0.0 && cp.inside < 0.05 && cp.jumps >= 0.6) {
+        c->keep_stream = true; // columns scattered over the whole vector: 0.08-0.11 of peak whatever runs; wave tiles 0.97-1.06x
+    } else if (p->dtype == CMI_F32 && mean >= 16.0 && cp.jumps < 0.5) {
+        c->keep_stream = true; // f32 stencil / FEM-block rows of 16+ entries (or unknown columns): the table's csr_stream is 5-6 % faster
+    } else if (mean < 12.0 && cp.jumps >= 0.0 && cp.jumps < (p->dtype == CMI_F64 ? 0.6 : 0.5)) {
+        // (f64 up to 0.6 since session 38: a 7-point stencil with 12 % of its entries removed -- rows of 1..7, 57 % jumps -- 118.3 us
+        //  with V = 1 against 127.0 with V = 4; in f32 V = 4 stays ahead there, 88.5 against 90.2 / 92.5)
+        // short rows whose columns share x lines: smaller tiles.  f64 rows of fewer than 8 entries, none longer than 16: V = 1
+        // (thermal2-like 20.4 / 63.4 us against 21.5 / 67.3 with V = 2); otherwise V = 2 -- against V = 4 (what every AUTO plan
+        // ran until the regret run of round 4, profiles/r04_auto_regret.txt): uniform 1..16 per row 74.9 against 78.3 us (f64) and
+        // 54.2 against 55.5 (f32), 4 / 40 per row 71.5 against 77.5 (V = 1: 78.6) and 44.9 against 46.3, thermal2-like x3 in f32
+        // 38.5 against 40.0.  Columns anywhere in a band (jumps >= 0.6) without the x window keep V = 4 (217.5 against 234.0).
+        // Either way only while the longest row still takes at most half of the smaller tile: with Q = 256 v - longest - 3
+        // entries per tile a few rows of 126-252 entries would leave Q = 127..1, i.e. up to one wave tile (8 bytes of plan
+        // memory, one wave) per handful of entries.  Widen back until the bound wavev_vectors() checked holds.
+        c->v = (p->dtype == CMI_F64 && mean < 8.0 && p->prof.max_len <= 16) ? 1 : 2;
+        while (c->v < 4 && 2 * (p->prof.max_len + 3) > 256 * c->v) c->v *= 2;
+    }
+}
+// csr_wavev / csr_wavex on a plan-built partition, asked for or by the AUTO rules (wavev_vectors, short_f64_rows, band_candidate);
+// `v` = wavev_vectors' answer, `cols_known` = an AUTO plan made with the columns
+static int route_wavev(cmi_plan *p, const int *Ap, const int *Aj, const csr_ask &ask, int v, bool cols_known, column_profile *cp, hipStream_t s)
+{
+    // v == 0 here: only the rules of round 4 for CACHE-RESIDENT matrices admitted this one -- f64 rows of fewer than 8 entries whose
+    // columns share x lines run wave tiles with V = 1, gather-bound band matrices V = 2 (f64) / 4 (f32); else nothing changes
+    const bool small_only = v == 0;
+    const bool short_rule = small_only && short_f64_rows(p->rows, p->nnz, p->prof, p->dtype, cols_known);
+    const bool band_rule = small_only && band_candidate(p->rows, p->nnz, p->prof, p->dtype, cols_known);
+    wavev_choice c{small_only ? 1 : v};
+    if (ask.wavev()) {
+        c.wavex = ask.kernel == CMI_CSR_STREAM_WAVEX;
+        c.window = ask.window;
+    } else {
+        if (int st = column_profile_of(p, Ap, Aj, s, cp)) return st;
+        wavev_refine(p, *cp, small_only, short_rule, band_rule, &c);
+    }
+    if (c.keep_stream) return CMI_SUCCESS; // (the table's csr_stream entry stays: nothing is built)
+    int st = wave_partition_build(p, Ap, c.v, s, 256 * c.v - (int)p->prof.max_len - 3);
+    if (st != CMI_SUCCESS || !p->wave_row_start) return st;
+    // (rows_per_block: the partition's; WAVEX: the window length, 0 = the default.  A caller's policy bits are kept as given)
+    adopt_wave_shape(&p->cfg, p->nnz, c.wavex ? CMI_CSR_STREAM_WAVEX : CMI_CSR_STREAM_WAVEV, c.wavex ? c.window : 0, c.v, sizeof(int) + (p->dtype == CMI_F64 ? 8 : 4),
+                     ask.wavev() && ask.lookup.nontemporal);
+    // ... and so is a caller's XCD dealing (< 0: launch order) -- select_config takes only block size and policy from an AUTO-kernel
+    // config, so until session 29 of round 4 an asked-for dealing was silently the table's (the "sweeps" of it measured nothing)
+    if (ask.wavev() && ask.lookup.xcd_swizzle != 0) p->cfg.xcd_swizzle = ask.lookup.xcd_swizzle < 0 ? 0 : ask.lookup.xcd_swizzle;
+    if (ask.cols16 && p->cfg.kernel == CMI_CSR_STREAM_WAVEV) st = wavev_cols16_build(p, Aj, s); // (asked for; not granted: the bit stays clear)
+    return st;
+}
+
+// csr_wave on a plan-built partition: asked for, or ($CMI_CSR_WAVE=2) for every AUTO plan whose rows qualify -- see wave_partition_k
+static int route_wave_partition(cmi_plan *p, const int *Ap, const csr_ask &ask, hipStream_t s)
+{
+    const int k = wave_partition_k(p->rows, p->nnz, p->prof, ask.partition(), ask.v);
+    if (ask.partition() && k == 0)
+        return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_create: wave tiles on a row partition need 2..10 entries per lane and the longest row <= 6.4 x that");
+    if (k == 0) return CMI_SUCCESS;
+    const int st = wave_partition_build(p, Ap, k, s);
+    if (st != CMI_SUCCESS || !p->wave_row_start) return st;
+    // (rows_per_block: the partition's, about Q / mean rows per wave.  A caller's policy bits are kept as given)
+    adopt_wave_shape(&p->cfg, p->nnz, CMI_CSR_STREAM_WAVE, 0, k, sizeof(int) + (p->dtype == CMI_F64 ? 8 : 4), ask.partition() && ask.lookup.nontemporal);
+    return CMI_SUCCESS;
+}
+
+// Which kernel a CSR plan runs instead of the table's csr_stream entry: the routes below are tried in this order and the first whose guard
+// passes claims the matrix -- even when it then builds nothing (csr_stream kept, a partition not built).  A builder's error ends plan creation.
+// DESIGN.md 3.1 has the order as a table.
+static int plan_csr_routes(cmi_plan *p, const int *Ap, const int *Aj, const void *values, const csr_ask &ask, bool auto_kernel, hipStream_t s)
+{
+    const size_t vbytes = p->dtype == CMI_F64 ? 8 : 4;
+    // open: no kernel named by the caller (or one of csr_ask's, stripped), and the table -- after the balanced override and the default
+    // 16-bit copy -- says csr_stream with one lane per row
+    const bool open = auto_kernel && table_stream(p->cfg);
+    const bool fits = wave_tiles_fit(p->rows, p->nnz, p->prof.max_len);
+    const bool asked_nothing = ask.kernel == CMI_KERNEL_AUTO;
+    column_profile cp;
+    int st = CMI_SUCCESS;
+    // Rows that all have (nearly) the same short length -- stencils -- take csr_stream's lane-strided body with wave-private
+    // tiles (spmv_csr.hip csr_wave_kernel): 64 rows per wave, as many entries per lane as the longest row has, so every
+    // tile fits and (mean within 7 % of the longest row) at least 93 % of the request lanes carry an entry.  Cache policy and
+    // XCD dealing are the table's csr_stream entry's.  Not for a caller's explicit kernel, not over a granted 16-bit copy.
+    // Equal short rows are a stencil's signature -- but only its columns make it one.  A plan made WITH the columns looks: where 75 %+ of
+    // the entries sit 16+ columns from their predecessor in the row (a 5-point stencil: 40 %, 7-point: 57 %, 9-point: 33 %; columns drawn
+    // anywhere inside a band: 97 %) the matrix is gather-bound and none of the stencil kernels below is right for it -- 6 / 9 entries per
+    // row exactly, columns anywhere in +-2000: csr_wave / V = 1 tiles 161-167 us (f64), 94-95 (f32), where the general rule further down
+    // (wave tiles V = 4, with the x window) gets 120-138 and 70-85 (profiles/r04_auto_regret_equal_lengths.txt).  Without the columns
+    // the lengths decide, as before.
+    bool gather_bound = false;
+    if (open && fits && asked_nothing && Aj) {
+        if ((st = column_profile_of(p, Ap, Aj, s, &cp))) return st;
+        gather_bound = (double)cp.jump_count >= 0.75 * (double)p->nnz;
+    }
+    if (open && fits && asked_nothing && !gather_bound) {
+        // stencil rows of 8+ entries whose columns come in runs (9-point: three runs of 3) and a plan made with the columns: the
+        // run-compressed copy, tried BEFORE csr_wave (waver_try's own gates: the table's rule; pieces shorter than it asks -> nothing
+        // is kept and csr_wave below runs).  9-point 3000^2: 143.9 us against csr_wave's 187.1 (f64), 89.8 against 134.0 (f32),
+        // profiles/r04_auto_regret.txt -- until then every stencil-like matrix took csr_wave unseen.
+        if (Aj && waver_try(p, Ap, Aj, false, 0, 0, false, nullptr, s, &st)) return CMI_SUCCESS;
+        if (st != CMI_SUCCESS) return st;
+        if (const int sv = stencil_vector_tiles(p->nnz, p->prof, p->dtype, vbytes)) return route_stencil_vector_tiles(p, Ap, Aj, sv, s);
+    }
+    if (open && fits && !gather_bound && !ask.wavev() && !ask.waver()) { // (csr_wave's fixed tiles; a caller who asked for a partition lands here too)
+        adopt_wave_shape(&p->cfg, p->nnz, CMI_CSR_STREAM_WAVE, 256, (int)p->prof.max_len, sizeof(int) + vbytes, false);
+        return CMI_SUCCESS;
+    }
+    if (open && fits && ask.packed() && values && Aj) {
+        // (stencil-like rows: packed wave tiles of the 16-bit copy, spmv_csr16.hip; p->cfg is set)
+        if (packed16_try(p, Ap, Aj, values, ask.lookup.nontemporal != 0, s, &st)) return CMI_SUCCESS;
+        if (st != CMI_SUCCESS) return st;
+    }
+    if (open && !ask.partition() && !ask.wavev() && Aj) {
+        if (waver_try(p, Ap, Aj, ask.waver(), ask.v, ask.cap, ask.waver() && ask.lookup.nontemporal != 0, ask.packed() ? values : nullptr, s, &st)) {
+            // (the run-compressed copy was built and pays: p->cfg is set; a caller's XCD dealing is kept as given)
+            if (ask.waver() && ask.lookup.xcd_swizzle != 0) p->cfg.xcd_swizzle = ask.lookup.xcd_swizzle < 0 ? 0 : ask.lookup.xcd_swizzle;
+            return CMI_SUCCESS;
+        }
+        if (st != CMI_SUCCESS) return st;
+    }
+    if (ask.waver())
+        return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_create: CMI_CSR_STREAM_WAVER / _PACKED need f64 values, 2 <= columns < 2^30, items_per_thread 0, 1, 2 or 4, no row of 512+ entries and the longest row at most half of the 256 x items_per_thread slots of a wave tile");
+    if (open && !ask.partition()) { // (a caller who asked for csr_wave on a partition gets that)
+        const bool cols_known = Aj != nullptr && !ask.wavev();
+        const int v = wavev_vectors(p->rows, p->nnz, p->prof, ask.wavev(), ask.v, vbytes);
+        if (v > 0 || short_f64_rows(p->rows, p->nnz, p->prof, p->dtype, cols_known) || band_candidate(p->rows, p->nnz, p->prof, p->dtype, cols_known))
+            return route_wavev(p, Ap, Aj, ask, v, cols_known, &cp, s);
+    }
+    if (ask.wavev())
+        return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_create: CMI_CSR_STREAM_WAVEV needs items_per_thread 0, 1, 2 or 4, no row of 512+ entries and the longest row at most half of the 256 x items_per_thread slots of a wave tile");
+    return open ? route_wave_partition(p, Ap, ask, s) : CMI_SUCCESS;
+}
+
+// A CSR plan's measurements and choices: the row-length profile, the balanced override, the default 16-bit copy, then the routes
+static int plan_csr(cmi_plan *p, const int *Ap, const int *Aj, const void *values, const csr_ask &ask, bool auto_kernel, bool want16, bool table_shape, hipStream_t s)
+{
+    const int64_t num_rows = p->rows, num_entries = p->nnz;
+    int64_t ends[2] = {0, num_entries};
+    if (int st = measure_row_lengths(num_rows, Ap, s, &p->prof.max_len, &p->prof.in_long, ends)) return st;
+    // the kernels and the plan-owned arrays (wave partition, 16-bit copy) are sized from num_entries: row offsets that do not span
+    // exactly [0, num_entries] are refused here, once, instead of being trusted by every multiply
+    if (ends[0] != 0 || ends[1] != num_entries) {
+        set_error("cmi_plan_create: row offsets run from %lld to %lld, expected 0 to num_entries = %lld", (long long)ends[0], (long long)ends[1], (long long)num_entries);
+        return CMI_ERROR_INVALID_VALUE;
+    }
+    if (auto_kernel && prefers_balanced(num_rows, num_entries, p->prof, p->dtype == CMI_F64 ? 8 : 4, p->cfg.threads_per_row == 1)) {
+        p->cfg.kernel = CMI_CSR_BALANCED;
+        p->cfg.items_per_thread = 0; // the table's row-tile launch shape does not apply: balanced defaults
+        p->cfg.blocks_per_cu = 0;
+        p->cfg.xcd_swizzle = 0;      // (chunks in launch order: a skewed matrix has no x window worth dealing for)
+    }
+    if (want16 && table_stream(p->cfg)) {
+        // the tiling is frozen into the copy, so the fused-dot instance cannot re-tile as spmv_csr.hip does for it: a
+        // table-chosen shape takes whole waves of rows per tile here, for every multiply, when one LDS pass holds them
+        const int tuned_rpb = p->cfg.rows_per_block;
+        if (table_shape) {
+            const int rpb = p->cfg.rows_per_block, up = (rpb + kWave - 1) / kWave * kWave;
+            const double mean = (double)num_entries / (double)num_rows;
+            if (up != rpb && up <= p->cfg.block_size && (double)up * mean + 3.0 <= (double)p->cfg.block_size * p->cfg.items_per_thread * 4) p->cfg.rows_per_block = up;
+        }
+        // (stencil-like rows and the table's shape: the copy is tiled for the wave-tile kernel instead -- 64 rows per tile)
+        const int wave_k = table_shape && wave_tiles_fit(num_rows, num_entries, p->prof.max_len) ? (int)p->prof.max_len : 0;
+        const int st = csr16_build(p, Ap, Aj, s, wave_k); // all tiles qualify -> cfg.kernel = CMI_CSR_STREAM_C16, else unchanged
+        if (p->cfg.kernel != CMI_CSR_STREAM_C16) p->cfg.rows_per_block = tuned_rpb; // not granted: csr_stream as tuned
+        if (st != CMI_SUCCESS) return st;
+    }
+    return plan_csr_routes(p, Ap, Aj, values, ask, auto_kernel, s);
+}
+
+// A COO plan: are the entries sorted by row?  Then the tile kernel's table entry and -- no kernel asked for -- row offsets and a CSR sub-plan
+static int plan_coo(cmi_plan *p, const int *Ai, const int *Aj, const cmi_config *cfg, void *stream)
+{
+    const int64_t num_rows = p->rows, num_cols = p->cols, num_entries = p->nnz;
+    int sorted = 1, long_runs = 0;
+    if (num_entries > 0)
+        if (int st = coo_rows_sorted(num_rows, num_entries, Ai, as_stream(stream), &sorted, &long_runs)) return st;
+    p->coo_sorted = sorted;
+    const bool auto_kernel = !cfg || cfg->kernel == CMI_KERNEL_AUTO;
+    // sorted entries: the table's CMI_TABLE_COO_SORTED key (the tile kernel with its tuned cache policy / XCD dealing)
+    // (fewer than four entries: the tile kernel's vector loads have nothing to read -- the order-agnostic kernel stays)
+    // (a row of more than 1024 entries: the tile kernel would walk its tail serially -- the order-agnostic kernel stays)
+    if (sorted && !long_runs && auto_kernel && num_entries >= 4) select_config(CMI_TABLE_COO_SORTED, p->dtype, num_rows, num_cols, num_entries, cfg, &p->cfg);
+    // Sorted entries and no kernel asked for: the row indices carry no more than row offsets do.  The plan builds the
+    // offsets once (4 bytes per row of HBM it owns) and a CSR plan for them; every multiply then streams 12 bytes per
+    // entry instead of 16 through the CSR kernels -- same products, storage-order sums, rows of any length.
+    // ($CMI_COO_PLAN_OFFSETS=0: keep the COO kernels -- measurements of the tile kernel.)
+    const char *off = std::getenv("CMI_COO_PLAN_OFFSETS");
+    int st = CMI_SUCCESS;
+    if (sorted && auto_kernel && num_entries >= 4 && num_rows > 0 && num_entries <= INT32_MAX - 65536 && !(off && off[0] == '0')) {
+        hipError_t e = hipMalloc((void **)&p->coo_offsets, (size_t)(num_rows + 1) * sizeof(int32_t));
+        if (e != hipSuccess) st = hip_fail(e, "cmi_plan_create: COO row offsets");
+        int sorted2 = 0;
+        if (st == CMI_SUCCESS) st = cmi_coo_row_offsets(num_rows, num_entries, Ai, p->coo_offsets, &sorted2, stream);
+        if (st == CMI_SUCCESS && sorted2)
+            st = plan_create(CMI_FORMAT_CSR, p->dtype, num_rows, num_cols, num_entries, p->coo_offsets, Aj /* cmi_plan_create_coo: the CSR plan may then hold the run-compressed copy */, nullptr, stream, &p->coo_csr_plan);
+        if (st == CMI_SUCCESS && p->coo_csr_plan) p->cfg = p->coo_csr_plan->cfg; // what cmi_plan_config reports: the kernel that runs
+    }
+    // an explicit CMI_COO_TILE on unsorted entries would add rows up wrongly: refuse it here, where it is known
+    if (st == CMI_SUCCESS && !sorted && p->cfg.kernel == CMI_COO_TILE) st = fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_create: CMI_COO_TILE needs row-sorted entries");
+    return st;
+}
+
 static int plan_create(int format, int dtype, int64_t num_rows, int64_t num_cols, int64_t num_entries,
                        const int32_t *index_array, const int32_t *csr_columns, const cmi_config *cfg, void *stream, cmi_plan **plan_out, const void *csr_values)
 {
@@ -418,15 +736,8 @@ static int plan_create(int format, int dtype, int64_t num_rows, int64_t num_cols
     const bool indexed = format == CMI_FORMAT_CSR || format == CMI_FORMAT_COO;
     if (indexed && !index_array && (format == CMI_FORMAT_CSR ? num_rows > 0 : num_entries > 0))
         return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_create: CSR / COO plans need the row offsets / row indices");
-    cmi_plan *p = new (std::nothrow) cmi_plan;
+    cmi_plan *p = plan_new(format, dtype, num_rows, num_cols, num_entries);
     if (!p) return fail(CMI_ERROR_ALLOC, "cmi_plan_create: out of host memory");
-    p->format = format;
-    p->dtype = dtype;
-    p->rows = num_rows;
-    p->cols = num_cols;
-    p->nnz = num_entries;
-    p->prof = row_profile{};
-    p->coo_sorted = -1;
     p->cfg_explicit = cfg && cfg->kernel != CMI_KERNEL_AUTO && !(cfg->kernel == CMI_CSR_STREAM_C16 && !(cfg->block_size || cfg->rows_per_block || cfg->items_per_thread));
     // CMI_CSR_STREAM_C16 is csr_stream's shape (the caller's launch-shape fields if any, else the table's) + the 16-bit copy
     cmi_config shape;
@@ -441,282 +752,20 @@ static int plan_create(int format, int dtype, int64_t num_rows, int64_t num_cols
         } else if (table_shape && compress_default())
             want16 = true;
     }
-    // CMI_CSR_STREAM_WAVE with rows_per_block < 0: wave tiles on a partition the plan builds (irregular short rows); launch policy from
-    // the table, entries per lane from the caller (items_per_thread) or the rule
-    cmi_config part_shape;
-    bool want_partition = false;
-    int partition_k = 0;
-    if (format == CMI_FORMAT_CSR && cfg && cfg->kernel == CMI_CSR_STREAM_WAVE && cfg->rows_per_block < 0) {
-        want_partition = true;
-        partition_k = cfg->items_per_thread;
-        part_shape = *cfg;
-        part_shape.kernel = CMI_KERNEL_AUTO;
-        part_shape.rows_per_block = 0;
-        part_shape.items_per_thread = 0;
-        part_shape.block_size = 0;
-        cfg = &part_shape;
-        p->cfg_explicit = false;
-    }
-    // CMI_CSR_STREAM_WAVEV: wave-private tiles with the 16-byte-vector body on a partition the plan builds (rows of ~16-250 entries);
-    // cache policy / XCD dealing from the caller's fields if set, else the table's; index vectors per lane from the caller or the rule
-    cmi_config wavev_shape;
-    bool want_wavev = false, want_wavex = false;
-    int wavev_v = 0, wavex_window = 0;
-    // nontemporal bit 8 (kPolCols16) on a CMI_CSR_STREAM_WAVEV config asks for the plan-owned 16-bit column copy (spmv_csr.hip
-    // wavev_cols16_build); it needs the columns (cmi_plan_create_csr).  The bit is not a cache policy: it is taken off here and put back
-    // into the plan's config only when the copy was granted.
-    const bool want_cols16 = format == CMI_FORMAT_CSR && cfg && cfg->kernel == CMI_CSR_STREAM_WAVEV && (cfg->nontemporal & kPolCols16) && csr_columns;
-    if (format == CMI_FORMAT_CSR && cfg && (cfg->kernel == CMI_CSR_STREAM_WAVEV || cfg->kernel == CMI_CSR_STREAM_WAVEX)) {
-        want_wavev = true;
-        want_wavex = cfg->kernel == CMI_CSR_STREAM_WAVEX; // the same partition; the multiply adds an x window in LDS (rows_per_block = its length)
-        wavex_window = cfg->rows_per_block > 0 ? cfg->rows_per_block : 0;
-        wavev_v = cfg->items_per_thread;
-        if (want_wavex && wavev_v == 0) wavev_v = 4;
-        if (want_wavex && wavev_v == 1) wavev_v = 2;
-        wavev_shape = *cfg;
-        wavev_shape.kernel = CMI_KERNEL_AUTO;
-        wavev_shape.rows_per_block = 0;
-        wavev_shape.items_per_thread = 0;
-        wavev_shape.block_size = 0;
-        wavev_shape.threads_per_row = 0;
-        wavev_shape.nontemporal &= ~kPolCols16;
-        cfg = &wavev_shape;
-        p->cfg_explicit = false;
-    }
-    // CMI_CSR_STREAM_WAVER / _PACKED: wave tiles on the run-compressed column copy (spmv_csr_runs.hip); policy / dealing as for WAVEV
-    cmi_config waver_shape;
-    bool want_waver = false, want_packed = false;
-    int waver_v = 0, waver_cap = 0;
-    if (format == CMI_FORMAT_CSR && cfg && (cfg->kernel == CMI_CSR_STREAM_WAVER || cfg->kernel == CMI_CSR_STREAM_PACKED)) {
-        if (!csr_columns && num_entries > 0) { delete p; return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_create: CMI_CSR_STREAM_WAVER needs the column indices -- use cmi_plan_create_csr"); }
-        want_waver = true;
-        want_packed = cfg->kernel == CMI_CSR_STREAM_PACKED;
-        waver_v = cfg->items_per_thread;
-        waver_cap = cfg->threads_per_row; // (this kernel's use of the field: entries per piece at most, 0 = the rule, 3 or 4)
-        waver_shape = *cfg;
-        waver_shape.kernel = CMI_KERNEL_AUTO;
-        waver_shape.rows_per_block = 0;
-        waver_shape.items_per_thread = 0;
-        waver_shape.block_size = 0;
-        waver_shape.threads_per_row = 0;
-        cfg = &waver_shape;
-        p->cfg_explicit = false;
-    }
-    p->kernel_asked = want_partition || want_wavev || want_waver;
+    csr_ask ask;
+    if (format == CMI_FORMAT_CSR) cfg = csr_ask_from(cfg, csr_columns != nullptr, &ask);
+    if (ask.waver() && !csr_columns && num_entries > 0) { delete p; return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_create: CMI_CSR_STREAM_WAVER needs the column indices -- use cmi_plan_create_csr"); }
+    p->kernel_asked = ask.kernel != CMI_KERNEL_AUTO;
+    if (p->kernel_asked) p->cfg_explicit = false;
     // HYB's table key is its ELL part's (the COO part looks its own shape up per call)
     select_config(format == CMI_FORMAT_HYB ? CMI_FORMAT_ELL : format, dtype, num_rows, num_cols, num_entries, cfg, &p->cfg);
     if (format == CMI_FORMAT_CSR) p->cfg.nontemporal &= ~kPolCols16; // (only a granted copy sets it, below)
     hipStream_t s = as_stream(stream);
-    const size_t vbytes = dtype == CMI_F64 ? 8 : 4;
     int st = CMI_SUCCESS;
-    if (format == CMI_FORMAT_CSR && num_rows > 0 && num_entries > 0) {
-        int64_t ends[2] = {0, num_entries};
-        st = measure_row_lengths(num_rows, index_array, s, &p->prof.max_len, &p->prof.in_long, ends);
-        // the kernels and the plan-owned arrays (wave partition, 16-bit copy) are sized from num_entries: row offsets that do not span
-        // exactly [0, num_entries] are refused here, once, instead of being trusted by every multiply
-        if (st == CMI_SUCCESS && (ends[0] != 0 || ends[1] != num_entries)) {
-            set_error("cmi_plan_create: row offsets run from %lld to %lld, expected 0 to num_entries = %lld", (long long)ends[0], (long long)ends[1], (long long)num_entries);
-            st = CMI_ERROR_INVALID_VALUE;
-        }
-        const bool auto_kernel = !cfg || cfg->kernel == CMI_KERNEL_AUTO;
-        if (st == CMI_SUCCESS && auto_kernel && prefers_balanced(num_rows, num_entries, p->prof, vbytes, p->cfg.threads_per_row == 1)) {
-            p->cfg.kernel = CMI_CSR_BALANCED;
-            p->cfg.items_per_thread = 0; // the table's row-tile launch shape does not apply: balanced defaults
-            p->cfg.blocks_per_cu = 0;
-            p->cfg.xcd_swizzle = 0;      // (chunks in launch order: a skewed matrix has no x window worth dealing for)
-        }
-        if (st == CMI_SUCCESS && want16 && p->cfg.kernel == CMI_CSR_STREAM && p->cfg.threads_per_row <= 1) {
-            // the tiling is frozen into the copy, so the fused-dot instance cannot re-tile as spmv_csr.hip does for it: a
-            // table-chosen shape takes whole waves of rows per tile here, for every multiply, when one LDS pass holds them
-            const int tuned_rpb = p->cfg.rows_per_block;
-            if (table_shape) {
-                const int rpb = p->cfg.rows_per_block, up = (rpb + kWave - 1) / kWave * kWave;
-                const double mean = (double)num_entries / (double)num_rows;
-                if (up != rpb && up <= p->cfg.block_size && (double)up * mean + 3.0 <= (double)p->cfg.block_size * p->cfg.items_per_thread * 4) p->cfg.rows_per_block = up;
-            }
-            // (stencil-like rows and the table's shape: the copy is tiled for the wave-tile kernel instead -- 64 rows per tile)
-            const int wave_k = table_shape && wave_tiles_fit(num_rows, num_entries, p->prof.max_len) ? (int)p->prof.max_len : 0;
-            st = csr16_build(p, index_array, csr_columns, s, wave_k); // all tiles qualify -> cfg.kernel = CMI_CSR_STREAM_C16, else unchanged
-            if (p->cfg.kernel != CMI_CSR_STREAM_C16) p->cfg.rows_per_block = tuned_rpb; // not granted: csr_stream as tuned
-        }
-        // Rows that all have (nearly) the same short length -- stencils -- take csr_stream's lane-strided body with wave-private
-        // tiles (spmv_csr.hip csr_wave_kernel): 64 rows per wave, as many entries per lane as the longest row has, so every
-        // tile fits and (mean within 7 % of the longest row) at least 93 % of the request lanes carry an entry.  Cache policy and
-        // XCD dealing are the table's csr_stream entry's.  Not for a caller's explicit kernel, not over a granted 16-bit copy.
-        // Equal short rows are a stencil's signature -- but only its columns make it one.  A plan made WITH the columns looks: where 75 %+ of
-        // the entries sit 16+ columns from their predecessor in the row (a 5-point stencil: 40 %, 7-point: 57 %, 9-point: 33 %; columns drawn
-        // anywhere inside a band: 97 %) the matrix is gather-bound and none of the stencil kernels below is right for it -- 6 / 9 entries per
-        // row exactly, columns anywhere in +-2000: csr_wave / V = 1 tiles 161-167 us (f64), 94-95 (f32), where the general rule further down
-        // (wave tiles V = 4, with the x window) gets 120-138 and 70-85 (profiles/r04_auto_regret_equal_lengths.txt).  Without the columns
-        // the lengths decide, as before.
-        bool gather_bound = false;
-        if (st == CMI_SUCCESS && auto_kernel && !want_partition && !want_wavev && !want_waver && csr_columns && p->cfg.kernel == CMI_CSR_STREAM && p->cfg.threads_per_row <= 1 &&
-            wave_tiles_fit(num_rows, num_entries, p->prof.max_len)) {
-            int64_t inside = 0, jumps = 0;
-            st = measure_column_locality(num_rows, num_cols, index_array, csr_columns, 1536, s, &inside, &jumps);
-            gather_bound = st == CMI_SUCCESS && (double)jumps >= 0.75 * (double)num_entries;
-        }
-        if (st == CMI_SUCCESS && !gather_bound && auto_kernel && !want_partition && !want_wavev && !want_waver && csr_columns && p->cfg.kernel == CMI_CSR_STREAM && p->cfg.threads_per_row <= 1 &&
-            wave_tiles_fit(num_rows, num_entries, p->prof.max_len) && waver_try(p, index_array, csr_columns, false, 0, 0, false, nullptr, s, &st)) {
-            // stencil rows of 8+ entries whose columns come in runs (9-point: three runs of 3) and a plan made with the columns: the
-            // run-compressed copy, tried BEFORE csr_wave (waver_try's own gates: the table's rule; pieces shorter than it asks -> nothing
-            // is kept and csr_wave below runs).  9-point 3000^2: 143.9 us against csr_wave's 187.1 (f64), 89.8 against 134.0 (f32),
-            // profiles/r04_auto_regret.txt -- until then every stencil-like matrix took csr_wave unseen.
-        } else if (st == CMI_SUCCESS && !gather_bound && auto_kernel && !want_partition && !want_wavev && !want_waver && p->cfg.kernel == CMI_CSR_STREAM && p->cfg.threads_per_row <= 1 &&
-                   wave_tiles_fit(num_rows, num_entries, p->prof.max_len) && stencil_vector_tiles(num_entries, p->prof, dtype, vbytes) > 0) {
-            // stencil rows of 5..8 entries beyond the Infinity Cache: wave tiles of 256 (f64) / 512 (f32) entries on a plan-built partition
-            // (8 bytes per tile), entries fetched as 16-byte vectors (csr_wavev, V = 1 / 2) -- see stencil_vector_tiles above
-            const int sv = stencil_vector_tiles(num_entries, p->prof, dtype, vbytes);
-            st = wave_partition_build(p, index_array, sv, s, 256 * sv - (int)p->prof.max_len - 3);
-            if (st == CMI_SUCCESS && p->wave_row_start) {
-                p->cfg.kernel = CMI_CSR_STREAM_WAVEV;
-                p->cfg.block_size = 256;
-                p->cfg.rows_per_block = 0;
-                p->cfg.items_per_thread = sv;
-                p->cfg.threads_per_row = 0;
-                p->cfg.nontemporal &= ~kPolStrided;
-                p->cfg.nontemporal |= kPolLoadNT | kPolStoreNT; // (beyond the cache by the rule: every line of the streams is requested once)
-                // ... and a plan made with the columns reads them from its own 16-bit copy (2 of the 12 / 8 bytes per entry leave the stream; see
-                // stencil_cols16 above for what was measured).  Only this branch: the other AUTO routes into csr_wavev below keep the 32-bit
-                // columns until a regret run over their matrices says otherwise.
-                if (csr_columns && stencil_cols16(dtype)) st = wavev_cols16_build(p, csr_columns, s);
-            }
-        } else if (st == CMI_SUCCESS && !gather_bound && auto_kernel && !want_wavev && !want_waver && p->cfg.kernel == CMI_CSR_STREAM && p->cfg.threads_per_row <= 1 &&
-            wave_tiles_fit(num_rows, num_entries, p->prof.max_len)) {
-            p->cfg.kernel = CMI_CSR_STREAM_WAVE;
-            p->cfg.block_size = 256;
-            p->cfg.rows_per_block = 256;
-            p->cfg.items_per_thread = (int)p->prof.max_len;
-            p->cfg.threads_per_row = 0;
-            p->cfg.nontemporal &= ~kPolStrided; // (the request shape is the kernel's own)
-            // every line of its streams is requested exactly once: beyond the Infinity Cache the streaming hint is right whatever
-            // the table's csr_stream entry of this bucket says (its 16-byte-vector shapes measured the other way) -- the top twelve of
-            // 96 swept shapes on the headline matrix all carry it, a tridiagonal matrix of 10^7 rows 91.8 -> 83 us
-            // (archive/profiles/r02_wave_shape_sweep.txt, r02_wave_ab.txt); below it, plain loads keep the matrix resident (tuning.hip)
-            if (num_entries * (int64_t)(sizeof(int) + vbytes) > kInfinityCacheBytes + kInfinityCacheBytes / 4) p->cfg.nontemporal |= kPolLoadNT;
-            p->cfg.nontemporal |= kPolStoreNT;
-        } else if (st == CMI_SUCCESS && want_packed && csr_values && csr_columns && p->cfg.kernel == CMI_CSR_STREAM && p->cfg.threads_per_row <= 1 &&
-                   wave_tiles_fit(num_rows, num_entries, p->prof.max_len) && packed16_try(p, index_array, csr_columns, csr_values, waver_shape.nontemporal != 0, s, &st)) {
-            // (stencil-like rows: packed wave tiles of the 16-bit copy, spmv_csr16.hip; p->cfg is set)
-        } else if (st == CMI_SUCCESS && auto_kernel && !want_partition && !want_wavev && csr_columns && p->cfg.kernel == CMI_CSR_STREAM && p->cfg.threads_per_row <= 1 &&
-                   waver_try(p, index_array, csr_columns, want_waver, waver_v, waver_cap, want_waver && waver_shape.nontemporal != 0, want_packed ? csr_values : nullptr, s, &st)) {
-            // (the run-compressed copy was built and pays: p->cfg is set; a caller's XCD dealing is kept as given)
-            if (want_waver && waver_shape.xcd_swizzle != 0) p->cfg.xcd_swizzle = waver_shape.xcd_swizzle < 0 ? 0 : waver_shape.xcd_swizzle;
-        } else if (st == CMI_SUCCESS && want_waver) {
-            st = fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_create: CMI_CSR_STREAM_WAVER / _PACKED need f64 values, 2 <= columns < 2^30, items_per_thread 0, 1, 2 or 4, no row of 512+ entries and the longest row at most half of the 256 x items_per_thread slots of a wave tile");
-        } else if (st == CMI_SUCCESS && auto_kernel && !want_partition && p->cfg.kernel == CMI_CSR_STREAM && p->cfg.threads_per_row <= 1 &&
-                   (wavev_vectors(num_rows, num_entries, p->prof, want_wavev, wavev_v, vbytes) > 0 ||
-                    short_f64_rows(num_rows, num_entries, p->prof, dtype, csr_columns != nullptr && !want_wavev) ||
-                    band_candidate(num_rows, num_entries, p->prof, dtype, csr_columns != nullptr && !want_wavev))) { // (a caller who asked for csr_wave on a partition gets that)
-            int v = wavev_vectors(num_rows, num_entries, p->prof, want_wavev, wavev_v, vbytes);
-            // v == 0 here: only the rules of round 4 for CACHE-RESIDENT matrices admitted this one -- f64 rows of fewer than 8 entries whose
-            // columns share x lines run wave tiles with V = 1, gather-bound band matrices V = 2 (f64) / 4 (f32); else nothing changes
-            const bool small_only = v == 0;
-            const bool short_rule = small_only && short_f64_rows(num_rows, num_entries, p->prof, dtype, csr_columns != nullptr && !want_wavev);
-            const bool band_rule = small_only && band_candidate(num_rows, num_entries, p->prof, dtype, csr_columns != nullptr && !want_wavev);
-            if (small_only) v = 1;
-            bool auto_wavex = false, keep_stream = false;
-            if (!want_wavev) { // an AUTO plan: refine by the value type and -- made with the columns -- by where the columns lie
-                const double mean = (double)num_entries / (double)num_rows;
-                column_profile cp;
-                if (csr_columns) {
-                    int64_t inside = 0, jumps = 0;
-                    st = measure_column_locality(num_rows, num_cols, index_array, csr_columns, 1536, s, &inside, &jumps);
-                    if (st == CMI_SUCCESS) { cp.inside = (double)inside / (double)num_entries; cp.jumps = (double)jumps / (double)num_entries; }
-                }
-                const char *wx = std::getenv("CMI_CSR_WAVEX");
-                if (small_only) {
-                    if (band_rule && cp.jumps >= 0.6 && cp.inside >= 0.25) v = dtype == CMI_F64 ? 2 : 4; // (plain tiles: no window inside the cache)
-                    else if (!(short_rule && cp.jumps >= 0.0 && cp.jumps < 0.5)) keep_stream = true;
-                } else if (cp.jumps >= 0.6 && cp.inside >= 0.25 && !(wx && wx[0] == '0')) {
-                    auto_wavex = true;
-                    wavex_window = (dtype == CMI_F32 && mean >= 15.0) ? 4096 : 2048;
-                } else if (cp.inside >= 0.0 && cp.inside < 0.05 && cp.jumps >= 0.6) {
-                    keep_stream = true; // columns scattered over the whole vector: 0.08-0.11 of peak whatever runs; wave tiles 0.97-1.06x
-                } else if (dtype == CMI_F32 && mean >= 16.0 && cp.jumps < 0.5) {
-                    keep_stream = true; // f32 stencil / FEM-block rows of 16+ entries (or unknown columns): the table's csr_stream is 5-6 % faster
-                } else if (mean < 12.0 && cp.jumps >= 0.0 && cp.jumps < (dtype == CMI_F64 ? 0.6 : 0.5)) {
-                    // (f64 up to 0.6 since session 38: a 7-point stencil with 12 % of its entries removed -- rows of 1..7, 57 % jumps -- 118.3 us
-                    //  with V = 1 against 127.0 with V = 4; in f32 V = 4 stays ahead there, 88.5 against 90.2 / 92.5)
-                    // short rows whose columns share x lines: smaller tiles.  f64 rows of fewer than 8 entries, none longer than 16: V = 1
-                    // (thermal2-like 20.4 / 63.4 us against 21.5 / 67.3 with V = 2); otherwise V = 2 -- against V = 4 (what every AUTO plan
-                    // ran until the regret run of round 4, profiles/r04_auto_regret.txt): uniform 1..16 per row 74.9 against 78.3 us (f64) and
-                    // 54.2 against 55.5 (f32), 4 / 40 per row 71.5 against 77.5 (V = 1: 78.6) and 44.9 against 46.3, thermal2-like x3 in f32
-                    // 38.5 against 40.0.  Columns anywhere in a band (jumps >= 0.6) without the x window keep V = 4 (217.5 against 234.0).
-                    // Either way only while the longest row still takes at most half of the smaller tile: with Q = 256 v - longest - 3
-                    // entries per tile a few rows of 126-252 entries would leave Q = 127..1, i.e. up to one wave tile (8 bytes of plan
-                    // memory, one wave) per handful of entries.  Widen back until the bound wavev_vectors() checked holds.
-                    v = (dtype == CMI_F64 && mean < 8.0 && p->prof.max_len <= 16) ? 1 : 2;
-                    while (v < 4 && 2 * (p->prof.max_len + 3) > 256 * v) v *= 2;
-                }
-            }
-            if (keep_stream) {
-                // (the table's csr_stream entry stays: nothing is built)
-            } else if (st == CMI_SUCCESS) st = wave_partition_build(p, index_array, v, s, 256 * v - (int)p->prof.max_len - 3);
-            if (st == CMI_SUCCESS && p->wave_row_start) {
-                p->cfg.kernel = (want_wavex || auto_wavex) ? CMI_CSR_STREAM_WAVEX : CMI_CSR_STREAM_WAVEV;
-                p->cfg.block_size = 256;
-                p->cfg.rows_per_block = (want_wavex || auto_wavex) ? wavex_window : 0; // (the partition's; WAVEX: the window length, 0 = the default)
-                p->cfg.items_per_thread = v;
-                p->cfg.threads_per_row = 0;
-                p->cfg.nontemporal &= ~kPolStrided;
-                if (!(want_wavev && wavev_shape.nontemporal)) { // (a caller's policy bits are kept as given)
-                    if (num_entries * (int64_t)(sizeof(int) + vbytes) > kInfinityCacheBytes + kInfinityCacheBytes / 4) p->cfg.nontemporal |= kPolLoadNT;
-                    p->cfg.nontemporal |= kPolStoreNT;
-                }
-                // ... and so is a caller's XCD dealing (< 0: launch order) -- select_config takes only block size and policy from an AUTO-kernel
-                // config, so until session 29 of round 4 an asked-for dealing was silently the table's (the "sweeps" of it measured nothing)
-                if (want_wavev && wavev_shape.xcd_swizzle != 0) p->cfg.xcd_swizzle = wavev_shape.xcd_swizzle < 0 ? 0 : wavev_shape.xcd_swizzle;
-                if (want_cols16 && p->cfg.kernel == CMI_CSR_STREAM_WAVEV) st = wavev_cols16_build(p, csr_columns, s); // (asked for; not granted: the bit stays clear)
-            }
-        } else if (st == CMI_SUCCESS && want_wavev) {
-            st = fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_create: CMI_CSR_STREAM_WAVEV needs items_per_thread 0, 1, 2 or 4, no row of 512+ entries and the longest row at most half of the 256 x items_per_thread slots of a wave tile");
-        } else if (st == CMI_SUCCESS && auto_kernel && p->cfg.kernel == CMI_CSR_STREAM && p->cfg.threads_per_row <= 1) {
-            const int k = wave_partition_k(num_rows, num_entries, p->prof, want_partition, partition_k);
-            if (want_partition && k == 0)
-                st = fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_create: wave tiles on a row partition need 2..10 entries per lane and the longest row <= 6.4 x that");
-            if (k > 0) st = wave_partition_build(p, index_array, k, s);
-            if (st == CMI_SUCCESS && p->wave_row_start) {
-                p->cfg.kernel = CMI_CSR_STREAM_WAVE;
-                p->cfg.block_size = 256;
-                p->cfg.rows_per_block = 0; // (the partition's: about Q / mean rows per wave)
-                p->cfg.items_per_thread = k;
-                p->cfg.threads_per_row = 0;
-                p->cfg.nontemporal &= ~kPolStrided;
-                if (!(want_partition && part_shape.nontemporal)) { // (a caller's policy bits are kept as given)
-                    if (num_entries * (int64_t)(sizeof(int) + vbytes) > kInfinityCacheBytes + kInfinityCacheBytes / 4) p->cfg.nontemporal |= kPolLoadNT;
-                    p->cfg.nontemporal |= kPolStoreNT;
-                }
-            }
-        }
-    } else if (format == CMI_FORMAT_COO) {
-        int sorted = 1, long_runs = 0;
-        if (num_entries > 0) st = coo_rows_sorted(num_rows, num_entries, index_array, s, &sorted, &long_runs);
-        if (st == CMI_SUCCESS) {
-            p->coo_sorted = sorted;
-            const bool auto_kernel = !cfg || cfg->kernel == CMI_KERNEL_AUTO;
-            // sorted entries: the table's CMI_TABLE_COO_SORTED key (the tile kernel with its tuned cache policy / XCD dealing)
-            // (fewer than four entries: the tile kernel's vector loads have nothing to read -- the order-agnostic kernel stays)
-            // (a row of more than 1024 entries: the tile kernel would walk its tail serially -- the order-agnostic kernel stays)
-            if (sorted && !long_runs && auto_kernel && num_entries >= 4) select_config(CMI_TABLE_COO_SORTED, dtype, num_rows, num_cols, num_entries, cfg, &p->cfg);
-            // Sorted entries and no kernel asked for: the row indices carry no more than row offsets do.  The plan builds the
-            // offsets once (4 bytes per row of HBM it owns) and a CSR plan for them; every multiply then streams 12 bytes per
-            // entry instead of 16 through the CSR kernels -- same products, storage-order sums, rows of any length.
-            // ($CMI_COO_PLAN_OFFSETS=0: keep the COO kernels -- measurements of the tile kernel.)
-            const char *off = std::getenv("CMI_COO_PLAN_OFFSETS");
-            if (sorted && auto_kernel && num_entries >= 4 && num_rows > 0 && num_entries <= INT32_MAX - 65536 && !(off && off[0] == '0')) {
-                hipError_t e = hipMalloc((void **)&p->coo_offsets, (size_t)(num_rows + 1) * sizeof(int32_t));
-                if (e != hipSuccess) st = hip_fail(e, "cmi_plan_create: COO row offsets");
-                int sorted2 = 0;
-                if (st == CMI_SUCCESS) st = cmi_coo_row_offsets(num_rows, num_entries, index_array, p->coo_offsets, &sorted2, stream);
-                if (st == CMI_SUCCESS && sorted2)
-                    st = plan_create(CMI_FORMAT_CSR, dtype, num_rows, num_cols, num_entries, p->coo_offsets, csr_columns /* cmi_plan_create_coo: the CSR plan may then hold the run-compressed copy */, nullptr, stream, &p->coo_csr_plan);
-                if (st == CMI_SUCCESS && p->coo_csr_plan) p->cfg = p->coo_csr_plan->cfg; // what cmi_plan_config reports: the kernel that runs
-            }
-            // an explicit CMI_COO_TILE on unsorted entries would add rows up wrongly: refuse it here, where it is known
-            if (!sorted && p->cfg.kernel == CMI_COO_TILE) st = fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_create: CMI_COO_TILE needs row-sorted entries");
-        }
-    }
+    if (format == CMI_FORMAT_CSR && num_rows > 0 && num_entries > 0)
+        st = plan_csr(p, index_array, csr_columns, csr_values, ask, !cfg || cfg->kernel == CMI_KERNEL_AUTO, want16, table_shape, s);
+    else if (format == CMI_FORMAT_COO)
+        st = plan_coo(p, index_array, csr_columns, cfg, stream);
     if (st == CMI_SUCCESS && indexed && index_array && index_length(p) > 0) {
         st = fingerprint(index_length(p), index_array, s, &p->fp_index);
         p->has_fp_index = st == CMI_SUCCESS;
@@ -752,15 +801,8 @@ CMI_API int cmi_plan_create_hyb(int dtype, int64_t num_rows, int64_t num_cols, i
     if (num_rows > INT32_MAX || num_cols > INT32_MAX || ell_entries_per_row > INT32_MAX)
         return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_create_hyb: sizes exceed the int32 index type");
     if (coo_entries > 0 && !coo_row_indices) return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_create_hyb: the COO part's row indices are needed");
-    cmi_plan *p = new (std::nothrow) cmi_plan;
+    cmi_plan *p = plan_new(CMI_FORMAT_HYB, dtype, num_rows, num_cols, num_rows * ell_entries_per_row);
     if (!p) return fail(CMI_ERROR_ALLOC, "cmi_plan_create_hyb: out of host memory");
-    p->format = CMI_FORMAT_HYB;
-    p->dtype = dtype;
-    p->rows = num_rows;
-    p->cols = num_cols;
-    p->nnz = num_rows * ell_entries_per_row;
-    p->prof = row_profile{};
-    p->coo_sorted = -1;
     p->hyb_width = ell_entries_per_row;
     p->hyb_coo = coo_entries;
     select_config(CMI_FORMAT_ELL, dtype, num_rows, num_cols, p->nnz, cfg_ell, &p->cfg);
@@ -825,20 +867,13 @@ CMI_API int cmi_plan_wavev_shift_tiles(const cmi_plan *plan, int64_t *marked)
 
 CMI_API int cmi_plan_destroy(cmi_plan *plan)
 {
-    if (plan && plan->hyb_tile_start) (void)hipFree(plan->hyb_tile_start);
-    if (plan && plan->hyb_coo_plan) (void)cmi_plan_destroy(plan->hyb_coo_plan);
-    if (plan && plan->coo_csr_plan) (void)cmi_plan_destroy(plan->coo_csr_plan);
-    if (plan && plan->coo_offsets) (void)hipFree(plan->coo_offsets);
-    if (plan && plan->wave_row_start) (void)hipFree(plan->wave_row_start);
-    if (plan && plan->wavev_base) (void)hipFree(plan->wavev_base);
-    if (plan && plan->wavev_cols16) (void)hipFree(plan->wavev_cols16);
-    if (plan && plan->wavev_shift) (void)hipFree(plan->wavev_shift);
-    if (plan && plan->csr16_base) (void)hipFree(plan->csr16_base);
-    if (plan && plan->csr16_cols) (void)hipFree(plan->csr16_cols);
-    if (plan && plan->runs_start) (void)hipFree(plan->runs_start);
-    if (plan && plan->runs_pieces) (void)hipFree(plan->runs_pieces);
-    if (plan && plan->runs_packed) (void)hipFree(plan->runs_packed);
-    if (plan && plan->csr16_packed) (void)hipFree(plan->csr16_packed);
+    if (!plan) return CMI_SUCCESS;
+    if (plan->hyb_coo_plan) (void)cmi_plan_destroy(plan->hyb_coo_plan);
+    if (plan->coo_csr_plan) (void)cmi_plan_destroy(plan->coo_csr_plan);
+    void *const owned[] = {plan->hyb_tile_start, plan->coo_offsets, plan->wave_row_start, plan->wavev_base, plan->wavev_cols16, plan->wavev_shift, plan->csr16_base,
+                           plan->csr16_cols, plan->runs_start, plan->runs_pieces, plan->runs_packed, plan->csr16_packed};
+    for (void *q : owned)
+        if (q) (void)hipFree(q);
     delete plan;
     return CMI_SUCCESS;
 }

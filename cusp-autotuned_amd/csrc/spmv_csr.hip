@@ -1901,18 +1901,7 @@ static int spmv_csr(int dtype, int64_t rows, int64_t cols, int64_t nnz, const in
             c.kernel == CMI_CSR_STREAM && c.threads_per_row <= 1 && rows >= 4096 && nnz > 0) {
             const double mean = (double)nnz / (double)rows;
             const int k = (int)std::ceil(mean);
-            if (k >= 2 && k <= kWaveTileMaxK && mean >= 0.995 * k) {
-                c.kernel = CMI_CSR_STREAM_WAVE;
-                c.block_size = 256;
-                c.rows_per_block = 256;
-                c.items_per_thread = k;
-                c.threads_per_row = 0;
-                c.nontemporal &= ~kPolStrided;
-                if (!(user && user->nontemporal)) {
-                    if (nnz * (int64_t)(sizeof(int) + sizeof(T)) > kInfinityCacheBytes + kInfinityCacheBytes / 4) c.nontemporal |= kPolLoadNT;
-                    c.nontemporal |= kPolStoreNT;
-                }
-            }
+            if (k >= 2 && k <= kWaveTileMaxK && mean >= 0.995 * k) adopt_wave_shape(&c, nnz, CMI_CSR_STREAM_WAVE, 256, k, sizeof(int) + sizeof(T), user && user->nontemporal);
         }
     }
     hipStream_t s = as_stream(stream);
