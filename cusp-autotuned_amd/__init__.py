@@ -29,6 +29,7 @@ from .binding import (  # noqa: F401
     pcg_update_jacobi, pcg_direction_x_jacobi, bicgstab_s, bicgstab_xr, bicgstab_p, cr_xr, cr_py,
     csr_abs_row_sums, ell_abs_row_sums, dia_abs_row_sums, random_fill, blas_scal_recip,
     csr_strength_symmetric, csr_scale_rows, aggregates_fit, csr_elementwise, relax_jacobi_presmooth,
+    csr_ring_max, maximal_independent_set, mis_aggregate,
     Comm, OP_SUM, OP_MAX, OP_MIN, csr_column_span,
 )
 from .matrices import (  # noqa: F401

@@ -263,6 +263,10 @@ def _declare(L):
         getattr(L, f"cmi_aggregates_fit_{suf}").argtypes = [i64, i64, vp, vp, vp, vp, vp, i64, vp, vp]
         getattr(L, f"cmi_csr_elementwise_{suf}").argtypes = [i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, c_int, vp, vp, vp, i64, POINTER(c_int), vp]
         getattr(L, f"cmi_relax_jacobi_presmooth_{suf}").argtypes = [i64, vp, vp, real, vp, vp]
+    # the maximal independent set and its aggregation (csrc/mis.hip)
+    L.cmi_csr_ring_max_u64.argtypes = [i64, i64, vp, vp, vp, vp, vp]
+    L.cmi_csr_maximal_independent_set.argtypes = [i64, i64, vp, vp, c_int, ctypes.c_uint64, vp, POINTER(c_int64), POINTER(c_int), vp]
+    L.cmi_csr_mis_aggregate.argtypes = [i64, i64, vp, vp, ctypes.c_uint64, vp, vp, POINTER(c_int64), vp]
 
 
 def lib():
@@ -501,6 +505,61 @@ def relax_jacobi_presmooth(diag, b, omega, x, stream=None):
     if diag.numel() != x.numel() or b.numel() != x.numel():
         raise ValueError("relax_jacobi_presmooth: vectors must have the same length")
     check(getattr(lib(), "cmi_relax_jacobi_presmooth_" + _suffix(x))(x.numel(), _ptr(diag), _ptr(b), float(omega), _ptr(x), _stream(stream)))
+
+
+def _pattern(A, who):
+    """(num_rows, Ap, Aj) of a square CSR pattern given as (num_rows, Ap, Aj) or as an object with row_offsets / column_indices."""
+    import torch
+    if isinstance(A, (tuple, list)):
+        num_rows, Ap, Aj = A
+    else:
+        if getattr(A, "num_rows", None) != getattr(A, "num_cols", None):
+            raise ValueError(f"{who}: matrix must be square")
+        num_rows, Ap, Aj = A.num_rows, A.row_offsets, A.column_indices
+    for t, nm in ((Ap, "Ap"), (Aj, "Aj")):
+        _need(t, nm, torch.int32)
+    if Ap.numel() != num_rows + 1:
+        raise ValueError(f"{who}: array lengths do not match the matrix shape")
+    return int(num_rows), Ap, Aj
+
+
+def csr_ring_max(num_rows, Ap, Aj, x, z=None, stream=None):
+    """cmi_csr_ring_max_u64: z[i] = max(x[i], max over row i of x[Aj[jj]]) on 64-bit keys (int64 tensors holding the
+    unsigned bits).  z=None: a new tensor; z must not be x."""
+    import torch
+    num_rows, Ap, Aj = _pattern((num_rows, Ap, Aj), "csr_ring_max")
+    if z is None:
+        z = torch.empty_like(x)
+    for t, nm in ((x, "x"), (z, "z")):
+        _need(t, nm, torch.int64)
+    if x.numel() != num_rows or z.numel() != num_rows:
+        raise ValueError("csr_ring_max: x and z must have num_rows elements")
+    check(lib().cmi_csr_ring_max_u64(num_rows, Aj.numel(), _ptr(Ap), _ptr(Aj), _ptr(x), _ptr(z), _stream(stream)))
+    return z
+
+
+def maximal_independent_set(A, k=1, seed=0, stream=None):
+    """cmi_csr_maximal_independent_set: MIS(k) of the graph whose edges are the stored entries of the square CSR matrix A
+    (a CSR matrix object, or (num_rows, Ap, Aj)).  Returns (stencil int32 0/1, set_size, rounds)."""
+    import torch
+    num_rows, Ap, Aj = _pattern(A, "maximal_independent_set")
+    stencil = torch.empty(num_rows, dtype=torch.int32, device=Ap.device)
+    size, rounds = c_int64(0), c_int(0)
+    check(lib().cmi_csr_maximal_independent_set(num_rows, Aj.numel(), _ptr(Ap), _ptr(Aj), int(k), int(seed), _ptr(stencil), byref(size), byref(rounds),
+                                                _stream(stream)))
+    return stencil, int(size.value), int(rounds.value)
+
+
+def mis_aggregate(C, seed=0, stream=None):
+    """cmi_csr_mis_aggregate: aggregates of the strength matrix C (a CSR matrix object, or (num_rows, Ap, Aj)) from MIS(2).
+    Returns (aggregates int32 with -1 for a node in no aggregate, mis int32 0/1, num_aggregates)."""
+    import torch
+    num_rows, Ap, Aj = _pattern(C, "mis_aggregate")
+    aggregates = torch.empty(num_rows, dtype=torch.int32, device=Ap.device)
+    mis = torch.empty(num_rows, dtype=torch.int32, device=Ap.device)
+    count = c_int64(0)
+    check(lib().cmi_csr_mis_aggregate(num_rows, Aj.numel(), _ptr(Ap), _ptr(Aj), int(seed), _ptr(aggregates), _ptr(mis), byref(count), _stream(stream)))
+    return aggregates, mis, int(count.value)
 
 
 def _plan_handle(plan):

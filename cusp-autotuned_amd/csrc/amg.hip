@@ -15,20 +15,9 @@
 //
 // Bad offsets are the caller's error, but none addresses memory unclamped: row offsets are clamped to [0, num_entries], a
 // decreasing pair is an empty row, a column outside the matrix reads no diagonal, and no lane writes at or beyond `capacity`.
-#include "common.h"
-
-#include <vector>
-
-#include <rocprim/rocprim.hpp>
+#include "amg_shared.h"
 
 namespace cmi {
-
-constexpr int64_t kAmgCeiling = (int64_t)INT32_MAX - 65536; // entries of a CSR matrix
-constexpr int kAmgBlock = 256;
-
-static unsigned amg_blocks(int64_t n) { return (unsigned)(n < 1 ? 1 : ceil_div(n, kAmgBlock)); }
-
-__device__ __forceinline__ int amg_clamp(int p, int64_t entries) { return p < 0 ? 0 : ((int64_t)p > entries ? (int)entries : p); }
 
 // correctly rounded: the plain functions (the compiler's IEEE square root; hipcc's default is the correctly rounded f32 divide and
 // square root).  The _rn intrinsics are NOT: without OCML's rounded-operations switch __fsqrt_rn is the native, 1-ulp instruction.
@@ -36,25 +25,6 @@ __device__ __forceinline__ double amg_sqrt(double v) { return sqrt(v); }
 __device__ __forceinline__ float amg_sqrt(float v) { return sqrtf(v); }
 __device__ __forceinline__ double amg_abs(double v) { return fabs(v); }
 __device__ __forceinline__ float amg_abs(float v) { return fabsf(v); }
-
-struct amg_scratch { // device allocations of one call, released on every path out
-    std::vector<void *> p;
-    hipError_t get(void **out, size_t bytes)
-    {
-        hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-        if (e == hipSuccess) {
-            try {
-                p.push_back(*out);
-            } catch (const std::bad_alloc &) {
-                (void)hipFree(*out);
-                *out = nullptr;
-                return hipErrorOutOfMemory;
-            }
-        }
-        return e;
-    }
-    ~amg_scratch() { for (void *q : p) (void)hipFree(q); }
-};
 
 // out[0 .. n] = exclusive prefix sums of in[0 .. n] (in[n] must be 0: the total lands in out[n]); `mem` keeps the temporary
 static hipError_t amg_offsets(amg_scratch &mem, const int *in, int *out, int64_t n, hipStream_t s)

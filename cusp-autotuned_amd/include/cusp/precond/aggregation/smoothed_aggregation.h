@@ -2,15 +2,18 @@
 // multigrid by smoothed aggregation, usable as the preconditioner M of every cusp::krylov solver that takes one
 // (reference cusp/precond/aggregation/smoothed_aggregation.h, detail/smoothed_aggregation.inl).
 //   smoothed_aggregation<int, double, cusp::device_memory> M(A);  cusp::krylov::cg(A, x, b, monitor, M);
-// A: any of the five formats, converted to CSR for set-up.  Per level: strength (theta) -> standard_aggregate (host) ->
-// fit_candidates -> smooth_prolongator -> form_restriction -> galerkin_product, until a level has at most min_level_size rows
-// (500) or max_levels (10) exist; Jacobi smoothing; a dense LU on the coarsest level.  Each device_memory component returns the
+// A: any of the five formats, converted to CSR for set-up.  Per level: strength (theta) -> standard_aggregate (host; with
+// mis_aggregation set: mis_aggregate, which on device_memory makes no host copy of the structure) -> fit_candidates ->
+// smooth_prolongator -> form_restriction -> galerkin_product, until a level has at most min_level_size rows (500) or
+// max_levels (10) exist; Jacobi smoothing; a dense LU on the coarsest level.  Each device_memory component returns the
 // bits of this project's host_memory path, which is the reference's sequential algorithm.
 // (The device sparse product alone keeps exact-zero sums that the host product drops; galerkin_product removes them, see there.
 // The rho estimate is the one number the two spaces may round differently: sa_level::rho_DinvA records what each used.)
 // Deviation: rho(D^-1 A) is estimated ONCE per level, kept in sa_level::rho_DinvA and used for the prolongator and the
 // smoother (the reference passes it by value and so estimates it twice).
-// Not built: evolution strength, MIS aggregation, other smoothers, several candidate vectors, a sharded hierarchy.
+// mis_aggregation (public, false by default): set it on a default-constructed object before initialize(A) to aggregate every
+// level with mis_aggregate instead of standard_aggregate; the cross-space constructor copies it.
+// Not built: evolution strength, other smoothers, several candidate vectors, a sharded hierarchy.
 #pragma once
 #include "../../detail/multilevel.h"
 #include "../smoother/jacobi_smoother.h"
@@ -42,6 +45,7 @@ class smoothed_aggregation
 
 public:
     double theta = 0.0;
+    bool mis_aggregation = false; // aggregate with mis_aggregate (MIS(2)) instead of standard_aggregate; read by extend_hierarchy
     std::vector<sa_level<IndexType, ValueType, MemorySpace>> sa_levels;
 
     smoothed_aggregation() {}
@@ -61,7 +65,7 @@ public:
         initialize(A, B);
     }
     template <typename MemorySpace2>
-    smoothed_aggregation(const smoothed_aggregation<IndexType, ValueType, MemorySpace2> &o) : Parent(o), theta(o.theta)
+    smoothed_aggregation(const smoothed_aggregation<IndexType, ValueType, MemorySpace2> &o) : Parent(o), theta(o.theta), mis_aggregation(o.mis_aggregation)
     {
         for (size_t i = 0; i < o.sa_levels.size(); i++) sa_levels.push_back(sa_level<IndexType, ValueType, MemorySpace>(o.sa_levels[i]));
     }
@@ -94,7 +98,8 @@ private:
         Csr C, T, P, R, RAP;
         cusp::array1d<ValueType, MemorySpace> B_coarse;
         symmetric_strength_of_connection(A, C, theta);
-        standard_aggregate(C, cur.aggregates);
+        if (mis_aggregation) mis_aggregate(C, cur.aggregates);
+        else standard_aggregate(C, cur.aggregates);
         fit_candidates(cur.aggregates, cur.B, T, B_coarse);
         cur.rho_DinvA = cusp::eigen::estimate_rho_Dinv_A(A);
         smooth_prolongator(A, T, P, cur.rho_DinvA);

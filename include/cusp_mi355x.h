@@ -554,6 +554,60 @@ int cmi_csr_elementwise_f32(int64_t num_rows, int64_t num_cols, int64_t a_entrie
                             float *Cx, int64_t capacity, int *sorted_host, void *stream);
 int cmi_relax_jacobi_presmooth_f64(int64_t n, const double *d, const double *b, double omega, double *x, void *stream);
 int cmi_relax_jacobi_presmooth_f32(int64_t n, const float *d, const float *b, float omega, float *x, void *stream);
+/* A maximal independent set and the aggregation built on it (mis.hip): the reference's parallel
+ * cusp::graph::maximal_independent_set and mis_aggregate on the device.  All integer work, exact in any order.  The graph is
+ * the stored pattern of a square CSR matrix: every stored entry is an edge whatever its value, columns may repeat, rows may
+ * be unsorted, and a node always sees itself whether or not its diagonal is stored.  The set is independent and maximal
+ * (within k steps) when the pattern is symmetric -- the reference's precondition, documented and not checked; the loops end
+ * on any pattern.  Rejected with CMI_ERROR_INVALID_VALUE before any device call: negative sizes, sizes beyond the CSR
+ * ceiling (rows < INT32_MAX, entries <= INT32_MAX - 65536), null arrays with non-zero sizes, k < 0.  num_rows == 0: success,
+ * nothing written.  Row offsets are clamped to [0, num_entries] before they address anything; a column outside
+ * [0, num_rows) is never used as an address.
+ *
+ * cmi_csr_ring_max_u64: one sweep,
+ *     for i: z[i] = x[i]; for jj in [Ap[i], Ap[i + 1]): z[i] = max(z[i], x[Aj[jj]])
+ *   on unsigned 64-bit keys; a column outside the matrix contributes nothing.  z must not be x (other rows gather x).
+ *   Reads the offsets and the columns, no values: 4 num_entries + 20 num_rows bytes from memory (offsets, columns, the own
+ *   key, the store) plus 8 num_entries bytes of gathered keys that the caches serve.  Rows of up to 64 entries are reduced
+ *   by one lane, longer rows by their wave.  No allocation, no synchronisation, no atomics.
+ * cmi_csr_maximal_independent_set: MIS(k) with r(i) = random_hash(i, seed) >> 33 (31 bits; cmi_random_hash).
+ *     state[i] = 1 (undecided) for every i; rounds = 0
+ *     while a state is 1:
+ *         key[i] = state[i] << 62 | r(i) << 31 | i
+ *         k times: key = the sweep above of key                       (each reads the one before it)
+ *         for i with state[i] == 1 and (key[i] & 0x7FFFFFFF) == i:  state[i] = 2      (in the set)
+ *         for i with state[i] == 1 and state[key[i] & 0x7FFFFFFF] == 2:  state[i] = 0   (after the line above is complete)
+ *         rounds += 1
+ *     stencil[i] = (state[i] == 2);  *set_size = their number
+ *   k == 0: every node, no sweep, *rounds = 0.  Ties cannot happen: the index is part of the key.  stencil (int32, device) is
+ *   written after the last round only; set_size and rounds are host words (untouched by a refusal made before any device call,
+ *   0 after a later failure).  One host read per round: the
+ *   undecided count, with a device flag for a column outside the matrix (CMI_ERROR_INVALID_VALUE, nothing of the caller's
+ *   written).  The last sweep of a round computes undecided rows only and applies the first of the two state lines; one
+ *   further launch applies the second, forms the next keys and counts (one integer atomic per wave).  Scratch: 8 bytes per
+ *   node for each of two (k == 1) or three key arrays and 4 for the states, ONE device allocation, released on every path out.  More than
+ *   num_rows + 1 rounds cannot happen and would return CMI_ERROR_NOT_SUPPORTED.
+ * cmi_csr_mis_aggregate: aggregates from MIS(2).
+ *     mis = the stencil of MIS(2) above
+ *     key[i] = mis[i] << 31 | i;  key = sweep(key);  key[i] += mis[i] << 31;  key = sweep(key)
+ *     number = the exclusive prefix sums of mis
+ *     first[i] = (key[i] >> 31) == 0 ? -1 : number[key[i] & 0x7FFFFFFF]
+ *     an id with fewer than two members is removed (its nodes get -1); the others are renumbered densely in order
+ *   The addition (the reference's "boost") makes a set node 2 and its neighbours 1, so a set node wins the second sweep.
+ *   Two rules are this library's own.  A node whose final key has a top part of 0 has no set node within two steps: it gets
+ *   -1 (the reference would gather an id from outside the range).  This is a guard: a node leaves the rounds above only on
+ *   seeing a set node within two steps of its own rows, so with mis computed here the case does not arise.  An id with no
+ *   member at all, which only a non-symmetric pattern produces, is removed like the reference's singletons (one member: an
+ *   isolated node is its own set node).  aggregates (int32: -1 or an id in [0, *num_aggregates)) and mis (int32 0 / 1) are
+ *   device arrays of num_rows elements, written at the very end; *num_aggregates is a host word.  The member counts are
+ *   integer atomics; the prefix sums are rocprim's.  Scratch: the above plus 24 bytes per node, one allocation; synchronises.
+ * Callers find the feature by the symbols (CMI_VERSION is unchanged). */
+int cmi_csr_ring_max_u64(int64_t num_rows, int64_t num_entries, const int32_t *Ap, const int32_t *Aj, const uint64_t *x, uint64_t *z,
+                         void *stream);
+int cmi_csr_maximal_independent_set(int64_t num_rows, int64_t num_entries, const int32_t *Ap, const int32_t *Aj, int k, uint64_t seed,
+                                    int32_t *stencil, int64_t *set_size, int *rounds, void *stream);
+int cmi_csr_mis_aggregate(int64_t num_rows, int64_t num_entries, const int32_t *Ap, const int32_t *Aj, uint64_t seed, int32_t *aggregates,
+                          int32_t *mis, int64_t *num_aggregates, void *stream);
 /* A CSR row sweep with a fixed elementwise write-back (spmv_csr_epilogue.hip): the smoothers that are an SpMV followed at
  * once by passes over the vector it wrote, in one launch.  s_i is row i's sum exactly as cmi_spmv_csr_* forms it: from
  * T(0), entries in storage order, multiply then add, by one lane; the same lane evaluates the expression once and
