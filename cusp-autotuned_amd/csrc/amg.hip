@@ -26,14 +26,13 @@ __device__ __forceinline__ float amg_sqrt(float v) { return sqrtf(v); }
 __device__ __forceinline__ double amg_abs(double v) { return fabs(v); }
 __device__ __forceinline__ float amg_abs(float v) { return fabsf(v); }
 
-// out[0 .. n] = exclusive prefix sums of in[0 .. n] (in[n] must be 0: the total lands in out[n]); `mem` keeps the temporary
-static hipError_t amg_offsets(amg_scratch &mem, const int *in, int *out, int64_t n, hipStream_t s)
+// out[0 .. n] = exclusive prefix sums of in[0 .. n] (in[n] must be 0: the total lands in out[n]); `temp` keeps the temporary
+static hipError_t amg_offsets(device_array<unsigned char> &temp, const int *in, int *out, int64_t n, hipStream_t s)
 {
-    void *temp = nullptr;
     size_t bytes = 0;
     hipError_t e = rocprim::exclusive_scan(nullptr, bytes, in, out, 0, (size_t)(n + 1), rocprim::plus<int>(), s);
-    if (e == hipSuccess) e = mem.get(&temp, bytes);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(temp, bytes, in, out, 0, (size_t)(n + 1), rocprim::plus<int>(), s);
+    if (e == hipSuccess) e = temp.alloc(bytes);
+    if (e == hipSuccess) e = rocprim::exclusive_scan(temp.get(), bytes, in, out, 0, (size_t)(n + 1), rocprim::plus<int>(), s);
     return e;
 }
 
@@ -156,12 +155,14 @@ static int strength_symmetric(int64_t num_rows, int64_t num_cols, int64_t num_en
         CMI_HIP(hipStreamSynchronize(s));
         return CMI_SUCCESS;
     }
-    amg_scratch mem;
-    T *diag = nullptr;
-    int *count = nullptr;
-    hipError_t e = mem.get((void **)&diag, (size_t)num_rows * sizeof(T));
-    if (e == hipSuccess) e = mem.get((void **)&count, (size_t)(num_rows + 1) * sizeof(int));
+    device_array<T> diag_block;
+    device_array<int> count_block;
+    device_array<unsigned char> scan_temp;
+    hipError_t e = diag_block.alloc((size_t)num_rows);
+    if (e == hipSuccess) e = count_block.alloc((size_t)num_rows + 1);
     if (e != hipSuccess) return hip_fail(e, "cmi_csr_strength_symmetric: scratch");
+    T *const diag = diag_block.get();
+    int *const count = count_block.get();
     int st = CMI_SUCCESS;
     hipLaunchKernelGGL((strength_diagonal_kernel<T>), dim3(amg_blocks(num_rows)), dim3(kAmgBlock), 0, s, num_rows, num_entries, Ap, Aj, Ax, diag);
     e = hipGetLastError();
@@ -170,7 +171,7 @@ static int strength_symmetric(int64_t num_rows, int64_t num_cols, int64_t num_en
         hipLaunchKernelGGL((strength_kernel<T, false>), dim3(amg_blocks(num_rows + 1)), dim3(kAmgBlock), 0, s, num_rows, num_entries, Ap, Aj, Ax, (const T *)diag,
                            theta, count, (const int *)nullptr, (int *)nullptr, (T *)nullptr, capacity);
         e = hipGetLastError();
-        if (e == hipSuccess) e = amg_offsets(mem, count, Sp, num_rows, s);
+        if (e == hipSuccess) e = amg_offsets(scan_temp, count, Sp, num_rows, s);
         if (e == hipSuccess) {
             hipLaunchKernelGGL((strength_kernel<T, true>), dim3(amg_blocks(num_rows)), dim3(kAmgBlock), 0, s, num_rows, num_entries, Ap, Aj, Ax, (const T *)diag,
                                theta, (int *)nullptr, (const int *)Sp, Sj, Sx, capacity);
@@ -321,34 +322,36 @@ static int aggregates_fit(int64_t n, int64_t num_aggregates, const int *aggregat
         CMI_HIP(hipStreamSynchronize(s));
         return CMI_SUCCESS;
     }
-    amg_scratch mem;
-    uint32_t *key = nullptr, *key_sorted = nullptr, *rows = nullptr;
-    int *keep = nullptr, *bad = nullptr;
-    void *temp = nullptr;
+    device_array<uint32_t> key_block, key_sorted_block, rows_block;
+    device_array<int> keep_block;
+    device_counters<int> bad; // (zeroed below, behind the other allocations)
+    device_array<unsigned char> temp, scan_temp;
     size_t temp_bytes = 0;
     rocprim::counting_iterator<uint32_t> position(0);
     const unsigned end_bit = (unsigned)amg_bits_for(num_aggregates + 1);
-    hipError_t e = mem.get((void **)&key, (size_t)n * sizeof(uint32_t));
-    if (e == hipSuccess) e = mem.get((void **)&key_sorted, (size_t)n * sizeof(uint32_t));
-    if (e == hipSuccess) e = mem.get((void **)&rows, (size_t)n * sizeof(uint32_t));
-    if (e == hipSuccess) e = mem.get((void **)&keep, (size_t)(n + 1) * sizeof(int));
-    if (e == hipSuccess) e = mem.get((void **)&bad, sizeof(int));
+    hipError_t e = key_block.alloc((size_t)n);
+    if (e == hipSuccess) e = key_sorted_block.alloc((size_t)n);
+    if (e == hipSuccess) e = rows_block.alloc((size_t)n);
+    if (e == hipSuccess) e = keep_block.alloc((size_t)n + 1);
+    if (e == hipSuccess) e = bad.block.alloc(1);
+    uint32_t *const key = key_block.get(), *const key_sorted = key_sorted_block.get(), *const rows = rows_block.get();
+    int *const keep = keep_block.get();
     if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, temp_bytes, (const uint32_t *)key, key_sorted, position, rows, (unsigned)n, 0u, end_bit, s);
-    if (e == hipSuccess) e = mem.get(&temp, temp_bytes);
+    if (e == hipSuccess) e = temp.alloc(temp_bytes);
     if (e != hipSuccess) return hip_fail(e, "cmi_aggregates_fit: scratch");
-    int bad_host = 0;
-    e = hipMemsetAsync(bad, 0, sizeof(int), s);
+    e = hipMemsetAsync(bad.dev(), 0, sizeof(int), s);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(fit_keys_kernel, dim3(amg_blocks(n + 1)), dim3(kAmgBlock), 0, s, n, num_aggregates, aggregates, key, keep, bad);
+        hipLaunchKernelGGL(fit_keys_kernel, dim3(amg_blocks(n + 1)), dim3(kAmgBlock), 0, s, n, num_aggregates, aggregates, key, keep, bad.dev());
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad_host, bad, sizeof(int), hipMemcpyDeviceToHost, s);
-    hipError_t e2 = hipStreamSynchronize(s); // the flag is read once, before anything of the caller's is written
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return hip_fail(e, "cmi_aggregates_fit: checking the aggregate ids");
-    if (bad_host) return fail(CMI_ERROR_INVALID_VALUE, "cmi_aggregates_fit: an aggregate id lies outside [-1, num_aggregates)");
-    e = rocprim::radix_sort_pairs(temp, temp_bytes, (const uint32_t *)key, key_sorted, position, rows, (unsigned)n, 0u, end_bit, s);
-    if (e == hipSuccess) e = amg_offsets(mem, keep, Tp, n, s);
+    if (e == hipSuccess) e = bad.fetch(s); // the flag is read once, before anything of the caller's is written
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(s); // (the blocks go when this returns)
+        return hip_fail(e, "cmi_aggregates_fit: checking the aggregate ids");
+    }
+    if (bad.host[0]) return fail(CMI_ERROR_INVALID_VALUE, "cmi_aggregates_fit: an aggregate id lies outside [-1, num_aggregates)");
+    e = rocprim::radix_sort_pairs(temp.get(), temp_bytes, (const uint32_t *)key, key_sorted, position, rows, (unsigned)n, 0u, end_bit, s);
+    if (e == hipSuccess) e = amg_offsets(scan_temp, keep, Tp, n, s);
     if (e == hipSuccess && num_aggregates > 0) {
         hipLaunchKernelGGL((fit_norms_kernel<T>), dim3(amg_blocks(num_aggregates)), dim3(kAmgBlock), 0, s, n, num_aggregates, (const uint32_t *)key_sorted,
                            (const uint32_t *)rows, B, R);
@@ -359,7 +362,7 @@ static int aggregates_fit(int64_t n, int64_t num_aggregates, const int *aggregat
                            capacity);
         e = hipGetLastError();
     }
-    e2 = hipStreamSynchronize(s);
+    const hipError_t e2 = hipStreamSynchronize(s);
     if (e == hipSuccess) e = e2;
     return e == hipSuccess ? CMI_SUCCESS : hip_fail(e, "cmi_aggregates_fit");
 }
@@ -440,30 +443,32 @@ static int csr_elementwise(int64_t num_rows, int64_t num_cols, int64_t a_entries
         return fail(CMI_ERROR_INVALID_VALUE, "cmi_csr_elementwise: null array");
     *sorted_host = 0;
     hipStream_t s = as_stream(stream);
-    amg_scratch mem;
-    int *count = nullptr, *flag = nullptr;
-    hipError_t e = mem.get((void **)&count, (size_t)(num_rows + 1) * sizeof(int));
-    if (e == hipSuccess) e = mem.get((void **)&flag, sizeof(int));
+    device_array<int> count_block;
+    device_counters<int> unsorted;
+    device_array<unsigned char> scan_temp;
+    hipError_t e = count_block.alloc((size_t)num_rows + 1);
+    if (e == hipSuccess) e = unsorted.block.alloc(1);
     if (e != hipSuccess) return hip_fail(e, "cmi_csr_elementwise: scratch");
-    int unsorted = 0;
-    e = hipMemsetAsync(flag, 0, sizeof(int), s);
+    int *const count = count_block.get();
+    e = hipMemsetAsync(unsorted.dev(), 0, sizeof(int), s);
     if (e == hipSuccess) {
         hipLaunchKernelGGL((elementwise_kernel<T, false>), dim3(amg_blocks(num_rows + 1)), dim3(kAmgBlock), 0, s, num_rows, num_cols, a_entries, Ap, Aj, Ax, b_entries,
-                           Bp, Bj, Bx, op, count, flag, (const int *)nullptr, (int *)nullptr, (T *)nullptr, capacity);
+                           Bp, Bj, Bx, op, count, unsorted.dev(), (const int *)nullptr, (int *)nullptr, (T *)nullptr, capacity);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&unsorted, flag, sizeof(int), hipMemcpyDeviceToHost, s);
-    hipError_t e2 = hipStreamSynchronize(s); // the flag is read once, before anything of the caller's is written
-    if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) return hip_fail(e, "cmi_csr_elementwise: counting");
-    if (unsorted) return CMI_SUCCESS; // *sorted_host == 0: the caller sorts, or takes its host path
-    e = amg_offsets(mem, count, Cp, num_rows, s);
+    if (e == hipSuccess) e = unsorted.fetch(s); // the flag is read once, before anything of the caller's is written
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(s); // (the blocks go when this returns)
+        return hip_fail(e, "cmi_csr_elementwise: counting");
+    }
+    if (unsorted.host[0]) return CMI_SUCCESS; // *sorted_host == 0: the caller sorts, or takes its host path
+    e = amg_offsets(scan_temp, count, Cp, num_rows, s);
     if (e == hipSuccess && num_rows > 0) {
         hipLaunchKernelGGL((elementwise_kernel<T, true>), dim3(amg_blocks(num_rows)), dim3(kAmgBlock), 0, s, num_rows, num_cols, a_entries, Ap, Aj, Ax, b_entries, Bp,
                            Bj, Bx, op, (int *)nullptr, (int *)nullptr, (const int *)Cp, Cj, Cx, capacity);
         e = hipGetLastError();
     }
-    e2 = hipStreamSynchronize(s);
+    const hipError_t e2 = hipStreamSynchronize(s);
     if (e == hipSuccess) e = e2;
     if (e != hipSuccess) return hip_fail(e, "cmi_csr_elementwise");
     *sorted_host = 1;

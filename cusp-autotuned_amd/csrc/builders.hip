@@ -15,7 +15,6 @@
 // {r+1 | ix<m-1}, {r+m | iy<n-1}; its offset has the closed form used below, so every lane writes
 // its row independently (no scan).
 #include "common.h"
-#include <vector>
 
 namespace cmi {
 
@@ -277,21 +276,17 @@ CMI_API int cmi_csr_diagonals(int64_t num_rows, int64_t num_cols, const int32_t 
     if (!Ap || !slot_map || (capacity > 0 && !diag_list)) return fail(CMI_ERROR_INVALID_VALUE, "cmi_csr_diagonals: null array");
     hipStream_t s = as_stream(stream);
     const int64_t map_len = num_rows + num_cols;
-    unsigned long long *counter = nullptr;
-    CMI_HIP(hipMalloc((void **)&counter, sizeof(unsigned long long)));
-    hipError_t e = hipMemsetAsync(counter, 0, sizeof(unsigned long long), s);
+    device_counters<unsigned long long> counter;
+    hipError_t e = counter.open(s);
     if (e == hipSuccess) e = hipMemsetAsync(slot_map, 0, (size_t)map_len * sizeof(int), s);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(dia_flag_kernel, dim3(grid_1d(num_rows * 8)), dim3(256), 0, s, num_rows, Ap, Aj, slot_map);
-        hipLaunchKernelGGL(dia_list_kernel, dim3(grid_1d(map_len)), dim3(256), 0, s, num_rows, map_len, slot_map, diag_list, capacity, counter);
+        hipLaunchKernelGGL(dia_list_kernel, dim3(grid_1d(map_len)), dim3(256), 0, s, num_rows, map_len, slot_map, diag_list, capacity, counter.dev());
         e = hipGetLastError();
     }
-    unsigned long long n = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&n, counter, sizeof(n), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(counter);
+    if (e == hipSuccess) e = counter.fetch(s);
     if (e != hipSuccess) return hip_fail(e, "cmi_csr_diagonals");
-    *num_diagonals_host = (int64_t)n;
+    *num_diagonals_host = (int64_t)counter.host[0];
     return CMI_SUCCESS;
 }
 
@@ -381,21 +376,21 @@ CMI_API int cmi_csr_column_span(int64_t num_entries, const int32_t *Aj, int32_t 
     if (num_entries == 0) return CMI_SUCCESS;
     if (!Aj) return fail(CMI_ERROR_INVALID_VALUE, "cmi_csr_column_span: null column indices");
     hipStream_t s = as_stream(stream);
-    int *dev = nullptr, host[2] = {INT32_MAX, INT32_MIN};
-    CMI_HIP(hipMalloc((void **)&dev, sizeof(host)));
-    hipError_t e = hipMemcpyAsync(dev, host, sizeof(host), hipMemcpyHostToDevice, s);
+    device_counters<int, 2> span; // (not opened: they start from the host's values, not from 0)
+    span.host[0] = INT32_MAX;
+    span.host[1] = INT32_MIN;
+    hipError_t e = span.block.alloc(2);
+    if (e == hipSuccess) e = hipMemcpyAsync(span.dev(), span.host, sizeof(span.host), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) {
         int64_t blocks = ceil_div(num_entries, 256 * 8);
         if (blocks > kCus * 8) blocks = kCus * 8;
-        hipLaunchKernelGGL(column_span_kernel, dim3((unsigned)blocks), dim3(256), 0, s, num_entries, Aj, dev);
+        hipLaunchKernelGGL(column_span_kernel, dim3((unsigned)blocks), dim3(256), 0, s, num_entries, Aj, span.dev());
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(host, dev, sizeof(host), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(dev);
+    if (e == hipSuccess) e = span.fetch(s);
     if (e != hipSuccess) return hip_fail(e, "cmi_csr_column_span");
-    *min_host = host[0];
-    *max_host = host[1];
+    *min_host = span.host[0];
+    *max_host = span.host[1];
     return CMI_SUCCESS;
 }
 
@@ -425,19 +420,19 @@ CMI_API int cmi_csr_interior_rows(int64_t num_rows, const int32_t *Ap, const int
     *last_host = num_rows;
     if (num_rows == 0) return CMI_SUCCESS;
     hipStream_t s = as_stream(stream);
-    int *dev = nullptr, host[2] = {-1, (int)num_rows};
-    CMI_HIP(hipMalloc((void **)&dev, sizeof(host)));
-    hipError_t e = hipMemcpyAsync(dev, host, sizeof(host), hipMemcpyHostToDevice, s);
+    device_counters<int, 2> edge; // (not opened: they start from the host's values, not from 0)
+    edge.host[0] = -1;
+    edge.host[1] = (int)num_rows;
+    hipError_t e = edge.block.alloc(2);
+    if (e == hipSuccess) e = hipMemcpyAsync(edge.dev(), edge.host, sizeof(edge.host), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(interior_rows_kernel, dim3(grid_1d(num_rows)), dim3(256), 0, s, num_rows, Ap, Aj, col_lo, col_hi, num_rows / 2, dev);
+        hipLaunchKernelGGL(interior_rows_kernel, dim3(grid_1d(num_rows)), dim3(256), 0, s, num_rows, Ap, Aj, col_lo, col_hi, num_rows / 2, edge.dev());
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(host, dev, sizeof(host), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(dev);
+    if (e == hipSuccess) e = edge.fetch(s);
     if (e != hipSuccess) return hip_fail(e, "cmi_csr_interior_rows");
-    *first_host = (int64_t)host[0] + 1;
-    *last_host = host[1];
+    *first_host = (int64_t)edge.host[0] + 1;
+    *last_host = edge.host[1];
     return CMI_SUCCESS;
 }
 
@@ -484,19 +479,15 @@ CMI_API int cmi_coo_row_offsets(int64_t num_rows, int64_t num_entries, const int
     if (!Ap || !sorted_host || (num_entries > 0 && !Ai)) return fail(CMI_ERROR_INVALID_VALUE, "cmi_coo_row_offsets: null array");
     *sorted_host = 0;
     hipStream_t s = as_stream(stream);
-    int *flag = nullptr;
-    CMI_HIP(hipMalloc((void **)&flag, sizeof(int)));
-    int host = 1;
-    hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), s);
+    device_counters<int> flag;
+    hipError_t e = flag.open(s);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(coo_row_offsets_kernel, dim3(grid_1d(num_entries + 1)), dim3(256), 0, s, num_rows, num_entries, Ai, Ap, flag);
+        hipLaunchKernelGGL(coo_row_offsets_kernel, dim3(grid_1d(num_entries + 1)), dim3(256), 0, s, num_rows, num_entries, Ai, Ap, flag.dev());
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(flag);
+    if (e == hipSuccess) e = flag.fetch(s);
     if (e != hipSuccess) return hip_fail(e, "cmi_coo_row_offsets");
-    *sorted_host = host == 0;
+    *sorted_host = flag.host[0] == 0;
     return CMI_SUCCESS;
 }
 
@@ -642,16 +633,15 @@ dia_to_csr_kernel(int64_t num_rows, int64_t num_cols, int nd, int64_t pitch, con
 static int exclusive_scan_i32(int64_t n, const int *in, int *out, int64_t *total_host, hipStream_t s)
 {
     const int64_t ntiles = ceil_div(n > 0 ? n : 1, (int64_t)kScanTile);
-    int *sums = nullptr;
-    CMI_HIP(hipMalloc((void **)&sums, (size_t)ntiles * sizeof(int)));
-    hipLaunchKernelGGL(scan_tile_sums_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, n, in, sums);
-    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(256), 0, s, ntiles, sums, out + n);
-    hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, n, in, sums, out);
+    device_array<int> sums;
+    CMI_HIP(sums.alloc((size_t)ntiles));
+    hipLaunchKernelGGL(scan_tile_sums_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, n, in, sums.get());
+    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(256), 0, s, ntiles, sums.get(), out + n);
+    hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, n, in, sums.get(), out);
     hipError_t e = hipGetLastError();
     int total = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&total, out + n, sizeof(int), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(sums);
     if (e != hipSuccess) return hip_fail(e, "exclusive scan");
     if (total < 0) return fail(CMI_ERROR_NOT_SUPPORTED, "conversion to CSR: more than INT32_MAX entries (int32 row offsets cannot address them)");
     if (total_host) *total_host = total;
@@ -665,8 +655,9 @@ static int ell_to_csr(int64_t rows, int64_t width, int64_t pitch, const int *eAj
     if (rows < 0 || width < 0 || width > kScanMaxCount || (width > 0 && pitch < rows)) return fail(CMI_ERROR_INVALID_VALUE, "cmi_ell_to_csr: bad size");
     if (!Ap || !nnz_host || (rows > 0 && width > 0 && (!eAj || !eAx))) return fail(CMI_ERROR_INVALID_VALUE, "cmi_ell_to_csr: null array");
     hipStream_t s = as_stream(stream);
-    int *counts = nullptr;
-    CMI_HIP(hipMalloc((void **)&counts, (size_t)(rows > 0 ? rows : 1) * sizeof(int)));
+    device_array<int> count_block;
+    CMI_HIP(count_block.alloc((size_t)(rows > 0 ? rows : 1)));
+    int *const counts = count_block.get();
     if (rows > 0) hipLaunchKernelGGL(ell_valid_counts_kernel, dim3(grid_1d(rows)), dim3(256), 0, s, rows, (int)width, pitch, eAj, counts);
     int st = exclusive_scan_i32(rows, counts, Ap, nnz_host, s);
     if (st == CMI_SUCCESS && Aj && Ax && *nnz_host > capacity) st = fail(CMI_ERROR_INVALID_VALUE, "cmi_ell_to_csr: capacity is smaller than the entry count");
@@ -674,7 +665,6 @@ static int ell_to_csr(int64_t rows, int64_t width, int64_t pitch, const int *eAj
         hipLaunchKernelGGL((ell_to_csr_kernel<T>), dim3(grid_1d(rows)), dim3(256), 0, s, rows, (int)width, pitch, eAj, eAx, Ap, Aj, Ax);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) st = fail(CMI_ERROR_HIP, "cmi_ell_to_csr: scatter failed");
     }
-    (void)hipFree(counts);
     return st;
 }
 
@@ -685,8 +675,9 @@ static int dia_to_csr(int64_t rows, int64_t cols, int64_t nd, int64_t pitch, con
     if (rows < 0 || cols < 0 || nd < 0 || nd > kScanMaxCount || (nd > 0 && pitch < rows)) return fail(CMI_ERROR_INVALID_VALUE, "cmi_dia_to_csr: bad size");
     if (!Ap || !nnz_host || (rows > 0 && nd > 0 && (!offsets || !vals))) return fail(CMI_ERROR_INVALID_VALUE, "cmi_dia_to_csr: null array");
     hipStream_t s = as_stream(stream);
-    int *counts = nullptr;
-    CMI_HIP(hipMalloc((void **)&counts, (size_t)(rows > 0 ? rows : 1) * sizeof(int)));
+    device_array<int> count_block;
+    CMI_HIP(count_block.alloc((size_t)(rows > 0 ? rows : 1)));
+    int *const counts = count_block.get();
     if (rows > 0) hipLaunchKernelGGL((dia_valid_counts_kernel<T>), dim3(grid_1d(rows)), dim3(256), 0, s, rows, cols, (int)nd, pitch, offsets, vals, counts);
     int st = exclusive_scan_i32(rows, counts, Ap, nnz_host, s);
     if (st == CMI_SUCCESS && Aj && Ax && *nnz_host > capacity) st = fail(CMI_ERROR_INVALID_VALUE, "cmi_dia_to_csr: capacity is smaller than the entry count");
@@ -694,7 +685,6 @@ static int dia_to_csr(int64_t rows, int64_t cols, int64_t nd, int64_t pitch, con
         hipLaunchKernelGGL((dia_to_csr_kernel<T>), dim3(grid_1d(rows)), dim3(256), 0, s, rows, cols, (int)nd, pitch, offsets, vals, Ap, Aj, Ax);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) st = fail(CMI_ERROR_HIP, "cmi_dia_to_csr: scatter failed");
     }
-    (void)hipFree(counts);
     return st;
 }
 
@@ -737,10 +727,10 @@ static int hyb_to_csr(int64_t rows, int64_t width, int64_t pitch, const int *eAj
     if (!Ap || !nnz_host || (rows > 0 && width > 0 && (!eAj || !eAx)) || (ncoo > 0 && (!cAi || !cAj || !cAx)))
         return fail(CMI_ERROR_INVALID_VALUE, "cmi_hyb_to_csr: null array");
     hipStream_t s = as_stream(stream);
-    int *scratch = nullptr; // [rows + 1] COO row offsets | [rows] counts | order flag
+    device_array<int> block; // [rows + 1] COO row offsets | [rows] counts | order flag
     const size_t n1 = (size_t)rows + 1;
-    CMI_HIP(hipMalloc((void **)&scratch, (2 * n1 + 1) * sizeof(int)));
-    int *coo_off = scratch, *counts = scratch + n1, *flag = scratch + 2 * n1;
+    CMI_HIP(block.alloc(2 * n1 + 1));
+    int *coo_off = block.get(), *counts = coo_off + n1, *flag = coo_off + 2 * n1;
     int st = CMI_SUCCESS, unsorted = 0;
     hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), s);
     if (e == hipSuccess) {
@@ -759,7 +749,6 @@ static int hyb_to_csr(int64_t rows, int64_t width, int64_t pitch, const int *eAj
         hipLaunchKernelGGL((hyb_to_csr_kernel<T>), dim3(grid_1d(rows)), dim3(256), 0, s, rows, (int)width, pitch, eAj, eAx, coo_off, cAj, cAx, Ap, Aj, Ax);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) st = fail(CMI_ERROR_HIP, "cmi_hyb_to_csr: scatter failed");
     }
-    (void)hipFree(scratch);
     return st;
 }
 
@@ -826,19 +815,15 @@ CMI_API int cmi_hyb_entries_per_row(int dtype, int64_t num_rows, const int32_t *
         if (st) return st;
     }
     hipStream_t s = as_stream(stream);
-    unsigned int *dev = nullptr;
-    const size_t bytes = (size_t)(kHybCap + 1) * sizeof(unsigned int);
-    CMI_HIP(hipMalloc((void **)&dev, bytes));
-    std::vector<unsigned int> hist(kHybCap + 1);
-    hipError_t e = hipMemsetAsync(dev, 0, bytes, s);
+    device_counters<unsigned int, kHybCap + 1> bins;
+    hipError_t e = bins.open(s);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(row_length_histogram_kernel, dim3(grid_1d(num_rows)), dim3(256), 0, s, num_rows, Ap, dev);
+        hipLaunchKernelGGL(row_length_histogram_kernel, dim3(grid_1d(num_rows)), dim3(256), 0, s, num_rows, Ap, bins.dev());
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(hist.data(), dev, bytes, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(dev);
+    if (e == hipSuccess) e = bins.fetch(s);
     if (e != hipSuccess) return hip_fail(e, "cmi_hyb_entries_per_row");
+    const unsigned int *const hist = bins.host;
     int max_len = 0;
     for (int k = 0; k <= kHybCap; k++) if (hist[k]) max_len = k;
     int64_t K = max_len;
@@ -891,20 +876,17 @@ template <typename T> static int count_zeros(int64_t n, const T *v, int64_t *cou
     if (n == 0) return CMI_SUCCESS;
     if (!v) return fail(CMI_ERROR_INVALID_VALUE, "cmi_count_zeros: null array");
     hipStream_t s = as_stream(stream);
-    unsigned long long *dev = nullptr, host = 0;
-    CMI_HIP(hipMalloc((void **)&dev, sizeof(host)));
-    hipError_t e = hipMemsetAsync(dev, 0, sizeof(host), s);
+    device_counters<unsigned long long> zeros;
+    hipError_t e = zeros.open(s);
     if (e == hipSuccess) {
         int64_t blocks = ceil_div(n, 256 * 8);
         if (blocks > kCus * 16) blocks = kCus * 16;
-        hipLaunchKernelGGL((count_zeros_kernel<T>), dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(256), 0, s, n, v, dev);
+        hipLaunchKernelGGL((count_zeros_kernel<T>), dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(256), 0, s, n, v, zeros.dev());
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&host, dev, sizeof(host), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(dev);
+    if (e == hipSuccess) e = zeros.fetch(s);
     if (e != hipSuccess) return hip_fail(e, "cmi_count_zeros");
-    *count_host = (int64_t)host;
+    *count_host = (int64_t)zeros.host[0];
     return CMI_SUCCESS;
 }
 } // namespace cmi

@@ -88,8 +88,7 @@ static int rccl_fail(ncclResult_t r, const char *what)
 struct cmi_comm {
     ncclComm_t nccl = nullptr;
     int rank = 0, world = 1, device = 0;
-    double *scratch = nullptr; // 256 device bytes: the barrier's token and the staging of cmi_comm_allgather_host's small records
-    size_t scratch_bytes = 0;
+    cmi::device_array<double> scratch; // 4096 device bytes: the barrier's token and the staging of cmi_comm_allgather_host's small records
 };
 
 using namespace cmi;
@@ -121,9 +120,8 @@ CMI_API int cmi_comm_create(const void *unique_id, int rank, int world, cmi_comm
     memcpy(&id, unique_id, sizeof(id));
     ncclResult_t r = g_rccl.CommInitRank(&c->nccl, world, id, rank); // collective: every rank of the world calls it
     if (r != ncclSuccess) { delete c; return rccl_fail(r, "ncclCommInitRank"); }
-    c->scratch_bytes = 4096;
-    e = hipMalloc((void **)&c->scratch, c->scratch_bytes);
-    if (e == hipSuccess) e = hipMemset(c->scratch, 0, c->scratch_bytes);
+    e = c->scratch.alloc(4096 / sizeof(double));
+    if (e == hipSuccess) e = hipMemset(c->scratch.get(), 0, c->scratch.bytes());
     if (e != hipSuccess) { (void)g_rccl.CommDestroy(c->nccl); delete c; return hip_fail(e, "cmi_comm_create: scratch"); }
     *comm_out = c;
     return CMI_SUCCESS;
@@ -133,7 +131,7 @@ CMI_API int cmi_comm_destroy(cmi_comm *comm)
 {
     if (!comm) return CMI_SUCCESS;
     int st = CMI_SUCCESS;
-    if (comm->scratch) (void)hipFree(comm->scratch);
+    comm->scratch.reset(); // (before the communicator goes)
     if (comm->nccl && g_rccl.CommDestroy) {
         const ncclResult_t r = g_rccl.CommDestroy(comm->nccl);
         if (r != ncclSuccess) st = rccl_fail(r, "ncclCommDestroy");
@@ -292,7 +290,7 @@ CMI_API int cmi_allreduce_f64(cmi_comm *comm, const double *send, double *recv, 
 CMI_API int cmi_comm_barrier(cmi_comm *comm, void *stream)
 {
     if (int st = check_comm(comm, "cmi_comm_barrier")) return st;
-    CMI_RCCL(g_rccl.AllReduce(comm->scratch, comm->scratch, 1, ncclDouble, ncclSum, comm->nccl, as_stream(stream)), "ncclAllReduce (barrier)");
+    CMI_RCCL(g_rccl.AllReduce(comm->scratch.get(), comm->scratch.get(), 1, ncclDouble, ncclSum, comm->nccl, as_stream(stream)), "ncclAllReduce (barrier)");
     CMI_HIP(hipStreamSynchronize(as_stream(stream)));
     return CMI_SUCCESS;
 }
@@ -305,9 +303,9 @@ CMI_API int cmi_comm_allgather_host(cmi_comm *comm, const void *send_host, void 
     if (bytes == 0) return CMI_SUCCESS;
     if (!send_host || !recv_host) return fail(CMI_ERROR_INVALID_VALUE, "cmi_comm_allgather_host: null buffer");
     const size_t pad = (bytes + 7) & ~(size_t)7; // whole 8-byte words per rank
-    if (pad * (size_t)comm->world + 8 > comm->scratch_bytes - 64) return fail(CMI_ERROR_INVALID_VALUE, "cmi_comm_allgather_host: record too large (bytes x world <= ~4000)");
+    if (pad * (size_t)comm->world + 8 > comm->scratch.bytes() - 64) return fail(CMI_ERROR_INVALID_VALUE, "cmi_comm_allgather_host: record too large (bytes x world <= ~4000)");
     hipStream_t s = as_stream(stream);
-    char *stage = reinterpret_cast<char *>(comm->scratch) + 64; // (the first line holds the barrier token)
+    char *stage = reinterpret_cast<char *>(comm->scratch.get()) + 64; // (the first line holds the barrier token)
     CMI_HIP(hipMemcpyAsync(stage + pad * comm->rank, send_host, bytes, hipMemcpyHostToDevice, s));
     CMI_RCCL(g_rccl.AllGather(stage + pad * comm->rank, stage, pad, ncclChar, comm->nccl, s), "ncclAllGather (host records)");
     CMI_HIP(hipStreamSynchronize(s));

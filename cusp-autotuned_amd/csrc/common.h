@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstring>
 #include <type_traits>
+#include <utility>
 
 #include "../../include/cusp_mi355x.h"
 
@@ -47,6 +48,67 @@ inline int hip_fail(hipError_t e, const char *what)
     } while (0)
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+
+// The owner of ONE device allocation in set-up code: a stack temporary of a builder, or a field of a plan.  Move-only; whatever
+// it holds when it goes out of scope, is reset() or is given another block is freed.  Errors come back as hipError_t.
+template <typename T> class device_array {
+    T *p_ = nullptr;
+    size_t bytes_ = 0;
+public:
+    device_array() = default;
+    device_array(const device_array &) = delete;
+    device_array &operator=(const device_array &) = delete;
+    device_array(device_array &&o) noexcept : p_(o.p_), bytes_(o.bytes_) { o.p_ = nullptr; o.bytes_ = 0; }
+    device_array &operator=(device_array &&o) noexcept
+    {
+        if (this != &o) {
+            reset();
+            p_ = o.p_; bytes_ = o.bytes_;
+            o.p_ = nullptr; o.bytes_ = 0;
+        }
+        return *this;
+    }
+    ~device_array() { reset(); }
+    // `count` elements, uninitialised (0: one byte, so that the block still has an address); frees what it held first
+    hipError_t alloc(size_t count)
+    {
+        reset();
+        void *q = nullptr;
+        const size_t b = count * sizeof(T);
+        const hipError_t e = hipMalloc(&q, b ? b : 1);
+        if (e == hipSuccess) { p_ = static_cast<T *>(q); bytes_ = b; }
+        return e;
+    }
+    void reset()
+    {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+        bytes_ = 0;
+    }
+    T *get() const { return p_; }
+    size_t bytes() const { return bytes_; } // as asked for; 0 when empty
+    explicit operator bool() const { return p_ != nullptr; }
+};
+
+// N words of type W that kernels add into and the host then reads: open() allocates and zeroes them on the stream, fetch() copies
+// them to `host` and synchronises the stream.
+template <typename W, int N = 1> struct device_counters {
+    device_array<W> block;
+    W host[N] = {};
+    hipError_t open(hipStream_t s)
+    {
+        hipError_t e = block.alloc(N);
+        if (e == hipSuccess) e = hipMemsetAsync(block.get(), 0, N * sizeof(W), s);
+        return e;
+    }
+    W *dev() const { return block.get(); }
+    hipError_t fetch(hipStream_t s)
+    {
+        hipError_t e = hipMemcpyAsync(host, block.get(), N * sizeof(W), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        return e;
+    }
+};
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
@@ -282,8 +344,8 @@ template <typename F> inline void with_bool(bool b, F &&f)
 } // namespace cmi
 
 // The plan object of include/cusp_mi355x.h (plan.hip): what the library learnt about one matrix.  Read-only after
-// cmi_plan_create*; owns no device memory except a HYB plan's `hyb_tile_start` (one int per 256 rows) and the opt-in
-// 16-bit column copy of a CMI_CSR_STREAM_C16 plan.
+// cmi_plan_create*.  Every device block a plan holds is a device_array field below: a builder moves a finished block in, `delete`
+// frees them all, and cmi_plan_device_bytes adds up what they were allocated with.
 struct cmi_plan {
     int format, dtype;
     int64_t rows, cols, nnz;
@@ -295,29 +357,29 @@ struct cmi_plan {
     // COO part is sorted by row -- for every tile of kHybTileRows rows the first COO entry at or after its first row
     int64_t hyb_width = 0, hyb_coo = 0;
     cmi_config hyb_coo_cfg = {};
-    int32_t *hyb_tile_start = nullptr; // device, tiles + 1 entries; null: two launches
+    cmi::device_array<int32_t> hyb_tile_start; // tiles + 1 entries; empty: two launches
     cmi_plan *hyb_coo_plan = nullptr;  // two launches: the COO half's own plan (sorted: row offsets + CSR kernels, accumulating)
     // COO whose entries are sorted by row (plan.hip): the row offsets the row indices imply (num_rows + 1 ints, built once) and
     // the CSR plan for them -- the multiply then runs the CSR kernels on (offsets, Aj, Ax) and never reads the row indices:
     // 12 nnz + 20 N bytes instead of 16 nnz + 16 N, storage-order sums, long rows handled as CSR handles them
-    int32_t *coo_offsets = nullptr;
+    cmi::device_array<int32_t> coo_offsets;
     cmi_plan *coo_csr_plan = nullptr;
     // CSR with cfg.kernel == CMI_CSR_STREAM_C16 (spmv_csr16.hip): per-tile smallest column and the 16-bit offsets from it
-    int32_t *csr16_base = nullptr;  // device, one per tile of cfg.rows_per_block rows
-    uint16_t *csr16_cols = nullptr; // device, nnz (+ padding) entries
-    int32_t *wave_row_start = nullptr; // device, 2 (wave_tiles + 1) entries, (first row, first entry) per tile: CMI_CSR_STREAM_WAVE on IRREGULAR short rows -- wave tile t owns the rows whose first
-                                       // entry lies in [t wave_q, (t + 1) wave_q) (plan.hip wave_partition); null: 64 rows per wave
+    cmi::device_array<int32_t> csr16_base;  // one per tile of cfg.rows_per_block rows
+    cmi::device_array<uint16_t> csr16_cols; // nnz (+ padding) entries
+    cmi::device_array<int32_t> wave_row_start; // 2 (wave_tiles + 1) entries, (first row, first entry) per tile: CMI_CSR_STREAM_WAVE on IRREGULAR short rows -- wave tile t owns the rows whose first
+                                       // entry lies in [t wave_q, (t + 1) wave_q) (plan.hip wave_partition); empty: 64 rows per wave
     int64_t wave_tiles = 0;
     int wave_q = 0;
     // csr_wavev with cfg.nontemporal & 8 (spmv_csr.hip wavev_cols16_build): per wave tile of the partition above the smallest column of its
     // entries, and per entry the 16-bit offset from its tile's base.  Both or neither (every tile spans at most 65535 columns, or nothing is kept).
-    int32_t *wavev_base = nullptr;    // device, wave_tiles entries
-    uint16_t *wavev_cols16 = nullptr; // device, nnz + 8 entries (zero padding), 16-byte aligned
+    cmi::device_array<int32_t> wavev_base;    // wave_tiles entries
+    cmi::device_array<uint16_t> wavev_cols16; // nnz + 8 entries (zero padding), 16-byte aligned
     // ... and, part of that copy (round 13), the SHIFT-INVARIANT tiles' table: int32 [wave_tiles][8], 32-byte aligned.  A tile of nr >= 1
     // rows of the longest row's length L <= 8 in which row r has row 0's columns plus r is MARKED: entry k < L holds Aj[nz0 + k] minus the
     // tile's first row, and the multiply forms its columns from these and reads none.  Entry 0 == INT32_MIN: not marked.  Kept only with the
-    // copy and only when at least a quarter of the tiles that have entries are marked (wavev_cols16_build); null otherwise.
-    int32_t *wavev_shift = nullptr;
+    // copy and only when at least a quarter of the tiles that have entries are marked (wavev_cols16_build); empty otherwise.
+    cmi::device_array<int32_t> wavev_shift;
     int64_t wavev_shift_marked = 0;   // marked tiles (0 without the table)
     // order-sensitive 64-bit checksums of the arrays the plan was made from (cmi_plan_validate): the index array (CSR row offsets, COO /
     // HYB-COO row indices) and -- when the plan owns data derived from them (the 16-bit copy) -- the CSR column indices
@@ -326,14 +388,12 @@ struct cmi_plan {
     int csr16_wave_k = 0;           // > 0: the copy is tiled per WAVE (64 rows; cfg.rows_per_block == 64) and multiplied by the wave-tile kernel with this many entries per lane
     bool kernel_asked = false;      // the caller named a plan-only kernel (WAVE on a partition, WAVEV, WAVEX, WAVER, PACKED): its requirements are hard errors, not fall-backs
     // CMI_CSR_STREAM_WAVER / _PACKED (spmv_csr_runs.hip): the run-compressed column copy on wave tiles (wave_tiles, wave_q as above)
-    int32_t *runs_start = nullptr;   // device, 4 (wave_tiles + 1) entries: {first row, first entry, first piece, packed offset / 16} per tile
-    uint32_t *runs_pieces = nullptr; // device, runs_count (+ padding): (first column << 2) | (length - 1)
+    cmi::device_array<int32_t> runs_start;   // 4 (wave_tiles + 1) entries: {first row, first entry, first piece, packed offset / 16} per tile
+    cmi::device_array<uint32_t> runs_pieces; // runs_count (+ padding): (first column << 2) | (length - 1)
     int64_t runs_count = 0;
     int runs_cap = 4;                // entries per piece at most (3 where that costs no more pieces: no LDS bank conflict between pieces)
-    unsigned char *runs_packed = nullptr; // device, _PACKED only: per tile [pieces | pad | values | pad]
-    int64_t runs_packed_bytes = 0;
-    unsigned char *csr16_packed = nullptr; // device, _PACKED on stencil-like rows (spmv_csr16.hip): fixed-stride wave tiles [head | row starts | 16-bit columns | values]
-    int64_t csr16_packed_bytes = 0;
+    cmi::device_array<unsigned char> runs_packed; // _PACKED only: per tile [pieces | pad | values | pad]
+    cmi::device_array<unsigned char> csr16_packed; // _PACKED on stencil-like rows (spmv_csr16.hip): fixed-stride wave tiles [head | row starts | 16-bit columns | values]
     uint64_t fp_values = 0;          // checksum of the values a _PACKED plan copied (cmi_plan_validate_values)
     bool has_fp_values = false;
 };

@@ -160,22 +160,18 @@ __global__ void __launch_bounds__(kAmgBlock) mis_flags_kernel(int64_t n, int64_t
     if (i < count) flag[i] = (i < n && (!state || state[i] == kStateIn)) ? 1 : 0;
 }
 
-// One device allocation per call, carved in 256-byte steps: a dozen hipMalloc / hipFree pairs of N-sized arrays cost more than
+// One device allocation per call, carved in 256-byte steps: a dozen allocate / free pairs of N-sized arrays cost more than
 // the sweeps they serve.  take() returns null once the reservation is used up (the caller sized it: a bug, reported as one).
 struct mis_arena {
-    char *base = nullptr;
-    size_t used = 0, size = 0;
+    device_array<char> block; // released with the arena, on every path out of the call
+    size_t used = 0;
     static size_t padded(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-    hipError_t open(amg_scratch &mem, size_t bytes)
-    {
-        size = bytes;
-        return mem.get((void **)&base, bytes);
-    }
+    hipError_t open(size_t bytes) { return block.alloc(bytes); }
     template <typename T> T *take(size_t count)
     {
         const size_t bytes = padded(count * sizeof(T));
-        if (!base || used + bytes > size) return nullptr;
-        T *p = reinterpret_cast<T *>(base + used);
+        if (!block || used + bytes > block.bytes()) return nullptr;
+        T *p = reinterpret_cast<T *>(block.get() + used);
         used += bytes;
         return p;
     }
@@ -262,11 +258,10 @@ static int maximal_independent_set(int64_t num_rows, int64_t num_entries, const 
     *set_size = 0;
     *rounds = 0;
     if (num_rows == 0) return CMI_SUCCESS;
-    amg_scratch mem;
     mis_arena arena;
     int *state = nullptr;
     if (k > 0) {
-        const hipError_t ea = arena.open(mem, mis_states_bytes(num_rows, k));
+        const hipError_t ea = arena.open(mis_states_bytes(num_rows, k));
         if (ea != hipSuccess) return hip_fail(ea, "cmi_csr_maximal_independent_set: scratch");
         const int r = mis_states(arena, num_rows, num_entries, Ap, Aj, k, seed, &state, nullptr, set_size, rounds, s);
         if (r != CMI_SUCCESS) {
@@ -330,12 +325,11 @@ static int mis_aggregate(int64_t num_rows, int64_t num_entries, const int *Ap, c
     if (num_rows == 0) return CMI_SUCCESS;
     hipStream_t s = as_stream(stream);
     const int64_t n = num_rows;
-    amg_scratch mem;
     mis_arena arena;
     size_t scan_bytes = 0; // of one exclusive scan of n + 1 ints (both scans have this shape)
     hipError_t e = rocprim::exclusive_scan(nullptr, scan_bytes, (const int *)nullptr, (int *)nullptr, 0, (size_t)(n + 1), rocprim::plus<int>(), s);
     if (e == hipSuccess)
-        e = arena.open(mem, mis_states_bytes(n, 2) + 5 * mis_arena::padded((size_t)(n + 1) * sizeof(int)) + mis_arena::padded((size_t)n * sizeof(int)) +
+        e = arena.open(mis_states_bytes(n, 2) + 5 * mis_arena::padded((size_t)(n + 1) * sizeof(int)) + mis_arena::padded((size_t)n * sizeof(int)) +
                                 mis_arena::padded(scan_bytes));
     if (e != hipSuccess) return hip_fail(e, "cmi_csr_mis_aggregate: scratch");
     int *state = nullptr, rounds = 0;

@@ -1,7 +1,7 @@
 // plan.hip -- cmi_plan: what a multiply needs to know about ONE matrix beyond its arrays, found once.
 //
 // SURVEY.md section 8(b) asked for `cmi_plan_create/destroy/select` owning "autotune table lookup, optional
-// preprocessing"; round 1 instead measured a CSR matrix's row lengths inside its first multiply (hipMalloc + copy +
+// preprocessing"; round 1 instead measured a CSR matrix's row lengths inside its first multiply (device allocation + copy +
 // stream synchronise, cached by pointer).  Here the measurement happens at plan creation, explicitly, and the
 // multiply entry points (cmi_spmv_*_plan_*) neither allocate nor wait.  The reference keeps comparable state in
 // function-local statics of its KTT path (cusp/system/cuda/ktt/csr_multiply.h:22-29,239-247: `row_starts`,
@@ -18,6 +18,7 @@
 #include "common.h"
 #include <cstdlib>
 #include <new>
+#include <utility>
 
 using namespace cmi;
 
@@ -70,20 +71,17 @@ static int fingerprint(int64_t n, const int *a, hipStream_t s, uint64_t *fp)
 {
     *fp = 0;
     if (n <= 0 || !a) return CMI_SUCCESS;
-    unsigned long long *dev = nullptr, host = 0;
-    CMI_HIP(hipMalloc((void **)&dev, sizeof(unsigned long long)));
-    hipError_t e = hipMemsetAsync(dev, 0, sizeof(host), s);
+    device_counters<unsigned long long> sum;
+    hipError_t e = sum.open(s);
     if (e == hipSuccess) {
         int64_t blocks = ceil_div(n, 256 * 8);
         if (blocks > kCus * 8) blocks = kCus * 8;
-        hipLaunchKernelGGL(fingerprint_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(256), 0, s, n, a, dev);
+        hipLaunchKernelGGL(fingerprint_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(256), 0, s, n, a, sum.dev());
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&host, dev, sizeof(host), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(dev);
+    if (e == hipSuccess) e = sum.fetch(s);
     if (e != hipSuccess) return hip_fail(e, "plan fingerprint");
-    *fp = (uint64_t)host;
+    *fp = (uint64_t)sum.host[0];
     return CMI_SUCCESS;
 }
 // how many entries of the index array a plan of this format was made from
@@ -391,18 +389,9 @@ CMI_API int cmi_plan_validate_values(const cmi_plan *plan, const void *values, v
 CMI_API int cmi_plan_device_bytes(const cmi_plan *plan, int64_t *bytes)
 {
     if (!plan || !bytes) return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_device_bytes: null argument");
-    int64_t b = 0;
-    if (plan->hyb_tile_start) b += (ceil_div(plan->rows, kHybTileRows) + 1) * 4;
-    if (plan->coo_offsets) b += (plan->rows + 1) * 4;
-    if (plan->wave_row_start) b += (plan->wave_tiles + 1) * 8;
-    if (plan->wavev_cols16) b += (plan->nnz + 8) * 2 + plan->wave_tiles * 4;
-    if (plan->wavev_shift) b += plan->wave_tiles * 32;
-    if (plan->csr16_cols) b += (plan->nnz + 8) * 2;
-    if (plan->csr16_base) b += ceil_div(plan->rows, plan->cfg.rows_per_block > 0 ? plan->cfg.rows_per_block : 1) * 4;
-    if (plan->runs_start) b += (plan->wave_tiles + 1) * 16;
-    if (plan->runs_pieces) b += (plan->runs_count + 64) * 4;
-    if (plan->runs_packed) b += plan->runs_packed_bytes;
-    if (plan->csr16_packed) b += plan->csr16_packed_bytes;
+    int64_t b = (int64_t)(plan->hyb_tile_start.bytes() + plan->coo_offsets.bytes() + plan->wave_row_start.bytes() + plan->wavev_base.bytes() +
+                          plan->wavev_cols16.bytes() + plan->wavev_shift.bytes() + plan->csr16_base.bytes() + plan->csr16_cols.bytes() +
+                          plan->runs_start.bytes() + plan->runs_pieces.bytes() + plan->runs_packed.bytes() + plan->csr16_packed.bytes());
     int64_t sub = 0;
     if (plan->hyb_coo_plan && cmi_plan_device_bytes(plan->hyb_coo_plan, &sub) == CMI_SUCCESS) b += sub;
     if (plan->coo_csr_plan && cmi_plan_device_bytes(plan->coo_csr_plan, &sub) == CMI_SUCCESS) b += sub;
@@ -707,12 +696,12 @@ static int plan_coo(cmi_plan *p, const int *Ai, const int *Aj, const cmi_config 
     const char *off = std::getenv("CMI_COO_PLAN_OFFSETS");
     int st = CMI_SUCCESS;
     if (sorted && auto_kernel && num_entries >= 4 && num_rows > 0 && num_entries <= INT32_MAX - 65536 && !(off && off[0] == '0')) {
-        hipError_t e = hipMalloc((void **)&p->coo_offsets, (size_t)(num_rows + 1) * sizeof(int32_t));
+        hipError_t e = p->coo_offsets.alloc((size_t)num_rows + 1);
         if (e != hipSuccess) st = hip_fail(e, "cmi_plan_create: COO row offsets");
         int sorted2 = 0;
-        if (st == CMI_SUCCESS) st = cmi_coo_row_offsets(num_rows, num_entries, Ai, p->coo_offsets, &sorted2, stream);
+        if (st == CMI_SUCCESS) st = cmi_coo_row_offsets(num_rows, num_entries, Ai, p->coo_offsets.get(), &sorted2, stream);
         if (st == CMI_SUCCESS && sorted2)
-            st = plan_create(CMI_FORMAT_CSR, p->dtype, num_rows, num_cols, num_entries, p->coo_offsets, Aj /* cmi_plan_create_coo: the CSR plan may then hold the run-compressed copy */, nullptr, stream, &p->coo_csr_plan);
+            st = plan_create(CMI_FORMAT_CSR, p->dtype, num_rows, num_cols, num_entries, p->coo_offsets.get(), Aj /* cmi_plan_create_coo: the CSR plan may then hold the run-compressed copy */, nullptr, stream, &p->coo_csr_plan);
         if (st == CMI_SUCCESS && p->coo_csr_plan) p->cfg = p->coo_csr_plan->cfg; // what cmi_plan_config reports: the kernel that runs
     }
     // an explicit CMI_COO_TILE on unsorted entries would add rows up wrongly: refuse it here, where it is known
@@ -821,21 +810,15 @@ CMI_API int cmi_plan_create_hyb(int dtype, int64_t num_rows, int64_t num_cols, i
         if (st == CMI_SUCCESS && sorted && !never && coo_entries <= INT32_MAX - 4096 &&
             (always || (double)coo_entries <= kHybFusedMaxPerRow * (double)num_rows)) {
             const int64_t tiles = ceil_div(num_rows, kHybTileRows);
-            int *max_dev = nullptr, max_in_tile = 0;
-            hipError_t e = hipMalloc((void **)&p->hyb_tile_start, (size_t)(tiles + 1) * sizeof(int32_t));
-            if (e == hipSuccess) e = hipMalloc((void **)&max_dev, sizeof(int));
+            device_array<int32_t> tile_start;
+            device_counters<int> max_in_tile;
+            hipError_t e = tile_start.alloc((size_t)tiles + 1);
+            if (e == hipSuccess) e = max_in_tile.open(s);
             if (e != hipSuccess) st = hip_fail(e, "cmi_plan_create_hyb: tile ranges");
-            if (st == CMI_SUCCESS) st = hyb_tile_starts(num_rows, coo_entries, coo_row_indices, p->hyb_tile_start, max_dev, s);
-            if (st == CMI_SUCCESS) {
-                e = hipMemcpyAsync(&max_in_tile, max_dev, sizeof(int), hipMemcpyDeviceToHost, s);
-                if (e == hipSuccess) e = hipStreamSynchronize(s);
-                if (e != hipSuccess) st = hip_fail(e, "cmi_plan_create_hyb: tile ranges");
-            }
-            if (max_dev) (void)hipFree(max_dev);
-            if (st == CMI_SUCCESS && !always && max_in_tile > kHybFusedMaxInTile) { // a few rows hold the COO part: two launches
-                (void)hipFree(p->hyb_tile_start);
-                p->hyb_tile_start = nullptr;
-            }
+            if (st == CMI_SUCCESS) st = hyb_tile_starts(num_rows, coo_entries, coo_row_indices, tile_start.get(), max_in_tile.dev(), s);
+            if (st == CMI_SUCCESS && (e = max_in_tile.fetch(s)) != hipSuccess) st = hip_fail(e, "cmi_plan_create_hyb: tile ranges");
+            // (a few rows hold the COO part: the ranges are dropped here, two launches)
+            if (st == CMI_SUCCESS && (always || max_in_tile.host[0] <= kHybFusedMaxInTile)) p->hyb_tile_start = std::move(tile_start);
         }
         // two launches: the COO half multiplies through a COO plan of its own (sorted entries: the CSR kernels on row offsets,
         // accumulating on top of the ELL half -- per row still the host chain)
@@ -870,11 +853,7 @@ CMI_API int cmi_plan_destroy(cmi_plan *plan)
     if (!plan) return CMI_SUCCESS;
     if (plan->hyb_coo_plan) (void)cmi_plan_destroy(plan->hyb_coo_plan);
     if (plan->coo_csr_plan) (void)cmi_plan_destroy(plan->coo_csr_plan);
-    void *const owned[] = {plan->hyb_tile_start, plan->coo_offsets, plan->wave_row_start, plan->wavev_base, plan->wavev_cols16, plan->wavev_shift, plan->csr16_base,
-                           plan->csr16_cols, plan->runs_start, plan->runs_pieces, plan->runs_packed, plan->csr16_packed};
-    for (void *q : owned)
-        if (q) (void)hipFree(q);
-    delete plan;
+    delete plan; // (its device_array fields free their blocks)
     return CMI_SUCCESS;
 }
 
@@ -912,7 +891,7 @@ CMI_API int cmi_plan_info(const cmi_plan *plan, int64_t *max_row_length, int64_t
                 exact = c.kernel == CMI_COO_TILE;
             break;
         default: // HYB: one launch = one chain per row; two launches: the same chain when the COO half is the tile kernel, else atomics
-            exact = plan->hyb_tile_start != nullptr;
+            exact = (bool)plan->hyb_tile_start;
             if (!exact && ell_lanes_per_row(c, plan->rows, plan->hyb_width) == 1) {
                 int sub = plan->hyb_coo == 0;
                 if (plan->hyb_coo_plan) (void)cmi_plan_info(plan->hyb_coo_plan, nullptr, nullptr, nullptr, &sub);

@@ -75,33 +75,20 @@ static int bits_for(int64_t count) // how many low bits hold every value in [0, 
     return b;
 }
 
-struct scratch { // device allocations of one call, released on every path out
-    void *p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    int n = 0;
-    hipError_t get(void **out, size_t bytes)
-    {
-        hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-        if (e == hipSuccess) p[n++] = *out;
-        return e;
-    }
-    ~scratch() { for (int i = 0; i < n; i++) (void)hipFree(p[i]); }
-};
-
 static int coo_order(int64_t num_rows, int64_t n, const int *Ai, const int *Aj, hipStream_t s, int *flags_host)
 {
     *flags_host = 0;
     if (n == 0) return CMI_SUCCESS;
-    scratch mem;
-    int *flags = nullptr;
-    hipError_t e = mem.get((void **)&flags, sizeof(int));
-    if (e == hipSuccess) e = hipMemsetAsync(flags, 0, sizeof(int), s);
+    device_counters<int> flags;
+    hipError_t e = flags.open(s);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(coo_order_kernel, dim3(grid_1d(n)), dim3(256), 0, s, num_rows, n, Ai, Aj, flags);
+        hipLaunchKernelGGL(coo_order_kernel, dim3(grid_1d(n)), dim3(256), 0, s, num_rows, n, Ai, Aj, flags.dev());
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(flags_host, flags, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    return e == hipSuccess ? CMI_SUCCESS : hip_fail(e, "cmi_coo_is_sorted");
+    if (e == hipSuccess) e = flags.fetch(s);
+    if (e != hipSuccess) return hip_fail(e, "cmi_coo_is_sorted");
+    *flags_host = flags.host[0];
+    return CMI_SUCCESS;
 }
 
 template <typename T>
@@ -117,61 +104,63 @@ static int coo_sort(int64_t num_rows, int64_t num_cols, int64_t n, int *Ai, int 
     if (flags & 4) return fail(CMI_ERROR_INVALID_VALUE, "cmi_coo_sort_by_row: a row index lies outside [0, num_rows)");
     if (!(flags & 3)) return CMI_SUCCESS; // already in the order asked for: nothing moves
 
-    scratch mem;
-    uint32_t *perm = nullptr;
-    void *temp = nullptr;
+    // the device blocks of this call, released on every path out
+    device_array<uint32_t> perm_block;
+    device_array<unsigned char> temp;
+    device_array<int> rows_block;
+    device_array<uint64_t> keys_block, keys_sorted_block;
+    device_array<T> vals_block;
     size_t temp_bytes = 0;
-    hipError_t e = mem.get((void **)&perm, (size_t)n * sizeof(uint32_t));
+    hipError_t e = perm_block.alloc((size_t)n);
+    uint32_t *const perm = perm_block.get();
     if (e != hipSuccess) return hip_fail(e, "cmi_coo_sort_by_row: scratch");
     rocprim::counting_iterator<uint32_t> position(0);
     const unsigned size = (unsigned)n;
     if (!and_column) {
-        int *rows_sorted = nullptr, *cols_sorted = nullptr;
-        T *vals_sorted = nullptr;
         const unsigned end_bit = (unsigned)bits_for(num_rows);
-        e = mem.get((void **)&rows_sorted, (size_t)n * sizeof(int));
+        e = rows_block.alloc((size_t)n);
+        int *const rows_sorted = rows_block.get();
         if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, temp_bytes, (const uint32_t *)Ai, (uint32_t *)rows_sorted, position, perm, size, 0u, end_bit, s);
-        if (e == hipSuccess) e = mem.get(&temp, temp_bytes);
-        if (e == hipSuccess) e = rocprim::radix_sort_pairs(temp, temp_bytes, (const uint32_t *)Ai, (uint32_t *)rows_sorted, position, perm, size, 0u, end_bit, s);
+        if (e == hipSuccess) e = temp.alloc(temp_bytes);
+        if (e == hipSuccess) e = rocprim::radix_sort_pairs(temp.get(), temp_bytes, (const uint32_t *)Ai, (uint32_t *)rows_sorted, position, perm, size, 0u, end_bit, s);
         if (e == hipSuccess) e = hipMemcpyAsync(Ai, rows_sorted, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, s);
         // the row scratch is free again once its copy has been enqueued behind it on the stream: reuse it for the columns
-        cols_sorted = rows_sorted;
+        int *const cols_sorted = rows_sorted;
         if (e == hipSuccess) {
             hipLaunchKernelGGL(gather_kernel<int>, dim3(grid_1d(n)), dim3(256), 0, s, n, perm, (const int *)Aj, cols_sorted);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipMemcpyAsync(Aj, cols_sorted, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = mem.get((void **)&vals_sorted, (size_t)n * sizeof(T));
+        if (e == hipSuccess) e = vals_block.alloc((size_t)n);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(gather_kernel<T>, dim3(grid_1d(n)), dim3(256), 0, s, n, perm, (const T *)Ax, vals_sorted);
+            hipLaunchKernelGGL(gather_kernel<T>, dim3(grid_1d(n)), dim3(256), 0, s, n, perm, (const T *)Ax, vals_block.get());
             e = hipGetLastError();
         }
-        if (e == hipSuccess) e = hipMemcpyAsync(Ax, vals_sorted, (size_t)n * sizeof(T), hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(Ax, vals_block.get(), (size_t)n * sizeof(T), hipMemcpyDeviceToDevice, s);
     } else {
-        uint64_t *keys = nullptr, *keys_sorted = nullptr;
-        T *vals_sorted = nullptr;
         const unsigned end_bit = 32u + (unsigned)bits_for(num_rows);
-        e = mem.get((void **)&keys, (size_t)n * sizeof(uint64_t));
-        if (e == hipSuccess) e = mem.get((void **)&keys_sorted, (size_t)n * sizeof(uint64_t));
+        e = keys_block.alloc((size_t)n);
+        if (e == hipSuccess) e = keys_sorted_block.alloc((size_t)n);
+        uint64_t *const keys = keys_block.get(), *const keys_sorted = keys_sorted_block.get();
         if (e == hipSuccess) {
             hipLaunchKernelGGL(pack_row_col_kernel, dim3(grid_1d(n)), dim3(256), 0, s, n, (const int *)Ai, (const int *)Aj, keys);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, temp_bytes, (const uint64_t *)keys, keys_sorted, position, perm, size, 0u, end_bit, s);
-        if (e == hipSuccess) e = mem.get(&temp, temp_bytes);
-        if (e == hipSuccess) e = rocprim::radix_sort_pairs(temp, temp_bytes, (const uint64_t *)keys, keys_sorted, position, perm, size, 0u, end_bit, s);
+        if (e == hipSuccess) e = temp.alloc(temp_bytes);
+        if (e == hipSuccess) e = rocprim::radix_sort_pairs(temp.get(), temp_bytes, (const uint64_t *)keys, keys_sorted, position, perm, size, 0u, end_bit, s);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(unpack_row_col_kernel, dim3(grid_1d(n)), dim3(256), 0, s, n, (const uint64_t *)keys_sorted, Ai, Aj);
             e = hipGetLastError();
         }
-        vals_sorted = (T *)keys; // (8 bytes per entry, no longer read)
+        T *const vals_sorted = (T *)keys; // (8 bytes per entry, no longer read)
         if (e == hipSuccess) {
             hipLaunchKernelGGL(gather_kernel<T>, dim3(grid_1d(n)), dim3(256), 0, s, n, perm, (const T *)Ax, vals_sorted);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipMemcpyAsync(Ax, vals_sorted, (size_t)n * sizeof(T), hipMemcpyDeviceToDevice, s);
     }
-    // the scratch is released when this returns: everything enqueued above must have finished with it
+    // the blocks are released when this returns: everything enqueued above must have finished with it
     hipError_t e2 = hipStreamSynchronize(s);
     if (e == hipSuccess) e = e2;
     return e == hipSuccess ? CMI_SUCCESS : hip_fail(e, "cmi_coo_sort_by_row");

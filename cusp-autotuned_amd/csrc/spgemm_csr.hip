@@ -176,35 +176,16 @@ static int capped_grid(int64_t n)
     return b < 1 ? 1 : (int)b;
 }
 
-struct spgemm_scratch { // device allocations of one call, released on every path out
-    std::vector<void *> p;
-    hipError_t get(void **out, size_t bytes)
-    {
-        hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-        if (e == hipSuccess) p.push_back(*out);
-        return e;
-    }
-    ~spgemm_scratch() { for (void *q : p) (void)hipFree(q); }
-};
-
 } // namespace cmi
 
 // What cmi_spgemm_csr_* returns: C's row offsets and its entries as one piece per slab, all on the device.
 struct cmi_spgemm {
     int dtype = CMI_F64;
     int64_t m = 0, num_entries = 0;
-    int32_t *Cp = nullptr; // m + 1; null: every offset is 0
-    struct piece { int32_t *Cj; void *Cx; int64_t count; };
+    cmi::device_array<int32_t> Cp; // m + 1; empty: every offset is 0
+    struct piece { cmi::device_array<int32_t> Cj; cmi::device_array<unsigned char> Cx; int64_t count = 0; }; // Cx: `count` values of dtype
     std::vector<piece> pieces;
     int64_t products = 0, slabs = 0, rows_in_tiles = 0, rows_in_slabs = 0;
-    ~cmi_spgemm()
-    {
-        if (Cp) (void)hipFree(Cp);
-        for (const piece &q : pieces) {
-            if (q.Cj) (void)hipFree(q.Cj);
-            if (q.Cx) (void)hipFree(q.Cx);
-        }
-    }
 };
 
 namespace cmi {
@@ -236,18 +217,22 @@ static int spgemm_csr(int64_t m, int64_t k, int64_t n, int64_t a_entries, const 
     }
 
     hipStream_t s = as_stream(stream);
-    spgemm_scratch mem;
-    int64_t *entry_start = nullptr, *row_start = nullptr;
-    void *temp = nullptr;
+    // the scratch of this call: released on every path out
+    device_array<int64_t> entry_block, row_block;
+    device_array<uint64_t> keys_block, keys_sorted_block;
+    device_array<uint32_t> perm_block, seg_block;
+    device_array<T> vals_block;
+    device_array<unsigned char> temp, sort_temp;
     size_t temp_bytes = 0;
-    hipError_t e = mem.get((void **)&entry_start, (size_t)(a_entries + 1) * sizeof(int64_t));
-    if (e == hipSuccess) e = mem.get((void **)&row_start, (size_t)(m + 1) * sizeof(int64_t));
+    hipError_t e = entry_block.alloc((size_t)a_entries + 1);
+    if (e == hipSuccess) e = row_block.alloc((size_t)m + 1);
     if (e != hipSuccess) return hip_fail(e, "cmi_spgemm_csr: scratch");
+    int64_t *const entry_start = entry_block.get(), *const row_start = row_block.get();
     hipLaunchKernelGGL(spgemm_entry_products_kernel, dim3(capped_grid(a_entries + 1)), dim3(256), 0, s, a_entries, k, b_entries, Aj, Bp, entry_start);
     CMI_LAUNCH_CHECK("spgemm entry products");
     e = rocprim::exclusive_scan(nullptr, temp_bytes, entry_start, entry_start, (int64_t)0, (size_t)(a_entries + 1), rocprim::plus<int64_t>(), s);
-    if (e == hipSuccess) e = mem.get(&temp, temp_bytes);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(temp, temp_bytes, entry_start, entry_start, (int64_t)0, (size_t)(a_entries + 1), rocprim::plus<int64_t>(), s);
+    if (e == hipSuccess) e = temp.alloc(temp_bytes);
+    if (e == hipSuccess) e = rocprim::exclusive_scan(temp.get(), temp_bytes, entry_start, entry_start, (int64_t)0, (size_t)(a_entries + 1), rocprim::plus<int64_t>(), s);
     if (e != hipSuccess) return hip_fail(e, "cmi_spgemm_csr: scan of the product counts");
     hipLaunchKernelGGL(spgemm_row_products_kernel, dim3(capped_grid(m + 1)), dim3(256), 0, s, m, a_entries, Ap, entry_start, row_start);
     CMI_LAUNCH_CHECK("spgemm row products");
@@ -269,10 +254,10 @@ static int spgemm_csr(int64_t m, int64_t k, int64_t n, int64_t a_entries, const 
     const int64_t total = start[m] - start[0];
     r->products = total;
 
-    e = hipMalloc((void **)&r->Cp, (size_t)(m + 1) * sizeof(int32_t));
+    e = r->Cp.alloc((size_t)m + 1);
     if (e != hipSuccess) return hip_fail(e, "cmi_spgemm_csr: row offsets of C");
     if (total == 0) {
-        e = hipMemsetAsync(r->Cp, 0, (size_t)(m + 1) * sizeof(int32_t), s);
+        e = hipMemsetAsync(r->Cp.get(), 0, (size_t)(m + 1) * sizeof(int32_t), s);
         hipError_t e2 = hipStreamSynchronize(s);
         if (e == hipSuccess) e = e2;
         if (e != hipSuccess) return hip_fail(e, "cmi_spgemm_csr");
@@ -308,21 +293,20 @@ static int spgemm_csr(int64_t m, int64_t k, int64_t n, int64_t a_entries, const 
         r0 = r1;
     }
 
-    uint64_t *keys = nullptr, *keys_sorted = nullptr;
-    uint32_t *perm = nullptr, *seg = nullptr;
-    T *vals = nullptr;
-    void *sort_temp = nullptr;
     size_t sort_bytes = 0, scan_bytes = 0;
     rocprim::counting_iterator<uint32_t> position(0);
     const size_t cap = (size_t)largest;
-    e = mem.get((void **)&keys, cap * sizeof(uint64_t));
-    if (e == hipSuccess) e = mem.get((void **)&keys_sorted, cap * sizeof(uint64_t));
-    if (e == hipSuccess) e = mem.get((void **)&perm, cap * sizeof(uint32_t));
-    if (e == hipSuccess) e = mem.get((void **)&seg, cap * sizeof(uint32_t));
-    if (e == hipSuccess) e = mem.get((void **)&vals, cap * sizeof(T));
+    e = keys_block.alloc(cap);
+    if (e == hipSuccess) e = keys_sorted_block.alloc(cap);
+    if (e == hipSuccess) e = perm_block.alloc(cap);
+    if (e == hipSuccess) e = seg_block.alloc(cap);
+    if (e == hipSuccess) e = vals_block.alloc(cap);
+    uint64_t *const keys = keys_block.get(), *const keys_sorted = keys_sorted_block.get();
+    uint32_t *const perm = perm_block.get(), *const seg = seg_block.get();
+    T *const vals = vals_block.get();
     if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, sort_bytes, (const uint64_t *)keys, keys_sorted, position, perm, (unsigned)cap, 0u, 64u, s);
     if (e == hipSuccess) e = rocprim::inclusive_scan(nullptr, scan_bytes, seg, seg, cap, rocprim::plus<uint32_t>(), s);
-    if (e == hipSuccess) e = mem.get(&sort_temp, std::max(sort_bytes, scan_bytes));
+    if (e == hipSuccess) e = sort_temp.alloc(std::max(sort_bytes, scan_bytes));
     if (e != hipSuccess) return hip_fail(e, "cmi_spgemm_csr: slab scratch");
     uint32_t *starts = reinterpret_cast<uint32_t *>(keys); // (the unsorted keys are dead once the sort has run)
 
@@ -336,12 +320,12 @@ static int spgemm_csr(int64_t m, int64_t k, int64_t n, int64_t a_entries, const 
         size_t sb = sort_bytes, cb = scan_bytes;
         hipLaunchKernelGGL(spgemm_expand_kernel<T>, dim3(blocks_for(P)), dim3(256), 0, s, P, start[r0], (int)r0, (int)r1, a_entries, Ap, Aj, Ax, Bp, Bj, Bx, (const int64_t *)entry_start, col_bits, col_mask, keys, vals);
         e = hipGetLastError();
-        if (e == hipSuccess) e = rocprim::radix_sort_pairs(sort_temp, sb, (const uint64_t *)keys, keys_sorted, position, perm, (unsigned)P, 0u, end_bit, s);
+        if (e == hipSuccess) e = rocprim::radix_sort_pairs(sort_temp.get(), sb, (const uint64_t *)keys, keys_sorted, position, perm, (unsigned)P, 0u, end_bit, s);
         if (e == hipSuccess) {
             hipLaunchKernelGGL(spgemm_heads_kernel, dim3(blocks_for(P)), dim3(256), 0, s, P, (const uint64_t *)keys_sorted, seg);
             e = hipGetLastError();
         }
-        if (e == hipSuccess) e = rocprim::inclusive_scan(sort_temp, cb, seg, seg, (size_t)P, rocprim::plus<uint32_t>(), s);
+        if (e == hipSuccess) e = rocprim::inclusive_scan(sort_temp.get(), cb, seg, seg, (size_t)P, rocprim::plus<uint32_t>(), s);
         uint32_t unique = 0;
         if (e == hipSuccess) e = hipMemcpyAsync(&unique, seg + (P - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -351,30 +335,31 @@ static int spgemm_csr(int64_t m, int64_t k, int64_t n, int64_t a_entries, const 
             st = fail(CMI_ERROR_INVALID_VALUE, "cmi_spgemm_csr: C has more entries than the int32 index type holds");
             break;
         }
-        cmi_spgemm::piece pc{nullptr, nullptr, U};
-        e = hipMalloc((void **)&pc.Cj, (size_t)U * sizeof(int32_t));
-        if (e == hipSuccess) e = hipMalloc(&pc.Cx, (size_t)U * sizeof(T));
+        cmi_spgemm::piece pc;
+        pc.count = U;
+        e = pc.Cj.alloc((size_t)U);
+        if (e == hipSuccess) e = pc.Cx.alloc((size_t)U * sizeof(T));
+        if (e != hipSuccess) { st = hip_fail(e, "cmi_spgemm_csr: entries of C"); break; }
+        int32_t *const Cj = pc.Cj.get();
+        T *const Cx = reinterpret_cast<T *>(pc.Cx.get());
         try {
-            r->pieces.push_back(pc); // (owned by the handle from here, whatever happens next)
+            r->pieces.push_back(std::move(pc)); // (the handle's from here)
         } catch (const std::bad_alloc &) {
-            if (pc.Cj) (void)hipFree(pc.Cj);
-            if (pc.Cx) (void)hipFree(pc.Cx);
             st = fail(CMI_ERROR_ALLOC, "cmi_spgemm_csr: out of host memory");
             break;
         }
-        if (e != hipSuccess) { st = hip_fail(e, "cmi_spgemm_csr: entries of C"); break; }
         hipLaunchKernelGGL(spgemm_starts_kernel, dim3(blocks_for(P)), dim3(256), 0, s, P, (const uint64_t *)keys_sorted, (const uint32_t *)seg, starts);
         hipLaunchKernelGGL(spgemm_sum_kernel<T>, dim3(blocks_for(U)), dim3(256), 0, s, U, P, (const uint64_t *)keys_sorted, (const uint32_t *)perm,
-                           (const uint32_t *)starts, (const T *)vals, col_mask, pc.Cj, (T *)pc.Cx);
+                           (const uint32_t *)starts, (const T *)vals, col_mask, Cj, Cx);
         hipLaunchKernelGGL(spgemm_row_offsets_kernel, dim3(blocks_for(r1 - r0)), dim3(256), 0, s, r1 - r0, P, (int)r0, entries, col_bits,
-                           (const uint64_t *)keys_sorted, (const uint32_t *)seg, r->Cp);
+                           (const uint64_t *)keys_sorted, (const uint32_t *)seg, r->Cp.get());
         e = hipGetLastError();
         if (e != hipSuccess) { st = hip_fail(e, "launch spgemm compress"); break; }
         entries += U;
         r->slabs++;
     }
     if (st == CMI_SUCCESS) {
-        e = hipMemsetD32Async((hipDeviceptr_t)(r->Cp + m), (int)entries, 1, s);
+        e = hipMemsetD32Async((hipDeviceptr_t)(r->Cp.get() + m), (int)entries, 1, s);
         if (e != hipSuccess) st = hip_fail(e, "cmi_spgemm_csr: last row offset");
     }
     // the scratch is released when this returns: everything enqueued above must have finished with it
@@ -398,13 +383,13 @@ template <typename T> static int spgemm_take(cmi_spgemm *r, int32_t *Cp, int32_t
     }
     if (!Cp || (r->num_entries > 0 && (!Cj || !Cx))) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spgemm_take: null array");
     hipStream_t s = as_stream(stream);
-    if (r->Cp) CMI_HIP(hipMemcpyAsync(Cp, r->Cp, (size_t)(r->m + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    if (r->Cp) CMI_HIP(hipMemcpyAsync(Cp, r->Cp.get(), (size_t)(r->m + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     else CMI_HIP(hipMemsetAsync(Cp, 0, (size_t)(r->m + 1) * sizeof(int32_t), s));
     int64_t at = 0;
     for (const cmi_spgemm::piece &q : r->pieces) {
         if (q.count == 0) continue;
-        CMI_HIP(hipMemcpyAsync(Cj + at, q.Cj, (size_t)q.count * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-        CMI_HIP(hipMemcpyAsync(Cx + at, q.Cx, (size_t)q.count * sizeof(T), hipMemcpyDeviceToDevice, s));
+        CMI_HIP(hipMemcpyAsync(Cj + at, q.Cj.get(), (size_t)q.count * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+        CMI_HIP(hipMemcpyAsync(Cx + at, q.Cx.get(), (size_t)q.count * sizeof(T), hipMemcpyDeviceToDevice, s));
         at += q.count;
     }
     return CMI_SUCCESS;

@@ -408,23 +408,19 @@ int coo_rows_sorted(int64_t rows, int64_t nnz, const int *Ai, hipStream_t s, int
 {
     *sorted = 0;
     if (long_runs) *long_runs = 0;
-    int *flag = nullptr;
-    CMI_HIP(hipMalloc((void **)&flag, sizeof(int)));
-    int host = 1;
-    hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), s);
+    device_counters<int> flag;
+    hipError_t e = flag.open(s);
     if (e == hipSuccess) {
         int64_t blocks = ceil_div(nnz, 256 * 8);
         if (blocks > kCus * 16) blocks = kCus * 16;
         if (blocks < 1) blocks = 1;
-        hipLaunchKernelGGL(coo_sorted_kernel, dim3((unsigned)blocks), dim3(256), 0, s, rows, nnz, Ai, flag);
+        hipLaunchKernelGGL(coo_sorted_kernel, dim3((unsigned)blocks), dim3(256), 0, s, rows, nnz, Ai, flag.dev());
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(flag);
+    if (e == hipSuccess) e = flag.fetch(s);
     if (e != hipSuccess) return hip_fail(e, "coo order check");
-    *sorted = (host & 1) == 0;
-    if (long_runs) *long_runs = (host & 2) != 0;
+    *sorted = (flag.host[0] & 1) == 0;
+    if (long_runs) *long_runs = (flag.host[0] & 2) != 0;
     return CMI_SUCCESS;
 }
 
@@ -442,8 +438,8 @@ static int spmv_coo(int dtype, int64_t rows, int64_t cols, int64_t nnz, const in
         return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_coo: too many entries for the tile kernel");
     if (!y || (nnz > 0 && (!Ai || !Aj || !Ax || !x))) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_coo: null array");
     if (plan && plan->coo_csr_plan) { // sorted entries: the plan's row offsets + the CSR kernels (the row indices are not read)
-        if constexpr (std::is_same<T, double>::value) return cmi_spmv_csr_plan_f64(plan->coo_csr_plan, plan->coo_offsets, Aj, Ax, x, y, accumulate, stream);
-        else return cmi_spmv_csr_plan_f32(plan->coo_csr_plan, plan->coo_offsets, Aj, Ax, x, y, accumulate, stream);
+        if constexpr (std::is_same<T, double>::value) return cmi_spmv_csr_plan_f64(plan->coo_csr_plan, plan->coo_offsets.get(), Aj, Ax, x, y, accumulate, stream);
+        else return cmi_spmv_csr_plan_f32(plan->coo_csr_plan, plan->coo_offsets.get(), Aj, Ax, x, y, accumulate, stream);
     }
     cmi_config c;
     if (plan) c = plan->cfg;
@@ -625,11 +621,10 @@ hyb_tile_max_kernel(int64_t tiles, const int32_t *__restrict__ tile_start, int *
     if ((threadIdx.x & (kWave - 1)) == 0 && n > 0) atomicMax(out, n);
 }
 
-// tile_start[] for the COO part (sorted by row) and *max_in_tile_dev <- the most entries of one tile (zeroed here)
+// tile_start[] for the COO part (sorted by row) and *max_in_tile_dev <- the most entries of one tile (zeroed by the caller)
 int hyb_tile_starts(int64_t rows, int64_t coo_entries, const int *coo_Ai, int32_t *tile_start, int *max_in_tile_dev, hipStream_t s)
 {
     const int64_t tiles = ceil_div(rows, kHybTileRows);
-    CMI_HIP(hipMemsetAsync(max_in_tile_dev, 0, sizeof(int), s));
     hipLaunchKernelGGL(hyb_tile_start_kernel, dim3((unsigned)ceil_div(tiles + 1, 256)), dim3(256), 0, s, tiles, (int)coo_entries, coo_Ai, tile_start);
     hipLaunchKernelGGL(hyb_tile_max_kernel, dim3((unsigned)ceil_div(tiles, 256)), dim3(256), 0, s, tiles, tile_start, max_in_tile_dev);
     CMI_LAUNCH_CHECK("hyb tile starts");
@@ -665,7 +660,7 @@ static int spmv_hyb_plan(const cmi_plan *plan, int dtype, int64_t pitch, const i
     if (wdot && dot_partial && !accumulate && tiles <= kPartialCapacity) {
         with_policy(plan->cfg.nontemporal & 3, [&](auto P) {
             constexpr int POL = decltype(P)::value;
-            hipLaunchKernelGGL((hyb_tile_kernel<T, POL, false, true>), dim3((unsigned)grid64), dim3(kHybTileRows), 0, s, rows, (int)width, pitch, eAj, eAx, cAi, cAj, cAx, plan->hyb_tile_start, x, y, tiles, tpx, swz, wdot, dot_partial);
+            hipLaunchKernelGGL((hyb_tile_kernel<T, POL, false, true>), dim3((unsigned)grid64), dim3(kHybTileRows), 0, s, rows, (int)width, pitch, eAj, eAx, cAi, cAj, cAx, plan->hyb_tile_start.get(), x, y, tiles, tpx, swz, wdot, dot_partial);
         });
         CMI_LAUNCH_CHECK("hyb tile spmv dot");
         if (dot_partials) *dot_partials = (int)tiles;
@@ -673,8 +668,8 @@ static int spmv_hyb_plan(const cmi_plan *plan, int dtype, int64_t pitch, const i
     }
     with_policy(plan->cfg.nontemporal & 3, [&](auto P) {
         constexpr int POL = decltype(P)::value;
-        if (accumulate) hipLaunchKernelGGL((hyb_tile_kernel<T, POL, true>), dim3((unsigned)grid64), dim3(kHybTileRows), 0, s, rows, (int)width, pitch, eAj, eAx, cAi, cAj, cAx, plan->hyb_tile_start, x, y, tiles, tpx, swz);
-        else            hipLaunchKernelGGL((hyb_tile_kernel<T, POL, false>), dim3((unsigned)grid64), dim3(kHybTileRows), 0, s, rows, (int)width, pitch, eAj, eAx, cAi, cAj, cAx, plan->hyb_tile_start, x, y, tiles, tpx, swz);
+        if (accumulate) hipLaunchKernelGGL((hyb_tile_kernel<T, POL, true>), dim3((unsigned)grid64), dim3(kHybTileRows), 0, s, rows, (int)width, pitch, eAj, eAx, cAi, cAj, cAx, plan->hyb_tile_start.get(), x, y, tiles, tpx, swz);
+        else            hipLaunchKernelGGL((hyb_tile_kernel<T, POL, false>), dim3((unsigned)grid64), dim3(kHybTileRows), 0, s, rows, (int)width, pitch, eAj, eAx, cAi, cAj, cAx, plan->hyb_tile_start.get(), x, y, tiles, tpx, swz);
     });
     CMI_LAUNCH_CHECK("hyb tile spmv");
     return CMI_SUCCESS;
@@ -717,7 +712,7 @@ CMI_API int cmi_spmv_coo_dot_plan_f64(const cmi_plan *plan, const int32_t *Ai, c
 {
     if (!plan || plan->format != CMI_FORMAT_COO || plan->dtype != CMI_F64)
         return cmi::fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_coo_dot_plan_f64: null plan, or a plan made for another format or value type");
-    if (plan->coo_csr_plan) return cmi_spmv_csr_dot_plan_f64(plan->coo_csr_plan, plan->coo_offsets, Aj, Ax, x, y, w, dot_dev, workspace, stream);
+    if (plan->coo_csr_plan) return cmi_spmv_csr_dot_plan_f64(plan->coo_csr_plan, plan->coo_offsets.get(), Aj, Ax, x, y, w, dot_dev, workspace, stream);
     const int st = cmi_spmv_coo_plan_f64(plan, Ai, Aj, Ax, x, y, 0, stream);
     return st ? st : cmi_blas_dot_f64(plan->rows, y, w, dot_dev, workspace, stream);
 }
@@ -726,7 +721,7 @@ CMI_API int cmi_spmv_coo_dot_plan_f32(const cmi_plan *plan, const int32_t *Ai, c
 {
     if (!plan || plan->format != CMI_FORMAT_COO || plan->dtype != CMI_F32)
         return cmi::fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_coo_dot_plan_f32: null plan, or a plan made for another format or value type");
-    if (plan->coo_csr_plan) return cmi_spmv_csr_dot_plan_f32(plan->coo_csr_plan, plan->coo_offsets, Aj, Ax, x, y, w, dot_dev, workspace, stream);
+    if (plan->coo_csr_plan) return cmi_spmv_csr_dot_plan_f32(plan->coo_csr_plan, plan->coo_offsets.get(), Aj, Ax, x, y, w, dot_dev, workspace, stream);
     const int st = cmi_spmv_coo_plan_f32(plan, Ai, Aj, Ax, x, y, 0, stream);
     return st ? st : cmi_blas_dotd_f32(plan->rows, y, w, dot_dev, workspace, stream);
 }

@@ -534,14 +534,14 @@ int wave_partition_build(cmi_plan *p, const int *Ap, int k, hipStream_t s, int q
     const int q = q_override > 0 ? q_override : kWave * k - (int)p->prof.max_len;
     if (q < 1 || rows <= 0 || nnz <= 0) return CMI_SUCCESS;
     const int64_t tiles = nnz / q + 1;
-    int32_t *start = nullptr;
-    hipError_t e = hipMalloc((void **)&start, (size_t)(tiles + 1) * 2 * sizeof(int32_t));
+    device_array<int32_t> start;
+    hipError_t e = start.alloc((size_t)(tiles + 1) * 2);
     if (e != hipSuccess) return hip_fail(e, "cmi_plan_create: wave partition");
-    hipLaunchKernelGGL(wave_partition_kernel, dim3((unsigned)ceil_div(rows + 1, 256)), dim3(256), 0, s, rows, Ap, q, tiles, start);
+    hipLaunchKernelGGL(wave_partition_kernel, dim3((unsigned)ceil_div(rows + 1, 256)), dim3(256), 0, s, rows, Ap, q, tiles, start.get());
     e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(s); // (the plan is complete when cmi_plan_create returns, like every other plan)
-    if (e != hipSuccess) { (void)hipFree(start); return hip_fail(e, "cmi_plan_create: wave partition"); }
-    p->wave_row_start = start;
+    if (e != hipSuccess) return hip_fail(e, "cmi_plan_create: wave partition");
+    p->wave_row_start = std::move(start);
     p->wave_tiles = tiles;
     p->wave_q = q;
     return CMI_SUCCESS;
@@ -648,63 +648,45 @@ int wavev_cols16_build(cmi_plan *p, const int *Aj, hipStream_t s)
     if (!p->wave_row_start || p->wave_tiles <= 0 || p->nnz <= 0 || !Aj) return CMI_SUCCESS;
     const int64_t tiles = p->wave_tiles, nnz = p->nnz;
     const unsigned grid = (unsigned)ceil_div(tiles, (int64_t)4);
-    const size_t cols_bytes = ((size_t)nnz + 8) * sizeof(uint16_t); // (zero padding: a vector load at the last entry stays inside the allocation)
     const int L = p->prof.max_len >= 1 && p->prof.max_len <= kShiftMaxLen ? (int)p->prof.max_len : 0;
-    int32_t *base = nullptr, *shift = nullptr;
-    uint16_t *cols16 = nullptr;
-    int *flag = nullptr;
-    unsigned long long *counts = nullptr;
-    int host = 1;
-    unsigned long long host_counts[2] = {0, 0};
-    hipError_t e = hipMalloc((void **)&base, (size_t)tiles * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&flag, sizeof(int));
-    if (e == hipSuccess) e = hipMemsetAsync(flag, 0, sizeof(int), s);
-    if (e == hipSuccess && L > 0) {
-        if (hipMalloc((void **)&shift, (size_t)tiles * 8 * sizeof(int32_t)) != hipSuccess || hipMalloc((void **)&counts, sizeof(host_counts)) != hipSuccess ||
-            hipMemsetAsync(counts, 0, sizeof(host_counts), s) != hipSuccess) { // (no room for the table: the copy alone)
-            (void)hipGetLastError();
-            if (shift) (void)hipFree(shift);
-            shift = nullptr;
-        }
+    device_array<int32_t> base, shift;
+    device_array<uint16_t> cols16;
+    device_counters<int> flag;                     // != 0: a tile spans more than 65535 columns
+    device_counters<unsigned long long, 2> counts; // {marked tiles, tiles that have entries}
+    hipError_t e = base.alloc((size_t)tiles);
+    if (e == hipSuccess) e = flag.open(s);
+    if (e == hipSuccess && L > 0 && (shift.alloc((size_t)tiles * 8) != hipSuccess || counts.open(s) != hipSuccess)) { // (no room for the table: the copy alone)
+        (void)hipGetLastError();
+        shift.reset();
     }
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(wavev_cols16_scan_kernel, dim3(grid), dim3(256), 0, s, p->wave_row_start, tiles, Aj, base, flag, shift, L > 0 ? L : 1,
+        hipLaunchKernelGGL(wavev_cols16_scan_kernel, dim3(grid), dim3(256), 0, s, p->wave_row_start.get(), tiles, Aj, base.get(), flag.dev(), shift.get(), L > 0 ? L : 1,
                            shift_div_mul(L > 0 ? L : 1));
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && host == 0) {
-        e = hipMalloc((void **)&cols16, cols_bytes);
-        if (e == hipSuccess) e = hipMemsetAsync(cols16 + nnz, 0, 8 * sizeof(uint16_t), s);
+    if (e == hipSuccess) e = flag.fetch(s);
+    if (e == hipSuccess && flag.host[0] == 0) {
+        e = cols16.alloc((size_t)nnz + 8); // (zero padding: a vector load at the last entry stays inside the allocation)
+        if (e == hipSuccess) e = hipMemsetAsync(cols16.get() + nnz, 0, 8 * sizeof(uint16_t), s);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(wavev_cols16_encode_kernel, dim3(grid), dim3(256), 0, s, p->wave_row_start, tiles, Aj, base, cols16);
+            hipLaunchKernelGGL(wavev_cols16_encode_kernel, dim3(grid), dim3(256), 0, s, p->wave_row_start.get(), tiles, Aj, base.get(), cols16.get());
             e = hipGetLastError();
         }
         if (e == hipSuccess && shift) {
-            hipLaunchKernelGGL(wavev_shift_count_kernel, dim3((unsigned)ceil_div(tiles, (int64_t)256)), dim3(256), 0, s, p->wave_row_start, tiles, shift, counts);
+            hipLaunchKernelGGL(wavev_shift_count_kernel, dim3((unsigned)ceil_div(tiles, (int64_t)256)), dim3(256), 0, s, p->wave_row_start.get(), tiles, shift.get(), counts.dev());
             e = hipGetLastError();
-            if (e == hipSuccess) e = hipMemcpyAsync(host_counts, counts, sizeof(host_counts), hipMemcpyDeviceToHost, s);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e == hipSuccess) e = counts.fetch(s);
+        } else if (e == hipSuccess)
+            e = hipStreamSynchronize(s);
     }
-    if (flag) (void)hipFree(flag);
-    if (counts) (void)hipFree(counts);
-    if (e != hipSuccess || host != 0) {
-        if (base) (void)hipFree(base);
-        if (cols16) (void)hipFree(cols16);
-        if (shift) (void)hipFree(shift);
-        if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return CMI_SUCCESS; } // (no room for the copy: the 32-bit kernel runs)
-        return e != hipSuccess ? hip_fail(e, "cmi_plan_create: csr_wavev 16-bit column copy") : (int)CMI_SUCCESS;
-    }
-    if (shift && !(host_counts[0] >= 1 && 4 * host_counts[0] >= host_counts[1])) { // (too few marked tiles to pay for 32 bytes per tile)
-        (void)hipFree(shift);
-        shift = nullptr;
-    }
-    p->wavev_base = base;
-    p->wavev_cols16 = cols16;
-    p->wavev_shift = shift;
-    p->wavev_shift_marked = shift ? (int64_t)host_counts[0] : 0;
+    if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return CMI_SUCCESS; } // (no room for the copy: the 32-bit kernel runs)
+    if (e != hipSuccess) return hip_fail(e, "cmi_plan_create: csr_wavev 16-bit column copy");
+    if (flag.host[0] != 0) return CMI_SUCCESS;
+    if (shift && !(counts.host[0] >= 1 && 4 * counts.host[0] >= counts.host[1])) shift.reset(); // (too few marked tiles to pay for 32 bytes per tile)
+    p->wavev_shift_marked = shift ? (int64_t)counts.host[0] : 0;
+    p->wavev_base = std::move(base);
+    p->wavev_cols16 = std::move(cols16);
+    p->wavev_shift = std::move(shift);
     p->cfg.nontemporal |= kPolCols16;
     return CMI_SUCCESS;
 }
@@ -1436,23 +1418,19 @@ __global__ void __launch_bounds__(256) max_row_length_kernel(int64_t num_rows, c
 
 int measure_row_lengths(int64_t rows, const int *Ap, hipStream_t s, int64_t *max_len, int64_t *entries_in_long_rows, int64_t *ends)
 {
-    unsigned long long *dev = nullptr;
-    CMI_HIP(hipMalloc((void **)&dev, 4 * sizeof(unsigned long long)));
-    unsigned long long host[4] = {0, 0, 0, 0};
-    hipError_t e = hipMemsetAsync(dev, 0, sizeof(host), s);
+    device_counters<unsigned long long, 4> out; // {longest row, entries in long rows, Ap[0], Ap[rows]}
+    hipError_t e = out.open(s);
     if (e == hipSuccess) {
         int64_t blocks = ceil_div(rows, 256 * 4);
         if (blocks > kCus * 8) blocks = kCus * 8;
-        hipLaunchKernelGGL(max_row_length_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(256), 0, s, rows, Ap, dev);
+        hipLaunchKernelGGL(max_row_length_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(256), 0, s, rows, Ap, out.dev());
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(host, dev, sizeof(host), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(dev);
+    if (e == hipSuccess) e = out.fetch(s);
     if (e != hipSuccess) return hip_fail(e, "row-length profile");
-    *max_len = (int64_t)host[0];
-    if (entries_in_long_rows) *entries_in_long_rows = (int64_t)host[1];
-    if (ends) { ends[0] = (int64_t)host[2]; ends[1] = (int64_t)host[3]; }
+    *max_len = (int64_t)out.host[0];
+    if (entries_in_long_rows) *entries_in_long_rows = (int64_t)out.host[1];
+    if (ends) { ends[0] = (int64_t)out.host[2]; ends[1] = (int64_t)out.host[3]; }
     return CMI_SUCCESS;
 }
 
@@ -1491,21 +1469,18 @@ __global__ void __launch_bounds__(256) column_locality_kernel(int64_t num_rows, 
 
 int measure_column_locality(int64_t rows, int64_t cols, const int *Ap, const int *Aj, int halfwin, hipStream_t s, int64_t *inside, int64_t *jumps)
 {
-    unsigned long long *dev = nullptr, host[2] = {0, 0};
-    CMI_HIP(hipMalloc((void **)&dev, sizeof(host)));
-    hipError_t e = hipMemsetAsync(dev, 0, sizeof(host), s);
+    device_counters<unsigned long long, 2> out;
+    hipError_t e = out.open(s);
     if (e == hipSuccess) {
         int64_t blocks = ceil_div(rows, 256);
         if (blocks > kCus * 16) blocks = kCus * 16;
-        hipLaunchKernelGGL(column_locality_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(256), 0, s, rows, cols, Ap, Aj, halfwin, dev);
+        hipLaunchKernelGGL(column_locality_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(256), 0, s, rows, cols, Ap, Aj, halfwin, out.dev());
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(host, dev, sizeof(host), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(dev);
+    if (e == hipSuccess) e = out.fetch(s);
     if (e != hipSuccess) return hip_fail(e, "column locality profile");
-    *inside = (int64_t)host[0];
-    *jumps = (int64_t)host[1];
+    *inside = (int64_t)out.host[0];
+    *jumps = (int64_t)out.host[1];
     return CMI_SUCCESS;
 }
 
@@ -1662,7 +1637,7 @@ static int launch_wave(const cmi_config &c, const cmi_plan *plan, int pol, hipSt
             with_int<2, 3, 4, 5, 6, 7, 8, 9, 10>(K, [&](auto KK) {
                 with_bool(dot, [&](auto DOT) {
                     hipLaunchKernelGGL((csr_wavep_kernel<T, decltype(KK)::value, decltype(P)::value, decltype(DOT)::value>), dim3((unsigned)grid64),
-                                       dim3(256), 0, s, plan->wave_row_start, plan->wave_tiles, Ap, Aj, Ax, x, y, tiles, tpx, swz, accumulate, w,
+                                       dim3(256), 0, s, plan->wave_row_start.get(), plan->wave_tiles, Ap, Aj, Ax, x, y, tiles, tpx, swz, accumulate, w,
                                        dot_partial);
                 });
             });
@@ -1725,9 +1700,9 @@ static int launch_wavev(const cmi_config &c, const cmi_plan *plan, int pol, hipS
                 with_int<0, 1, 2>(columns_from, [&](auto CF) {
                     constexpr int cf = decltype(CF)::value;
                     hipLaunchKernelGGL((csr_wavev_kernel<T, decltype(VV)::value, decltype(P)::value, decltype(DOT)::value, cf >= 1, cf == 2>),
-                                       dim3((unsigned)grid64), dim3(256), 0, s, plan->wave_row_start, plan->wave_tiles, nnz, Ap, Aj, Ax, x, y, tiles, tpx,
-                                       swz, accumulate, w, dot_partial, uniform_len, plan->wavev_cols16, plan->wavev_base, (int)(cols - 1),
-                                       plan->wavev_shift, shift_div_mul(uniform_len > 0 ? uniform_len : 1));
+                                       dim3((unsigned)grid64), dim3(256), 0, s, plan->wave_row_start.get(), plan->wave_tiles, nnz, Ap, Aj, Ax, x, y, tiles, tpx,
+                                       swz, accumulate, w, dot_partial, uniform_len, plan->wavev_cols16.get(), plan->wavev_base.get(), (int)(cols - 1),
+                                       plan->wavev_shift.get(), shift_div_mul(uniform_len > 0 ? uniform_len : 1));
                 });
             });
         });
@@ -1762,7 +1737,7 @@ static int launch_wavex(const cmi_config &c, const cmi_plan *plan, int pol, hipS
         with_int<2, 4>(V, [&](auto VV) {
             with_bool(dot, [&](auto DOT) {
                 hipLaunchKernelGGL((csr_wavex_kernel<T, decltype(VV)::value, decltype(P)::value, decltype(DOT)::value>), dim3((unsigned)grid64),
-                                   dim3(256), lds, s, plan->wave_row_start, plan->wave_tiles, nnz, rows, cols, Ap, Aj, Ax, x, y, tiles, tpx, swz,
+                                   dim3(256), lds, s, plan->wave_row_start.get(), plan->wave_tiles, nnz, rows, cols, Ap, Aj, Ax, x, y, tiles, tpx, swz,
                                    accumulate, window, w, dot_partial);
             });
         });

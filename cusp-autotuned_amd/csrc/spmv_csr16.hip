@@ -79,37 +79,30 @@ int csr16_build(cmi_plan *p, const int *Ap, const int *Aj, hipStream_t s, int wa
     if (rpb < 1 || rpb > block) return CMI_SUCCESS; // the single-pass kernel gives every row its own lane
     const int64_t tiles = ceil_div(rows, rpb);
     if (tiles > INT32_MAX) return CMI_SUCCESS;
-    int32_t *base = nullptr;
-    uint16_t *cols16 = nullptr;
-    int *flag = nullptr;
-    int host = 1;
-    hipError_t e = hipMalloc((void **)&base, (size_t)tiles * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc((void **)&flag, sizeof(int));
-    if (e == hipSuccess) e = hipMemsetAsync(flag, 0, sizeof(int), s);
+    device_array<int32_t> base;
+    device_array<uint16_t> cols16;
+    device_counters<int> flag; // != 0: a tile does not qualify
+    hipError_t e = base.alloc((size_t)tiles);
+    if (e == hipSuccess) e = flag.open(s);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(csr16_scan_kernel, dim3((unsigned)tiles), dim3(wave_k > 0 ? 64 : 256), 0, s, rows, Ap, Aj, rpb, pass_entries, base, flag);
+        hipLaunchKernelGGL(csr16_scan_kernel, dim3((unsigned)tiles), dim3(wave_k > 0 ? 64 : 256), 0, s, rows, Ap, Aj, rpb, pass_entries, base.get(), flag.dev());
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && host == 0) {
+    if (e == hipSuccess) e = flag.fetch(s);
+    if (e == hipSuccess && flag.host[0] == 0) {
         // (nnz rounded up to whole 8-byte vectors + one: the kernel's last vector load stays inside the allocation)
-        e = hipMalloc((void **)&cols16, ((size_t)nnz + 8) * sizeof(uint16_t));
-        if (e == hipSuccess) e = hipMemsetAsync(cols16, 0, ((size_t)nnz + 8) * sizeof(uint16_t), s);
+        e = cols16.alloc((size_t)nnz + 8);
+        if (e == hipSuccess) e = hipMemsetAsync(cols16.get(), 0, cols16.bytes(), s);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(csr16_encode_kernel, dim3((unsigned)tiles), dim3(wave_k > 0 ? 64 : 256), 0, s, rows, Ap, Aj, rpb, base, cols16);
+            hipLaunchKernelGGL(csr16_encode_kernel, dim3((unsigned)tiles), dim3(wave_k > 0 ? 64 : 256), 0, s, rows, Ap, Aj, rpb, base.get(), cols16.get());
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipStreamSynchronize(s);
     }
-    if (flag) (void)hipFree(flag);
-    if (e != hipSuccess || host != 0) {
-        if (base) (void)hipFree(base);
-        if (cols16) (void)hipFree(cols16);
-        return e != hipSuccess ? hip_fail(e, "cmi_plan_create: 16-bit column copy") : (int)CMI_SUCCESS;
-    }
-    p->csr16_base = base;
-    p->csr16_cols = cols16;
+    if (e != hipSuccess) return hip_fail(e, "cmi_plan_create: 16-bit column copy");
+    if (flag.host[0] != 0) return CMI_SUCCESS;
+    p->csr16_base = std::move(base);
+    p->csr16_cols = std::move(cols16);
     p->cfg.kernel = CMI_CSR_STREAM_C16;
     if (wave_k > 0) {
         p->csr16_wave_k = wave_k;
@@ -167,22 +160,19 @@ int csr16_pack(cmi_plan *p, const int *Ap, const void *values, hipStream_t s)
     const size_t vbytes = p->dtype == CMI_F64 ? 8 : 4;
     const int64_t wtiles = ceil_div(p->rows, (int64_t)kWave);
     const int64_t bytes = wtiles * pack16_span(k, vbytes);
-    unsigned char *buf = nullptr;
-    hipError_t e = hipMalloc((void **)&buf, (size_t)bytes);
+    device_array<unsigned char> buf;
+    hipError_t e = buf.alloc((size_t)bytes);
     if (e == hipSuccess) {
         const unsigned grid = (unsigned)ceil_div(wtiles, 4);
-        if (p->dtype == CMI_F64) hipLaunchKernelGGL((csr16_pack_kernel<double>), dim3(grid), dim3(256), 0, s, p->rows, wtiles, k, Ap, p->csr16_cols, p->csr16_base, (const double *)values, buf);
-        else hipLaunchKernelGGL((csr16_pack_kernel<float>), dim3(grid), dim3(256), 0, s, p->rows, wtiles, k, Ap, p->csr16_cols, p->csr16_base, (const float *)values, buf);
+        if (p->dtype == CMI_F64) hipLaunchKernelGGL((csr16_pack_kernel<double>), dim3(grid), dim3(256), 0, s, p->rows, wtiles, k, Ap, p->csr16_cols.get(), p->csr16_base.get(), (const double *)values, buf.get());
+        else hipLaunchKernelGGL((csr16_pack_kernel<float>), dim3(grid), dim3(256), 0, s, p->rows, wtiles, k, Ap, p->csr16_cols.get(), p->csr16_base.get(), (const float *)values, buf.get());
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { if (buf) (void)hipFree(buf); return hip_fail(e, "cmi_plan_create: packed wave tiles"); }
-    (void)hipFree(p->csr16_cols);
-    (void)hipFree(p->csr16_base);
-    p->csr16_cols = nullptr;
-    p->csr16_base = nullptr;
-    p->csr16_packed = buf;
-    p->csr16_packed_bytes = bytes;
+    if (e != hipSuccess) return hip_fail(e, "cmi_plan_create: packed wave tiles");
+    p->csr16_cols.reset(); // (only now: the packed buffer is complete)
+    p->csr16_base.reset();
+    p->csr16_packed = std::move(buf);
     p->cfg.kernel = CMI_CSR_STREAM_PACKED;
     return CMI_SUCCESS;
 }
@@ -446,7 +436,7 @@ static int csr16_multiply(const cmi_plan *p, const int *Ap, const T *Ax, const T
             with_int<2, 3, 4, 5, 6, 7, 8, 9, 10>(K, [&](auto KK) { // (csr16_wave_k: the longest row, 2..10, plan.hip wave_tiles_fit)
                 with_bool(wdot, [&](auto DOT) {
                     hipLaunchKernelGGL((csr_wave16p_kernel<T, decltype(KK)::value, decltype(P)::value, decltype(DOT)::value>), dim3((unsigned)wgrid), dim3(wblock),
-                                       wlds, s, rows, p->csr16_packed, x, y, wtiles, wtpx, wswz, accumulate, w, dot_partial);
+                                       wlds, s, rows, p->csr16_packed.get(), x, y, wtiles, wtpx, wswz, accumulate, w, dot_partial);
                 });
             });
         });
@@ -467,7 +457,7 @@ static int csr16_multiply(const cmi_plan *p, const int *Ap, const T *Ax, const T
             with_int<2, 3, 4, 5, 6, 7, 8, 9, 10>(K, [&](auto KK) { // (csr16_wave_k: the longest row, 2..10, plan.hip wave_tiles_fit)
                 with_bool(wdot, [&](auto DOT) {
                     hipLaunchKernelGGL((csr_wave16_kernel<T, decltype(KK)::value, decltype(P)::value, decltype(DOT)::value>), dim3((unsigned)wgrid), dim3(wblock),
-                                       wlds, s, rows, Ap, p->csr16_cols, p->csr16_base, Ax, x, y, wtiles, wtpx, wswz, accumulate, w, dot_partial);
+                                       wlds, s, rows, Ap, p->csr16_cols.get(), p->csr16_base.get(), Ax, x, y, wtiles, wtpx, wswz, accumulate, w, dot_partial);
                 });
             });
         });
@@ -489,7 +479,7 @@ static int csr16_multiply(const cmi_plan *p, const int *Ap, const T *Ax, const T
         launched = with_int<1, 2, 4>(ipt, [&](auto I) {
             with_bool(dot, [&](auto DOT) {
                 hipLaunchKernelGGL((csr_stream16_kernel<T, decltype(I)::value, decltype(P)::value, decltype(DOT)::value>), dim3((unsigned)grid64),
-                                   dim3(block), lds, s, rows, nnz, (int)p->cols, Ap, p->csr16_cols, p->csr16_base, Ax, x, y, rpb, tiles, tpx, swz,
+                                   dim3(block), lds, s, rows, nnz, (int)p->cols, Ap, p->csr16_cols.get(), p->csr16_base.get(), Ax, x, y, rpb, tiles, tpx, swz,
                                    accumulate, strided, w, dot_partial);
             });
         });

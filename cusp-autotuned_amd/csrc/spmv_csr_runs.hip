@@ -179,12 +179,11 @@ runs_pack_kernel(int64_t tiles, int32_t *__restrict__ start, const int *__restri
 static int device_exclusive_scan(const int *in, int *out, size_t n, hipStream_t s)
 {
     size_t bytes = 0;
-    void *tmp = nullptr;
+    device_array<unsigned char> tmp;
     hipError_t e = rocprim::exclusive_scan(nullptr, bytes, in, out, 0, n, rocprim::plus<int>(), s);
-    if (e == hipSuccess) e = hipMalloc(&tmp, bytes ? bytes : 16);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(tmp, bytes, in, out, 0, n, rocprim::plus<int>(), s);
+    if (e == hipSuccess) e = tmp.alloc(bytes ? bytes : 16);
+    if (e == hipSuccess) e = rocprim::exclusive_scan(tmp.get(), bytes, in, out, 0, n, rocprim::plus<int>(), s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (tmp) (void)hipFree(tmp);
     return e == hipSuccess ? (int)CMI_SUCCESS : hip_fail(e, "cmi_plan_create: run-compressed columns (scan)");
 }
 
@@ -198,13 +197,12 @@ int csr_runs_build(cmi_plan *p, const int *Ap, const int *Aj, int v, double min_
     if (rows <= 0 || nnz <= 0 || nnz > INT32_MAX - 65536 || p->cols < (p->dtype == CMI_F64 ? 2 : 4) || p->cols >= kRunMaxCols || p->prof.max_len < 1) return CMI_SUCCESS;
     const int q = 256 * v - (int)p->prof.max_len - 3;
     if (q < 1) return CMI_SUCCESS;
-    int *count = nullptr, *count3 = nullptr;
-    unsigned long long *totals = nullptr, host_totals[2] = {0, 0};
-    hipError_t e = hipMalloc((void **)&count, (size_t)(rows + 1) * 2 * sizeof(int)); // [rows + 1] cut at 4, then [rows + 1] cut at 3
+    device_array<int> counts; // [rows + 1] cut at 4, then [rows + 1] cut at 3
+    device_counters<unsigned long long, 2> totals; // pieces cut at 4, cut at 3
+    hipError_t e = counts.alloc((size_t)(rows + 1) * 2);
     if (e != hipSuccess) return hip_fail(e, "cmi_plan_create: run-compressed columns");
-    count3 = count + rows + 1;
-    e = hipMalloc((void **)&totals, sizeof(host_totals));
-    if (e == hipSuccess) e = hipMemsetAsync(totals, 0, sizeof(host_totals), s);
+    int *const count = counts.get(), *const count3 = count + rows + 1;
+    e = totals.open(s);
     if (e == hipSuccess) e = hipMemsetAsync(count + rows, 0, sizeof(int), s);
     if (e == hipSuccess) e = hipMemsetAsync(count3 + rows, 0, sizeof(int), s);
     // rows per workgroup of the tile kernels: as many as keep the block's entries inside the LDS tile at the MEAN row length (with a
@@ -218,43 +216,41 @@ int csr_runs_build(cmi_plan *p, const int *Ap, const int *Aj, int v, double min_
     // 3 % more pieces than cap 4, unless `cap_asked` (a plan's config.threads_per_row, else the rule's cap) is 3 or 4.  One walk counts both.
     int cap = kRunCap;
     if (e == hipSuccess) {
-        hipLaunchKernelGGL((runs_tile_kernel<false>), dim3(tgrid), dim3(256), 0, s, rows, Ap, Aj, rpb, kRunCap, count, count3, totals, (const int *)nullptr, (uint32_t *)nullptr);
+        hipLaunchKernelGGL((runs_tile_kernel<false>), dim3(tgrid), dim3(256), 0, s, rows, Ap, Aj, rpb, kRunCap, count, count3, totals.dev(), (const int *)nullptr, (uint32_t *)nullptr);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(host_totals, totals, sizeof(host_totals), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e == hipSuccess && (cap_asked == 3 || (cap_asked != 4 && (double)host_totals[1] <= 1.03 * (double)host_totals[0]))) cap = 3;
-    if (totals) (void)hipFree(totals);
+    if (e == hipSuccess) e = totals.fetch(s);
+    if (e == hipSuccess && (cap_asked == 3 || (cap_asked != 4 && (double)totals.host[1] <= 1.03 * (double)totals.host[0]))) cap = 3;
     int *chosen = cap == 3 ? count3 : count; // the per-row counts that are scanned, in place, into piece offsets
     int st = e == hipSuccess ? (int)CMI_SUCCESS : hip_fail(e, "cmi_plan_create: run-compressed columns");
     if (st == CMI_SUCCESS) st = device_exclusive_scan(chosen, chosen, (size_t)rows + 1, s); // chosen[r] <- pieces before row r
-    const int total = (int)(cap == 3 ? host_totals[1] : host_totals[0]); // (= chosen[rows]: the totals were summed by the same walk)
-    uint32_t *pieces = nullptr;
-    int32_t *start = nullptr;
+    const int total = (int)(cap == 3 ? totals.host[1] : totals.host[0]); // (= chosen[rows]: the totals were summed by the same walk)
+    device_array<uint32_t> pieces;
+    device_array<int32_t> start;
     const int64_t tiles = nnz / q + 1;
     if (st == CMI_SUCCESS && total > 0) {
         if (mean_piece) *mean_piece = (double)nnz / (double)total;
-        if ((double)nnz / (double)total < min_mean_piece) { (void)hipFree(count); return CMI_SUCCESS; }
-        e = hipMalloc((void **)&pieces, ((size_t)total + 64) * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemsetAsync(pieces + total, 0, 64 * sizeof(uint32_t), s);
-        if (e == hipSuccess) e = hipMalloc((void **)&start, (size_t)(tiles + 1) * 4 * sizeof(int32_t));
+        if ((double)nnz / (double)total < min_mean_piece) return CMI_SUCCESS;
+        e = pieces.alloc((size_t)total + 64);
+        if (e == hipSuccess) e = hipMemsetAsync(pieces.get() + total, 0, 64 * sizeof(uint32_t), s);
+        if (e == hipSuccess) e = start.alloc((size_t)(tiles + 1) * 4);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL((runs_tile_kernel<true>), dim3(tgrid), dim3(256), 0, s, rows, Ap, Aj, rpb, cap, (int *)nullptr, (int *)nullptr, (unsigned long long *)nullptr, (const int *)chosen, pieces);
-            hipLaunchKernelGGL(runs_partition_kernel, dim3((unsigned)ceil_div(rows + 1, 256)), dim3(256), 0, s, rows, Ap, (const int *)chosen, q, tiles, start);
+            hipLaunchKernelGGL((runs_tile_kernel<true>), dim3(tgrid), dim3(256), 0, s, rows, Ap, Aj, rpb, cap, (int *)nullptr, (int *)nullptr, (unsigned long long *)nullptr, (const int *)chosen, pieces.get());
+            hipLaunchKernelGGL(runs_partition_kernel, dim3((unsigned)ceil_div(rows + 1, 256)), dim3(256), 0, s, rows, Ap, (const int *)chosen, q, tiles, start.get());
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) st = hip_fail(e, "cmi_plan_create: run-compressed columns");
     }
-    (void)hipFree(count);
-    unsigned char *packed = nullptr;
-    int64_t packed_bytes = 0;
+    counts.reset(); // (8 (rows + 1) bytes: gone before the packed buffer is asked for)
+    device_array<unsigned char> packed;
     if (st == CMI_SUCCESS && pieces && values) { // PACKED: spans per tile -> offsets -> the copy
-        int *span = nullptr;
-        e = hipMalloc((void **)&span, (size_t)(tiles + 1) * sizeof(int));
+        device_array<int> spans; // (released at the end of this block)
+        e = spans.alloc((size_t)tiles + 1);
+        int *const span = spans.get();
         if (e == hipSuccess) e = hipMemsetAsync(span + tiles, 0, sizeof(int), s);
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(runs_span_kernel, dim3((unsigned)ceil_div(tiles, 256)), dim3(256), 0, s, tiles, start, p->dtype == CMI_F64 ? 2 : 4, span);
+            hipLaunchKernelGGL(runs_span_kernel, dim3((unsigned)ceil_div(tiles, 256)), dim3(256), 0, s, tiles, start.get(), p->dtype == CMI_F64 ? 2 : 4, span);
             e = hipGetLastError();
         }
         if (e != hipSuccess) st = hip_fail(e, "cmi_plan_create: packed tiles");
@@ -266,32 +262,24 @@ int csr_runs_build(cmi_plan *p, const int *Ap, const int *Aj, int v, double min_
         }
         if (st == CMI_SUCCESS && end16 < 0) st = fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_create: the packed copy would exceed 32 GiB");
         if (st == CMI_SUCCESS) {
-            packed_bytes = (int64_t)end16 * 16 + 64 * 16; // (+ slack: a wave's clamped request never leaves the buffer)
-            e = hipMalloc((void **)&packed, (size_t)packed_bytes);
-            if (e == hipSuccess) e = hipMemsetAsync(packed + (size_t)end16 * 16, 0, 64 * 16, s);
+            e = packed.alloc((size_t)end16 * 16 + 64 * 16); // (+ slack: a wave's clamped request never leaves the buffer)
+            if (e == hipSuccess) e = hipMemsetAsync(packed.get() + (size_t)end16 * 16, 0, 64 * 16, s);
             if (e == hipSuccess) {
                 const unsigned grid = (unsigned)ceil_div(tiles + 1, 4);
-                if (p->dtype == CMI_F64) hipLaunchKernelGGL((runs_pack_kernel<double>), dim3(grid), dim3(256), 0, s, tiles, start, span, pieces, (const double *)values, packed);
-                else hipLaunchKernelGGL((runs_pack_kernel<float>), dim3(grid), dim3(256), 0, s, tiles, start, span, pieces, (const float *)values, packed);
+                if (p->dtype == CMI_F64) hipLaunchKernelGGL((runs_pack_kernel<double>), dim3(grid), dim3(256), 0, s, tiles, start.get(), span, pieces.get(), (const double *)values, packed.get());
+                else hipLaunchKernelGGL((runs_pack_kernel<float>), dim3(grid), dim3(256), 0, s, tiles, start.get(), span, pieces.get(), (const float *)values, packed.get());
                 e = hipGetLastError();
             }
             if (e == hipSuccess) e = hipStreamSynchronize(s);
             if (e != hipSuccess) st = hip_fail(e, "cmi_plan_create: packed tiles");
         }
-        if (span) (void)hipFree(span);
     }
-    if (st != CMI_SUCCESS || !pieces) {
-        if (pieces) (void)hipFree(pieces);
-        if (start) (void)hipFree(start);
-        if (packed) (void)hipFree(packed);
-        return st;
-    }
-    p->runs_start = start;
-    p->runs_pieces = pieces;
+    if (st != CMI_SUCCESS || !pieces) return st;
+    p->runs_start = std::move(start);
+    p->runs_pieces = std::move(pieces);
     p->runs_count = total;
     p->runs_cap = cap;
-    p->runs_packed = packed;
-    p->runs_packed_bytes = packed_bytes;
+    p->runs_packed = std::move(packed);
     p->wave_tiles = tiles;
     p->wave_q = q;
     return CMI_SUCCESS;
@@ -460,8 +448,8 @@ static int csr_runs_multiply(const cmi_plan *p, const int *Ap, const int *Aj, co
             with_bool(packed, [&](auto PK) {
                 with_bool(dot, [&](auto DOT) {
                     hipLaunchKernelGGL((csr_waver_kernel<T, decltype(VV)::value, decltype(P)::value, decltype(DOT)::value, decltype(PK)::value>),
-                                       dim3((unsigned)grid64), dim3(256), 0, s, p->runs_start, p->wave_tiles, p->nnz, (int)p->cols, Ap, Aj, p->runs_pieces,
-                                       Ax, p->runs_packed, x, y, tiles, tpx, swz, accumulate, w, dot_partial);
+                                       dim3((unsigned)grid64), dim3(256), 0, s, p->runs_start.get(), p->wave_tiles, p->nnz, (int)p->cols, Ap, Aj, p->runs_pieces.get(),
+                                       Ax, p->runs_packed.get(), x, y, tiles, tpx, swz, accumulate, w, dot_partial);
                 });
             });
         });

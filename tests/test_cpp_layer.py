@@ -3,6 +3,7 @@ boundary.  tests/cpp/*.cpp are written like the reference's own tests (same matr
 see tests/cpp/spmv_tests.h); this file builds them with g++ and runs them:
   * test_host   (host_memory containers, conversions, CG, MatrixMarket)      -- CPU, -m "not gpu"
   * test_device (device_memory containers -> C-ABI -> gfx950 kernels)        -- -m gpu
+  * test_device_mem (the owner types of the library's set-up code, hipcc)     -- host_* on the CPU, gpu_* with -m gpu
 """
 import os
 import subprocess
@@ -48,6 +49,30 @@ def test_headers_compile_standalone(tmp_path):
         src.write_text(f"#include <{h}>\nint main() {{ return 0; }}\n")
         r = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", f"-I{inc}", str(src)], capture_output=True, text=True)
         assert r.returncode == 0, h + "\n" + r.stderr[-2000:]
+
+
+def _run_device_mem(prefix, count):
+    """tests/cpp/test_device_mem.cpp (hipcc: the library's common.h is a HIP header), the tests whose name starts with `prefix`."""
+    exe = os.path.join(CPP, "bin", "test_device_mem")
+    if not os.path.exists(exe):
+        _build()
+    r = subprocess.run(["timeout", "-k", "10", "60", exe, prefix], capture_output=True, text=True)
+    print(r.stdout[-2000:])
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert f"{count} tests, 0 failed" in r.stdout
+
+
+def test_device_memory_owner_types_host_part(cmi):
+    """device_array / device_counters of csrc/common.h: an empty owner is false and holds 0 bytes; moving and resetting it is harmless."""
+    _build()
+    _run_device_mem("host_", 2)
+
+
+@pytest.mark.gpu
+def test_device_memory_owner_types_on_the_device(cmi):
+    """alloc(0) / alloc(n) report their bytes, a move empties its source, a second alloc replaces the first, the counter block reads
+    zeros after open() and then what a kernel added."""
+    _run_device_mem("gpu_", 4)
 
 
 @pytest.mark.gpu
