@@ -506,8 +506,6 @@ cg_direction_fold_kernel(int64_t n, int npartial_in, double *__restrict__ area_i
     }
 }
 
-static bool aligned16(const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
 } // namespace cmi
 
 using namespace cmi;

@@ -63,7 +63,7 @@ __device__ __forceinline__ double dot_acc(wide<float>::type a, wide<float>::type
 template <typename T> bool can_widen(int64_t n, std::initializer_list<const void *> ptrs)
 {
     if (n % wide<T>::n != 0) return false;
-    for (const void *q : ptrs) if (reinterpret_cast<uintptr_t>(q) % 16 != 0) return false;
+    for (const void *q : ptrs) if (!aligned16(q)) return false;
     return true;
 }
 
@@ -490,8 +490,7 @@ template <typename T> int axpy_dot_impl(int64_t n, const double *h, const T *v, 
     if (n < 0) return fail(CMI_ERROR_INVALID_VALUE, "cmi_blas_axpy_dot: negative n");
     if (!out || !workspace || (n > 0 && (!w || !u || (h && !v)))) return fail(CMI_ERROR_INVALID_VALUE, "cmi_blas_axpy_dot: null argument");
     const int grid = grid_for(n);
-    auto aligned = [](const void *p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-    const int vec = aligned(w) && aligned(u) && (!h || aligned(v));
+    const int vec = aligned16(w, u) && (!h || aligned16(v));
     hipLaunchKernelGGL((axpy_dot_kernel<T>), dim3(grid), dim3(kBlock), 0, as_stream(stream), n, h, v, w, u, (double *)workspace, (int)(u == w), vec);
     hipLaunchKernelGGL(sum1_final_kernel, dim3(1), dim3(kBlock), 0, as_stream(stream), grid, (const double *)workspace, out, (double *)nullptr);
     CMI_LAUNCH_CHECK("axpy_dot");

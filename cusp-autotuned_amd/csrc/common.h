@@ -270,6 +270,66 @@ inline int64_t padded_grid(int64_t tiles, int swizzle)
     return ceil_div(tiles, (int64_t)kXcds * swizzle) * kXcds * swizzle;
 }
 
+// ---- the host side of a multiply launch, shared by the spmv_*.hip launchers ------------------------------------------------
+// are all these pointers 16-byte aligned?  (what the kernels' 16-byte vector loads and stores need)
+template <typename... P> inline bool aligned16(const P *...p) { return ((reinterpret_cast<uintptr_t>(p) % 16 == 0) && ...); }
+
+// What a tile kernel is launched with: its tiles, the three scalars tile_of_block() takes, and the padded grid.
+struct tile_launch { int64_t tiles, tiles_per_xcd; int swizzle; unsigned grid; };
+// ... from the tile count and a config's xcd_swizzle (< 0: launch order); `who` names the kernel in "<who>: grid too large"
+inline int tile_launch_for(int64_t tiles, int cfg_swizzle, const char *who, tile_launch *g)
+{
+    const int swz = cfg_swizzle < 0 ? 0 : cfg_swizzle;
+    const int64_t grid64 = padded_grid(tiles, swz);
+    if (grid64 > INT32_MAX) { set_error("%s: grid too large", who); return CMI_ERROR_INVALID_VALUE; }
+    *g = {tiles, ceil_div(tiles, kXcds), swz, (unsigned)grid64};
+    return CMI_SUCCESS;
+}
+
+// The fused <y, w> a multiply may be asked for: w, where the kernel leaves one partial (a double) per tile, and the caller's
+// count of them.  THE CONTRACT: the count is zeroed on entry (left(0)) and set to the number of partials only by a launch that
+// fused the dot; 0 means y is computed and the caller runs a separate dot (finish_dot below does).  A launcher fuses when
+// fits(tiles) and its own conditions (csr_stream: 16-byte aligned arrays; HYB: not accumulating) hold.
+template <typename T> struct dot_request {
+    const T *w = nullptr;
+    double *partial = nullptr;
+    int *count = nullptr;
+    bool asked() const { return w && partial; }
+    bool fits(int64_t tiles) const { return asked() && tiles <= kPartialCapacity; }
+    void left(int64_t partials) const { if (count) *count = (int)partials; }
+};
+// a fused dot leaves one partial per workgroup: widen the workgroups (ELL, DIA; 1024 lanes at most) until they fit the workspace
+inline int widen_block_for_partials(int block, int64_t rows, int rows_per_lane)
+{
+    while (block < 1024 && ceil_div(rows, (int64_t)block * rows_per_lane) > kPartialCapacity) block *= 2;
+    return block;
+}
+// the arguments every cmi_spmv_*_dot_* entry point needs besides the multiply's
+inline bool dot_args_missing(const void *w, int64_t rows, const void *dot_dev, const void *workspace)
+{
+    return (!w && rows > 0) || !dot_dev || !workspace;
+}
+// after a multiply that was asked for <y, w>: fold the partials it left, or (none: it could not fuse) the library's dot of y and w
+template <typename T> inline int finish_dot(int partials, int64_t rows, const T *y, const T *w, double *dot_dev, void *workspace, void *stream)
+{
+    if (partials > 0) {
+        if (int st = reduce_partials_f64(partials, (double *)workspace, dot_dev, as_stream(stream))) return st;
+        CMI_LAUNCH_CHECK("spmv dot fold");
+        return CMI_SUCCESS;
+    }
+    if constexpr (std::is_same<T, double>::value) return cmi_blas_dot_f64(rows, y, w, dot_dev, workspace, stream);
+    else return cmi_blas_dotd_f32(rows, y, w, dot_dev, workspace, stream);
+}
+
+// The operands of y <- A x (or y += A x) for a CSR matrix of T.
+template <typename T> struct csr_operands {
+    int64_t rows, cols, nnz;
+    const int *Ap, *Aj;
+    const T *Ax, *x;
+    T *y;
+    int accumulate;
+};
+
 template <typename T> struct vec2;
 template <> struct vec2<double> { typedef double __attribute__((ext_vector_type(2))) type; };
 template <> struct vec2<float>  { typedef float  __attribute__((ext_vector_type(2))) type; };
@@ -413,13 +473,8 @@ int wavev_cols16_build(cmi_plan *p, const int *Aj, hipStream_t s); // spmv_csr.h
 int csr16_build(cmi_plan *p, const int *Ap, const int *Aj, hipStream_t s, int wave_k = 0);
 // spmv_csr_runs.hip: the plan's run-compressed column copy (+ the packed tiles when `values` is given) and the multiply that reads it
 int csr_runs_build(cmi_plan *p, const int *Ap, const int *Aj, int v, double min_mean_piece, const void *values, hipStream_t s, double *mean_piece, int cap = 0);
-int csr_runs_multiply_f64(const cmi_plan *p, const int *Ap, const int *Aj, const double *Ax, const double *x, double *y, int accumulate, hipStream_t s,
-                          const double *w, double *dot_partial, int *dot_partials, int cache_policy, int xcd_swizzle);
-int csr_runs_multiply_f32(const cmi_plan *p, const int *Ap, const int *Aj, const float *Ax, const float *x, float *y, int accumulate, hipStream_t s,
-                          const float *w, double *dot_partial, int *dot_partials, int cache_policy, int xcd_swizzle);
 int csr16_pack(cmi_plan *p, const int *Ap, const void *values, hipStream_t s); // the wave-tiled 16-bit copy + the values -> packed wave tiles (CMI_CSR_STREAM_PACKED)
-int csr16_multiply_f64(const cmi_plan *p, const int *Ap, const double *Ax, const double *x, double *y, int accumulate,
-                       hipStream_t s, const double *w, double *dot_partial, int *dot_partials, int cache_policy, int xcd_swizzle);
-int csr16_multiply_f32(const cmi_plan *p, const int *Ap, const float *Ax, const float *x, float *y, int accumulate,
-                       hipStream_t s, const float *w, double *dot_partial, int *dot_partials, int cache_policy, int xcd_swizzle);
+// the multiplies that read those copies (instantiated for double and float in their files); both check their launch
+template <typename T> int csr_runs_multiply(const cmi_plan *p, const csr_operands<T> &A, const dot_request<T> &dot, int cache_policy, int xcd_swizzle, hipStream_t s);
+template <typename T> int csr16_multiply(const cmi_plan *p, const csr_operands<T> &A, const dot_request<T> &dot, int cache_policy, int xcd_swizzle, hipStream_t s);
 }

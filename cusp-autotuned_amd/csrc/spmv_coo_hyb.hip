@@ -433,8 +433,7 @@ static int spmv_coo(int dtype, int64_t rows, int64_t cols, int64_t nnz, const in
     if (rows == 0) return CMI_SUCCESS;
     // the tile kernel's ceiling (its entry positions are int), checked before the arrays when a plan-less call asks for it; a plan's
     // choice meets the same check below
-    if (!plan && user && user->kernel == CMI_COO_TILE && nnz > INT32_MAX - 4096 && reinterpret_cast<uintptr_t>(Ai) % 16 == 0 &&
-        reinterpret_cast<uintptr_t>(Aj) % 16 == 0 && reinterpret_cast<uintptr_t>(Ax) % 16 == 0)
+    if (!plan && user && user->kernel == CMI_COO_TILE && nnz > INT32_MAX - 4096 && aligned16(Ai, Aj, Ax))
         return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_coo: too many entries for the tile kernel");
     if (!y || (nnz > 0 && (!Ai || !Aj || !Ax || !x))) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_coo: null array");
     if (plan && plan->coo_csr_plan) { // sorted entries: the plan's row offsets + the CSR kernels (the row indices are not read)
@@ -447,19 +446,15 @@ static int spmv_coo(int dtype, int64_t rows, int64_t cols, int64_t nnz, const in
     if (c.kernel != CMI_COO_SEGMENTED && c.kernel != CMI_COO_LANE4 && c.kernel != CMI_COO_TILE)
         return fail(CMI_ERROR_NOT_SUPPORTED, "cmi_spmv_coo: config.kernel is not a COO kernel");
     hipStream_t s = as_stream(stream);
-    const bool aligned = reinterpret_cast<uintptr_t>(Ai) % 16 == 0 && reinterpret_cast<uintptr_t>(Aj) % 16 == 0 &&
-                         reinterpret_cast<uintptr_t>(Ax) % 16 == 0;
+    const bool aligned = aligned16(Ai, Aj, Ax);
     if (c.kernel == CMI_COO_TILE && aligned && nnz >= 4) { // sorted entries (a plan checked, or the caller's explicit config vouches)
         if (nnz > INT32_MAX - 4096) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_coo: too many entries for the tile kernel");
-        const int64_t tiles = ceil_div(nnz, kCooTile);
-        const int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
-        const int64_t tpx = ceil_div(tiles, kXcds);
-        const int64_t grid64 = padded_grid(tiles, swz);
-        if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_coo: grid too large");
+        tile_launch g;
+        if (int st = tile_launch_for(ceil_div(nnz, kCooTile), c.xcd_swizzle, "cmi_spmv_coo", &g)) return st;
         with_policy(c.nontemporal & 3, [&](auto P) {
             constexpr int POL = decltype(P)::value;
-            if (accumulate) hipLaunchKernelGGL((coo_tile_kernel<T, POL, true>), dim3((unsigned)grid64), dim3(kCooBlock), 0, s, rows, nnz, Ai, Aj, Ax, x, y, tiles, tpx, swz);
-            else            hipLaunchKernelGGL((coo_tile_kernel<T, POL, false>), dim3((unsigned)grid64), dim3(kCooBlock), 0, s, rows, nnz, Ai, Aj, Ax, x, y, tiles, tpx, swz);
+            if (accumulate) hipLaunchKernelGGL((coo_tile_kernel<T, POL, true>), dim3(g.grid), dim3(kCooBlock), 0, s, rows, nnz, Ai, Aj, Ax, x, y, g.tiles, g.tiles_per_xcd, g.swizzle);
+            else            hipLaunchKernelGGL((coo_tile_kernel<T, POL, false>), dim3(g.grid), dim3(kCooBlock), 0, s, rows, nnz, Ai, Aj, Ax, x, y, g.tiles, g.tiles_per_xcd, g.swizzle);
         });
         CMI_LAUNCH_CHECK("coo tile spmv");
         return CMI_SUCCESS;
@@ -633,10 +628,9 @@ int hyb_tile_starts(int64_t rows, int64_t coo_entries, const int *coo_Ai, int32_
 
 template <typename T>
 static int spmv_hyb_plan(const cmi_plan *plan, int dtype, int64_t pitch, const int *eAj, const T *eAx, const int *cAi,
-                         const int *cAj, const T *cAx, const T *x, T *y, int accumulate, void *stream,
-                         const T *wdot = nullptr, double *dot_partial = nullptr, int *dot_partials = nullptr)
+                         const int *cAj, const T *cAx, const T *x, T *y, int accumulate, void *stream, const dot_request<T> &d = {})
 {
-    if (dot_partials) *dot_partials = 0; // > 0: the one-launch kernel left that many partials of <y, wdot>
+    d.left(0);
     if (!plan || plan->format != CMI_FORMAT_HYB || plan->dtype != dtype)
         return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_hyb_plan: null plan, or a plan made for another format or value type");
     const int64_t rows = plan->rows, width = plan->hyb_width, coo = plan->hyb_coo;
@@ -651,25 +645,22 @@ static int spmv_hyb_plan(const cmi_plan *plan, int dtype, int64_t pitch, const i
     if (rows == 0) return CMI_SUCCESS;
     if (width > 0 && pitch < rows) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_hyb_plan: pitch < num_rows");
     if (!y || !x || (width > 0 && (!eAj || !eAx)) || !cAi || !cAj || !cAx) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_hyb_plan: null array");
-    const int64_t tiles = ceil_div(rows, kHybTileRows);
-    const int swz = plan->cfg.xcd_swizzle < 0 ? 0 : plan->cfg.xcd_swizzle;
-    const int64_t tpx = ceil_div(tiles, kXcds);
-    const int64_t grid64 = padded_grid(tiles, swz);
-    if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_hyb_plan: grid too large");
+    tile_launch g;
+    if (int st = tile_launch_for(ceil_div(rows, kHybTileRows), plan->cfg.xcd_swizzle, "cmi_spmv_hyb_plan", &g)) return st;
     hipStream_t s = as_stream(stream);
-    if (wdot && dot_partial && !accumulate && tiles <= kPartialCapacity) {
+    if (!accumulate && d.fits(g.tiles)) { // (the dot instance does not accumulate)
         with_policy(plan->cfg.nontemporal & 3, [&](auto P) {
             constexpr int POL = decltype(P)::value;
-            hipLaunchKernelGGL((hyb_tile_kernel<T, POL, false, true>), dim3((unsigned)grid64), dim3(kHybTileRows), 0, s, rows, (int)width, pitch, eAj, eAx, cAi, cAj, cAx, plan->hyb_tile_start.get(), x, y, tiles, tpx, swz, wdot, dot_partial);
+            hipLaunchKernelGGL((hyb_tile_kernel<T, POL, false, true>), dim3(g.grid), dim3(kHybTileRows), 0, s, rows, (int)width, pitch, eAj, eAx, cAi, cAj, cAx, plan->hyb_tile_start.get(), x, y, g.tiles, g.tiles_per_xcd, g.swizzle, d.w, d.partial);
         });
         CMI_LAUNCH_CHECK("hyb tile spmv dot");
-        if (dot_partials) *dot_partials = (int)tiles;
+        d.left(g.tiles);
         return CMI_SUCCESS;
     }
     with_policy(plan->cfg.nontemporal & 3, [&](auto P) {
         constexpr int POL = decltype(P)::value;
-        if (accumulate) hipLaunchKernelGGL((hyb_tile_kernel<T, POL, true>), dim3((unsigned)grid64), dim3(kHybTileRows), 0, s, rows, (int)width, pitch, eAj, eAx, cAi, cAj, cAx, plan->hyb_tile_start.get(), x, y, tiles, tpx, swz);
-        else            hipLaunchKernelGGL((hyb_tile_kernel<T, POL, false>), dim3((unsigned)grid64), dim3(kHybTileRows), 0, s, rows, (int)width, pitch, eAj, eAx, cAi, cAj, cAx, plan->hyb_tile_start.get(), x, y, tiles, tpx, swz);
+        if (accumulate) hipLaunchKernelGGL((hyb_tile_kernel<T, POL, true>), dim3(g.grid), dim3(kHybTileRows), 0, s, rows, (int)width, pitch, eAj, eAx, cAi, cAj, cAx, plan->hyb_tile_start.get(), x, y, g.tiles, g.tiles_per_xcd, g.swizzle);
+        else            hipLaunchKernelGGL((hyb_tile_kernel<T, POL, false>), dim3(g.grid), dim3(kHybTileRows), 0, s, rows, (int)width, pitch, eAj, eAx, cAi, cAj, cAx, plan->hyb_tile_start.get(), x, y, g.tiles, g.tiles_per_xcd, g.swizzle);
     });
     CMI_LAUNCH_CHECK("hyb tile spmv");
     return CMI_SUCCESS;
@@ -773,13 +764,10 @@ template <typename T>
 static int hyb_dot_plan(const cmi_plan *plan, int dtype, int64_t pitch, const int *eAj, const T *eAx, const int *cAi, const int *cAj,
                         const T *cAx, const T *x, T *y, const T *w, double *dot_dev, void *workspace, void *stream)
 {
-    if (!plan || (!w && plan->rows > 0) || !dot_dev || !workspace) return cmi::fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_hyb_dot_plan: null plan, w, result or workspace");
+    if (!plan || cmi::dot_args_missing(w, plan->rows, dot_dev, workspace)) return cmi::fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_hyb_dot_plan: null plan, w, result or workspace");
     int partials = 0;
-    const int st = cmi::spmv_hyb_plan<T>(plan, dtype, pitch, eAj, eAx, cAi, cAj, cAx, x, y, 0, stream, w, (double *)workspace, &partials);
-    if (st) return st;
-    if (partials > 0) return cmi::reduce_partials_f64(partials, (double *)workspace, dot_dev, cmi::as_stream(stream));
-    if constexpr (std::is_same<T, double>::value) return cmi_blas_dot_f64(plan->rows, y, w, dot_dev, workspace, stream);
-    else return cmi_blas_dotd_f32(plan->rows, y, w, dot_dev, workspace, stream);
+    if (int st = cmi::spmv_hyb_plan<T>(plan, dtype, pitch, eAj, eAx, cAi, cAj, cAx, x, y, 0, stream, {w, (double *)workspace, &partials})) return st;
+    return cmi::finish_dot(partials, plan->rows, y, w, dot_dev, workspace, stream);
 }
 CMI_API int cmi_spmv_hyb_dot_plan_f64(const cmi_plan *plan, int64_t ell_pitch, const int32_t *ell_Aj, const double *ell_Ax,
                                       const int32_t *coo_Ai, const int32_t *coo_Aj, const double *coo_Ax, const double *x,

@@ -1528,27 +1528,25 @@ static int dot_swizzle(int table_swizzle, const cmi_plan *plan)
 }
 
 template <typename T>
-static int launch_scalar(const cmi_config &c, int pol, hipStream_t s, int64_t rows, const int *Ap, const int *Aj, const T *Ax, const T *x,
-                         T *y, int accumulate)
+static int launch_scalar(const cmi_config &c, int pol, hipStream_t s, const csr_operands<T> &A)
 {
     const int block = c.block_size;
-    const int grid = grid_for(rows, block);
+    const int grid = grid_for(A.rows, block);
     with_policy(pol, [&](auto P) {
-        hipLaunchKernelGGL((csr_scalar_kernel<T, decltype(P)::value>), dim3(grid), dim3(block), 0, s, rows, Ap, Aj, Ax, x, y, accumulate);
+        hipLaunchKernelGGL((csr_scalar_kernel<T, decltype(P)::value>), dim3(grid), dim3(block), 0, s, A.rows, A.Ap, A.Aj, A.Ax, A.x, A.y, A.accumulate);
     });
     return CMI_SUCCESS;
 }
 
 template <typename T>
-static int launch_vector(const cmi_config &c, int pol, hipStream_t s, int64_t rows, const int *Ap, const int *Aj, const T *Ax, const T *x,
-                         T *y, int accumulate)
+static int launch_vector(const cmi_config &c, int pol, hipStream_t s, const csr_operands<T> &A)
 {
     const int block = c.block_size, tpr = c.threads_per_row;
-    const int grid = grid_for(rows * tpr, block);
+    const int grid = grid_for(A.rows * tpr, block);
     const bool launched = with_int<2, 4, 8, 16, 32, 64>(tpr, [&](auto TPR) {
         with_bool((pol & kPolLoadNT) != 0, [&](auto NT) {
-            hipLaunchKernelGGL((csr_vector_kernel<T, decltype(TPR)::value, decltype(NT)::value>), dim3(grid), dim3(block), 0, s, rows, Ap, Aj,
-                               Ax, x, y, accumulate);
+            hipLaunchKernelGGL((csr_vector_kernel<T, decltype(TPR)::value, decltype(NT)::value>), dim3(grid), dim3(block), 0, s, A.rows, A.Ap, A.Aj,
+                               A.Ax, A.x, A.y, A.accumulate);
         });
     });
     if (!launched) return fail(CMI_ERROR_NOT_SUPPORTED, "csr_vector: threads_per_row must be 2,4,8,16,32 or 64");
@@ -1557,9 +1555,9 @@ static int launch_vector(const cmi_config &c, int pol, hipStream_t s, int64_t ro
 
 template <typename T>
 static int launch_stream(const cmi_config &c, const cmi_config *user, const cmi_plan *plan, int64_t known_max_len, int pol, hipStream_t s,
-                         int64_t rows, int64_t nnz, const int *Ap, const int *Aj, const T *Ax, const T *x, T *y, int accumulate, const T *w,
-                         double *dot_partial, int *dot_partials)
+                         const csr_operands<T> &A, const dot_request<T> &d)
 {
+    const int64_t rows = A.rows, nnz = A.nnz;
     int rpb = c.rows_per_block;
     const int ipt = c.items_per_thread;
     // The fused <y, w> instance wants whole waves of rows: with the table's 176 rows per tile (2.75 waves) the dot costs
@@ -1567,7 +1565,8 @@ static int launch_stream(const cmi_config &c, const cmi_config *user, const cmi_
     // archive/profiles/r02_probe_dot_ablation.txt).  So a table-chosen shape (not a caller's explicit one) is rounded up to the
     // next multiple of 64 rows when the tile's single LDS pass still holds them.
     int block = c.block_size; // (the dot instance may widen it)
-    if (w && dot_partial && (!user || user->kernel == CMI_KERNEL_AUTO || user->rows_per_block == 0) && c.threads_per_row <= 1 && rows > 0) {
+    const bool table_rows = d.asked() && (!user || user->kernel == CMI_KERNEL_AUTO || user->rows_per_block == 0) && c.threads_per_row <= 1;
+    if (table_rows && rows > 0) {
         const int up = (rpb + kWave - 1) / kWave * kWave;
         const double mean = (double)nnz / (double)rows;
         const int64_t tile_entries = (int64_t)block * ipt * 4;
@@ -1575,7 +1574,7 @@ static int launch_stream(const cmi_config &c, const cmi_config *user, const cmi_
     }
     // ... and one partial per tile must fit the workspace: a table shape with small tiles (f32's 96 rows of 128 lanes at 10^7
     // rows: 104 000 tiles) is doubled -- lanes and rows together, the same fill of the LDS pass -- until it does
-    if (w && dot_partial && (!user || user->kernel == CMI_KERNEL_AUTO || user->rows_per_block == 0) && c.threads_per_row <= 1)
+    if (table_rows)
         while (ceil_div(rows, rpb) > kPartialCapacity && block * 2 <= 1024) { block *= 2; rpb *= 2; }
     int tpr = c.threads_per_row <= 1 ? 1 : c.threads_per_row;
     if (tpr > 64 || (tpr & (tpr - 1)) != 0) return fail(CMI_ERROR_NOT_SUPPORTED, "csr_stream: threads_per_row must be 0/1 or a power of two <= 64");
@@ -1583,19 +1582,16 @@ static int launch_stream(const cmi_config &c, const cmi_config *user, const cmi_
     // are streamed by the whole workgroup (re-associated); == 1: storage order for every row, whatever its length
     const int long_len = c.threads_per_row == 1 ? 0 : (tpr * kLongRowPerLane > kLongRowMin ? tpr * kLongRowPerLane : kLongRowMin);
     if (rpb < 1 || rpb > 4 * (block / tpr)) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream: rows_per_block must be in [1, 4*block_size/threads_per_row]");
-    const int64_t tiles = ceil_div(rows, rpb);
-    const int64_t tpx = ceil_div(tiles, kXcds);
-    int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
     // ... and its tiles go out in launch order: inside the solve that measured 2.3-3.5 us per iteration better than any chunk
     // dealing, for every tile shape (tools/cg_dot_shape_probe.py, archive/profiles/r02_cg_dot_shape.txt) -- stand-alone it is the
     // other way round (section 3.1 of DESIGN.md).  A caller's explicit shape is left alone.
-    if (w && dot_partial && (!user || user->kernel == CMI_KERNEL_AUTO)) swz = dot_swizzle(swz, plan);
-    const int64_t grid64 = swz == 0 ? tiles : swz == 1 ? tpx * kXcds : ceil_div(tiles, (int64_t)kXcds * swz) * kXcds * swz;
-    if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream: grid too large");
+    const bool dot_dealing = d.asked() && (!user || user->kernel == CMI_KERNEL_AUTO);
+    tile_launch g;
+    if (int st = tile_launch_for(ceil_div(rows, rpb), dot_dealing ? dot_swizzle(c.xcd_swizzle, plan) : c.xcd_swizzle, "csr_stream", &g)) return st;
     const size_t lds = (size_t)block * ipt * 4 * sizeof(T) + (size_t)(rpb + 1) * sizeof(int);
     if (lds > 160 * 1024) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream: tile does not fit 160 KiB of LDS");
-    const bool vec = (reinterpret_cast<uintptr_t>(Aj) % 16 == 0) && (reinterpret_cast<uintptr_t>(Ax) % 16 == 0);
-    const bool dot = w && dot_partial && vec && tiles <= kPartialCapacity;
+    const bool vec = aligned16(A.Aj, A.Ax);
+    const bool dot = vec && d.fits(g.tiles); // (the dot instance needs the 16-byte vector body)
     // the LONG instance only for a matrix whose plan shows such a row (no plan: the ordinary instance, which sums
     // any row, one lane or lane group at a time -- correct, slow on a long row)
     const bool lng = long_len > 0 && nnz >= long_len && known_max_len >= long_len;
@@ -1606,87 +1602,76 @@ static int launch_stream(const cmi_config &c, const cmi_config *user, const cmi_
             auto go = [&](auto VEC, auto DOT, auto LONG) {
                 hipLaunchKernelGGL((csr_stream_kernel<T, decltype(I)::value, decltype(VEC)::value, decltype(P)::value, decltype(DOT)::value,
                                                       decltype(LONG)::value>),
-                                   dim3((unsigned)grid64), dim3(block), lds, s, rows, nnz, Ap, Aj, Ax, x, y, rpb, tiles, tpx, swz, accumulate, tpr,
-                                   long_len, strided, w, dot_partial);
+                                   dim3(g.grid), dim3(block), lds, s, rows, nnz, A.Ap, A.Aj, A.Ax, A.x, A.y, rpb, g.tiles, g.tiles_per_xcd, g.swizzle,
+                                   A.accumulate, tpr, long_len, strided, d.w, d.partial);
             };
-            with_bool(lng, [&](auto LONG) { // (the dot instance needs the 16-byte vector body)
+            with_bool(lng, [&](auto LONG) {
                 if (dot) go(std::true_type(), std::true_type(), LONG);
                 else with_bool(vec, [&](auto VEC) { go(VEC, std::false_type(), LONG); });
             });
         });
     });
     if (!launched) return fail(CMI_ERROR_NOT_SUPPORTED, "csr_stream: items_per_thread must be 1, 2 or 4");
-    if (dot && dot_partials) *dot_partials = (int)tiles;
+    if (dot) d.left(g.tiles);
     return CMI_SUCCESS;
 }
 
 template <typename T>
-static int launch_wave(const cmi_config &c, const cmi_plan *plan, int pol, hipStream_t s, int64_t rows, const int *Ap,
-                       const int *Aj, const T *Ax, const T *x, T *y, int accumulate, const T *w, double *dot_partial, int *dot_partials)
+static int launch_wave(const cmi_config &c, const cmi_plan *plan, int pol, hipStream_t s, const csr_operands<T> &A, const dot_request<T> &d)
 {
     const int K = c.items_per_thread;
+    if (K < 2 || K > kWaveTileMaxK) return fail(CMI_ERROR_NOT_SUPPORTED, "csr_wave: items_per_thread (entries per lane) must be 2..10");
+    tile_launch g;
     if (plan && plan->wave_row_start) { // irregular short rows: the plan's partition (above)
-        if (K < 2 || K > kWaveTileMaxK) return fail(CMI_ERROR_NOT_SUPPORTED, "csr_wave: items_per_thread (entries per lane) must be 2..10");
-        const int64_t tiles = ceil_div(plan->wave_tiles, (int64_t)4);
-        const int64_t tpx = ceil_div(tiles, kXcds);
-        const int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
-        const int64_t grid64 = padded_grid(tiles, swz);
-        if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_wave: grid too large");
-        const bool dot = w && dot_partial && tiles <= kPartialCapacity;
+        if (int st = tile_launch_for(ceil_div(plan->wave_tiles, (int64_t)4), c.xcd_swizzle, "csr_wave", &g)) return st;
+        const bool dot = d.fits(g.tiles);
         with_policy(pol, [&](auto P) {
             with_int<2, 3, 4, 5, 6, 7, 8, 9, 10>(K, [&](auto KK) {
                 with_bool(dot, [&](auto DOT) {
-                    hipLaunchKernelGGL((csr_wavep_kernel<T, decltype(KK)::value, decltype(P)::value, decltype(DOT)::value>), dim3((unsigned)grid64),
-                                       dim3(256), 0, s, plan->wave_row_start.get(), plan->wave_tiles, Ap, Aj, Ax, x, y, tiles, tpx, swz, accumulate, w,
-                                       dot_partial);
+                    hipLaunchKernelGGL((csr_wavep_kernel<T, decltype(KK)::value, decltype(P)::value, decltype(DOT)::value>), dim3(g.grid),
+                                       dim3(256), 0, s, plan->wave_row_start.get(), plan->wave_tiles, A.Ap, A.Aj, A.Ax, A.x, A.y, g.tiles, g.tiles_per_xcd,
+                                       g.swizzle, A.accumulate, d.w, d.partial);
                 });
             });
         });
-        if (dot && dot_partials) *dot_partials = (int)tiles;
+        if (dot) d.left(g.tiles);
         return CMI_SUCCESS;
     }
     const int block = c.block_size, waves = block / kWave;
-    if (K < 2 || K > kWaveTileMaxK) return fail(CMI_ERROR_NOT_SUPPORTED, "csr_wave: items_per_thread (entries per lane) must be 2..10");
     if (c.rows_per_block < waves || c.rows_per_block % waves != 0 || c.rows_per_block / waves > kWave)
         return fail(CMI_ERROR_INVALID_VALUE, "csr_wave: rows_per_block must be block_size/64 waves x 1..64 rows each");
     const int rpw = c.rows_per_block / waves;
-    const int64_t tiles = ceil_div(rows, (int64_t)c.rows_per_block);
-    const int64_t tpx = ceil_div(tiles, kXcds);
     // (the wave-tile kernel keeps the table's chunk dealing inside a solve too: 239 against 243.5 us per CG iteration in launch
     //  order, archive/profiles/r02_cg_wave_dot.txt -- csr_stream's dot instance is the other way round)
-    const int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
-    const int64_t grid64 = padded_grid(tiles, swz);
-    if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_wave: grid too large");
+    if (int st = tile_launch_for(ceil_div(A.rows, (int64_t)c.rows_per_block), c.xcd_swizzle, "csr_wave", &g)) return st;
     const size_t lds = (size_t)block * K * sizeof(T);
     if (lds > 64 * 1024) return fail(CMI_ERROR_INVALID_VALUE, "csr_wave: block_size x items_per_thread products do not fit 64 KiB of LDS");
-    const bool dot = w && dot_partial && tiles <= kPartialCapacity;
+    const bool dot = d.fits(g.tiles);
     with_policy(pol, [&](auto P) {
         with_int<2, 3, 4, 5, 6, 7, 8, 9, 10>(K, [&](auto KK) {
             with_bool(dot, [&](auto DOT) {
-                hipLaunchKernelGGL((csr_wave_kernel<T, decltype(KK)::value, decltype(P)::value, decltype(DOT)::value>), dim3((unsigned)grid64),
-                                   dim3(block), lds, s, rows, Ap, Aj, Ax, x, y, rpw, tiles, tpx, swz, accumulate, w, dot_partial);
+                hipLaunchKernelGGL((csr_wave_kernel<T, decltype(KK)::value, decltype(P)::value, decltype(DOT)::value>), dim3(g.grid),
+                                   dim3(block), lds, s, A.rows, A.Ap, A.Aj, A.Ax, A.x, A.y, rpw, g.tiles, g.tiles_per_xcd, g.swizzle, A.accumulate, d.w,
+                                   d.partial);
             });
         });
     });
-    if (dot && dot_partials) *dot_partials = (int)tiles;
+    if (dot) d.left(g.tiles);
     return CMI_SUCCESS;
 }
 
 // wave-private tiles, 16-byte-vector body, on the plan's row partition
 template <typename T>
-static int launch_wavev(const cmi_config &c, const cmi_plan *plan, int pol, hipStream_t s, int64_t cols, int64_t nnz, const int *Ap, const int *Aj,
-                        const T *Ax, const T *x, T *y, int accumulate, const T *w, double *dot_partial, int *dot_partials)
+static int launch_wavev(const cmi_config &c, const cmi_plan *plan, int pol, hipStream_t s, const csr_operands<T> &A, const dot_request<T> &d)
 {
     const int V = c.items_per_thread;
+    const int64_t cols = A.cols;
     if (!plan || !plan->wave_row_start || plan->wave_q <= 0) return fail(CMI_ERROR_NOT_SUPPORTED, "CMI_CSR_STREAM_WAVEV runs through a plan (cmi_plan_create) only");
     if (V != 1 && V != 2 && V != 4) return fail(CMI_ERROR_NOT_SUPPORTED, "csr_wavev: items_per_thread (index vectors per lane) must be 1, 2 or 4");
-    if (reinterpret_cast<uintptr_t>(Aj) % 16 != 0 || reinterpret_cast<uintptr_t>(Ax) % 16 != 0) return fail(CMI_ERROR_INVALID_VALUE, "csr_wavev: Aj and Ax must be 16-byte aligned");
-    const int64_t tiles = ceil_div(plan->wave_tiles, (int64_t)4);
-    const int64_t tpx = ceil_div(tiles, kXcds);
-    const int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
-    const int64_t grid64 = padded_grid(tiles, swz);
-    if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_wavev: grid too large");
-    const bool dot = w && dot_partial && tiles <= kPartialCapacity;
+    if (!aligned16(A.Aj, A.Ax)) return fail(CMI_ERROR_INVALID_VALUE, "csr_wavev: Aj and Ax must be 16-byte aligned");
+    tile_launch g;
+    if (int st = tile_launch_for(ceil_div(plan->wave_tiles, (int64_t)4), c.xcd_swizzle, "csr_wavev", &g)) return st;
+    const bool dot = d.fits(g.tiles);
     // the exact longest row (max_row_length_kernel, measured with the partition): a tile of nr rows and nr * that many entries has only
     // rows of that length and takes its row bounds from the partition entry; 0 = every tile reads the row offsets
     const int uniform_len = plan->prof.max_len >= 1 && plan->prof.max_len <= INT32_MAX ? (int)plan->prof.max_len : 0;
@@ -1700,106 +1685,91 @@ static int launch_wavev(const cmi_config &c, const cmi_plan *plan, int pol, hipS
                 with_int<0, 1, 2>(columns_from, [&](auto CF) {
                     constexpr int cf = decltype(CF)::value;
                     hipLaunchKernelGGL((csr_wavev_kernel<T, decltype(VV)::value, decltype(P)::value, decltype(DOT)::value, cf >= 1, cf == 2>),
-                                       dim3((unsigned)grid64), dim3(256), 0, s, plan->wave_row_start.get(), plan->wave_tiles, nnz, Ap, Aj, Ax, x, y, tiles, tpx,
-                                       swz, accumulate, w, dot_partial, uniform_len, plan->wavev_cols16.get(), plan->wavev_base.get(), (int)(cols - 1),
-                                       plan->wavev_shift.get(), shift_div_mul(uniform_len > 0 ? uniform_len : 1));
+                                       dim3(g.grid), dim3(256), 0, s, plan->wave_row_start.get(), plan->wave_tiles, A.nnz, A.Ap, A.Aj, A.Ax, A.x, A.y, g.tiles,
+                                       g.tiles_per_xcd, g.swizzle, A.accumulate, d.w, d.partial, uniform_len, plan->wavev_cols16.get(), plan->wavev_base.get(),
+                                       (int)(cols - 1), plan->wavev_shift.get(), shift_div_mul(uniform_len > 0 ? uniform_len : 1));
                 });
             });
         });
     });
-    if (dot && dot_partials) *dot_partials = (int)tiles;
+    if (dot) d.left(g.tiles);
     return CMI_SUCCESS;
 }
 
 // csr_wavev + an x window in LDS per workgroup (gather-bound band matrices)
 template <typename T>
-static int launch_wavex(const cmi_config &c, const cmi_plan *plan, int pol, hipStream_t s, int64_t rows, int64_t cols, int64_t nnz,
-                        const int *Ap, const int *Aj, const T *Ax, const T *x, T *y, int accumulate, const T *w, double *dot_partial,
-                        int *dot_partials)
+static int launch_wavex(const cmi_config &c, const cmi_plan *plan, int pol, hipStream_t s, const csr_operands<T> &A, const dot_request<T> &d)
 {
     const int V = c.items_per_thread;
     if (!plan || !plan->wave_row_start || plan->wave_q <= 0) return fail(CMI_ERROR_NOT_SUPPORTED, "CMI_CSR_STREAM_WAVEX runs through a plan (cmi_plan_create) only");
     if (V != 2 && V != 4) return fail(CMI_ERROR_NOT_SUPPORTED, "csr_wavex: items_per_thread (index vectors per lane) must be 2 or 4");
-    if (reinterpret_cast<uintptr_t>(Aj) % 16 != 0 || reinterpret_cast<uintptr_t>(Ax) % 16 != 0 || reinterpret_cast<uintptr_t>(x) % 16 != 0)
-        return fail(CMI_ERROR_INVALID_VALUE, "csr_wavex: Aj, Ax and x must be 16-byte aligned");
+    if (!aligned16(A.Aj, A.Ax, A.x)) return fail(CMI_ERROR_INVALID_VALUE, "csr_wavex: Aj, Ax and x must be 16-byte aligned");
     const int xe = 16 / (int)sizeof(T);
     int window = c.rows_per_block > 0 ? c.rows_per_block : 4096; // (the config's rows_per_block field carries the window length for this kernel)
     window = (window + 256 * xe - 1) / (256 * xe) * (256 * xe);
     if (window > 8 * 256 * xe) window = 8 * 256 * xe;
-    const int64_t tiles = ceil_div(plan->wave_tiles, (int64_t)4);
-    const int64_t tpx = ceil_div(tiles, kXcds);
-    const int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
-    const int64_t grid64 = padded_grid(tiles, swz);
-    if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_wavex: grid too large");
+    tile_launch g;
+    if (int st = tile_launch_for(ceil_div(plan->wave_tiles, (int64_t)4), c.xcd_swizzle, "csr_wavex", &g)) return st;
     const size_t lds = ((size_t)window + (size_t)4 * kWave * V * 4) * sizeof(T);
-    const bool dot = w && dot_partial && tiles <= kPartialCapacity;
+    const bool dot = d.fits(g.tiles);
     with_policy(pol, [&](auto P) {
         with_int<2, 4>(V, [&](auto VV) {
             with_bool(dot, [&](auto DOT) {
-                hipLaunchKernelGGL((csr_wavex_kernel<T, decltype(VV)::value, decltype(P)::value, decltype(DOT)::value>), dim3((unsigned)grid64),
-                                   dim3(256), lds, s, plan->wave_row_start.get(), plan->wave_tiles, nnz, rows, cols, Ap, Aj, Ax, x, y, tiles, tpx, swz,
-                                   accumulate, window, w, dot_partial);
+                hipLaunchKernelGGL((csr_wavex_kernel<T, decltype(VV)::value, decltype(P)::value, decltype(DOT)::value>), dim3(g.grid),
+                                   dim3(256), lds, s, plan->wave_row_start.get(), plan->wave_tiles, A.nnz, A.rows, A.cols, A.Ap, A.Aj, A.Ax, A.x, A.y, g.tiles,
+                                   g.tiles_per_xcd, g.swizzle, A.accumulate, window, d.w, d.partial);
             });
         });
     });
-    if (dot && dot_partials) *dot_partials = (int)tiles;
+    if (dot) d.left(g.tiles);
     return CMI_SUCCESS;
 }
 
 // the plan's run-compressed column copy on wave tiles (spmv_csr_runs.hip); Aj is read by the array-tail fall-back only
 template <typename T>
-static int launch_runs(const cmi_config &c, const cmi_plan *plan, int pol, hipStream_t s, const int *Ap, const int *Aj, const T *Ax,
-                       const T *x, T *y, int accumulate, const T *w, double *dot_partial, int *dot_partials)
+static int launch_runs(const cmi_config &c, const cmi_plan *plan, int pol, hipStream_t s, const csr_operands<T> &A, const dot_request<T> &d)
 {
     if (!plan) return fail(CMI_ERROR_NOT_SUPPORTED, "CMI_CSR_STREAM_WAVER / _PACKED run through a plan of cmi_plan_create_csr only");
-    if (plan->csr16_packed) { // stencil-like rows: packed wave tiles of the 16-bit copy (spmv_csr16.hip); neither Ap nor Aj nor Ax is read
-        if constexpr (std::is_same<T, double>::value) return csr16_multiply_f64(plan, Ap, Ax, x, y, accumulate, s, w, dot_partial, dot_partials, pol, c.xcd_swizzle);
-        else return csr16_multiply_f32(plan, Ap, Ax, x, y, accumulate, s, w, dot_partial, dot_partials, pol, c.xcd_swizzle);
-    }
-    if constexpr (std::is_same<T, double>::value) return csr_runs_multiply_f64(plan, Ap, Aj, Ax, x, y, accumulate, s, w, dot_partial, dot_partials, pol, c.xcd_swizzle);
-    else return csr_runs_multiply_f32(plan, Ap, Aj, Ax, x, y, accumulate, s, w, dot_partial, dot_partials, pol, c.xcd_swizzle);
+    // stencil-like rows: packed wave tiles of the 16-bit copy (spmv_csr16.hip); neither Ap nor Aj nor Ax is read
+    if (plan->csr16_packed) return csr16_multiply(plan, A, d, pol, c.xcd_swizzle, s);
+    return csr_runs_multiply(plan, A, d, pol, c.xcd_swizzle, s);
 }
 
 // the plan's 16-bit column copy (spmv_csr16.hip); Aj itself is not read
 template <typename T>
-static int launch_c16(const cmi_config &c, const cmi_plan *plan, int pol, hipStream_t s, const int *Ap, const T *Ax, const T *x, T *y,
-                      int accumulate, const T *w, double *dot_partial, int *dot_partials)
+static int launch_c16(const cmi_config &c, const cmi_plan *plan, int pol, hipStream_t s, const csr_operands<T> &A, const dot_request<T> &d)
 {
     if (!plan || !plan->csr16_cols) return fail(CMI_ERROR_NOT_SUPPORTED, "CMI_CSR_STREAM_C16 runs through a plan of cmi_plan_create_csr only");
-    if (reinterpret_cast<uintptr_t>(Ax) % 16 != 0) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream_c16: values must be 16-byte aligned");
+    if (!aligned16(A.Ax)) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream_c16: values must be 16-byte aligned");
     // (the stream kernel of the copy deals its fused dot's tiles as csr_stream does; the wave-tiled copy keeps the table's dealing)
-    const int swz = w && dot_partial && plan->csr16_wave_k == 0 ? dot_swizzle(c.xcd_swizzle, plan) : c.xcd_swizzle;
-    if constexpr (std::is_same<T, double>::value) return csr16_multiply_f64(plan, Ap, Ax, x, y, accumulate, s, w, dot_partial, dot_partials, pol, swz);
-    else return csr16_multiply_f32(plan, Ap, Ax, x, y, accumulate, s, w, dot_partial, dot_partials, pol, swz);
+    return csr16_multiply(plan, A, d, pol, d.asked() && plan->csr16_wave_k == 0 ? dot_swizzle(c.xcd_swizzle, plan) : c.xcd_swizzle, s);
 }
 
 template <typename T>
-static int launch_pipe(const cmi_config &c, int pol, hipStream_t s, int64_t rows, int64_t nnz, const int *Ap, const int *Aj, const T *Ax,
-                       const T *x, T *y, int accumulate)
+static int launch_pipe(const cmi_config &c, int pol, hipStream_t s, const csr_operands<T> &A)
 {
     const int block = c.block_size, rpb = c.rows_per_block;
     if (rpb < 1 || rpb >= block) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream_pipe: rows_per_block must be in [1, block_size-1]");
-    const bool vec = (reinterpret_cast<uintptr_t>(Aj) % 16 == 0) && (reinterpret_cast<uintptr_t>(Ax) % 16 == 0);
-    if (!vec || nnz < 4) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream_pipe: needs 16-byte aligned Aj/Ax and >= 4 entries (use CMI_CSR_STREAM)");
-    const int64_t tiles = ceil_div(rows, rpb);
+    if (!aligned16(A.Aj, A.Ax) || A.nnz < 4) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream_pipe: needs 16-byte aligned Aj/Ax and >= 4 entries (use CMI_CSR_STREAM)");
+    const int64_t tiles = ceil_div(A.rows, rpb);
     const size_t lds = 2 * ((size_t)block * 4 * sizeof(T) + (size_t)block * sizeof(int));
     const int bpc = c.blocks_per_cu > 0 ? c.blocks_per_cu : 8;
     int64_t grid64 = (int64_t)kCus * bpc;
     if (grid64 > tiles) grid64 = tiles;
     const int chunked = c.xcd_swizzle != 0;
     with_policy(pol, [&](auto P) {
-        with_bool(accumulate != 0, [&](auto ACC) {
-            hipLaunchKernelGGL((csr_stream_pipe_kernel<T, decltype(P)::value, decltype(ACC)::value>), dim3((int)grid64), dim3(block), lds, s, rows,
-                               nnz, Ap, Aj, Ax, x, y, rpb, tiles, chunked);
+        with_bool(A.accumulate != 0, [&](auto ACC) {
+            hipLaunchKernelGGL((csr_stream_pipe_kernel<T, decltype(P)::value, decltype(ACC)::value>), dim3((int)grid64), dim3(block), lds, s, A.rows,
+                               A.nnz, A.Ap, A.Aj, A.Ax, A.x, A.y, rpb, tiles, chunked);
         });
     });
     return CMI_SUCCESS;
 }
 
 template <typename T>
-static int launch_balanced(const cmi_config &c, hipStream_t s, int64_t rows, int64_t nnz, const int *Ap, const int *Aj, const T *Ax,
-                           const T *x, T *y, int accumulate)
+static int launch_balanced(const cmi_config &c, hipStream_t s, const csr_operands<T> &A)
 {
+    const int64_t rows = A.rows, nnz = A.nnz;
     if (rows + nnz > ((int64_t)1 << 40)) return fail(CMI_ERROR_INVALID_VALUE, "csr_balanced: matrix too large");
     const int64_t tiles = ceil_div(rows + nnz, kBalItems);
     // A workgroup walks `per` consecutive tiles (one search of the row offsets, then tile ends chain) and the
@@ -1807,37 +1777,31 @@ static int launch_balanced(const cmi_config &c, hipStream_t s, int64_t rows, int
     // measured 2x faster than giving each of 2048 resident workgroups its own distant chunk (2048 DRAM fronts).
     // blocks_per_cu > 0 asks for that persistent shape instead (grid = CUs * blocks_per_cu).
     int64_t per = c.items_per_thread > 0 ? c.items_per_thread : 4;
-    int64_t grid64 = ceil_div(tiles, per);
+    int64_t chunks = ceil_div(tiles, per);
     if (c.blocks_per_cu > 0) {
-        grid64 = (int64_t)kCus * c.blocks_per_cu;
-        if (grid64 > tiles) grid64 = tiles;
-        per = ceil_div(tiles, grid64);
+        chunks = (int64_t)kCus * c.blocks_per_cu;
+        if (chunks > tiles) chunks = tiles;
+        per = ceil_div(tiles, chunks);
     }
-    const int64_t chunks = grid64;
-    const int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
-    const int64_t cpx = ceil_div(chunks, kXcds);
-    grid64 = padded_grid(chunks, swz);
-    if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_balanced: grid too large");
-    if (!accumulate) // rows split across tiles are completed with atomics: they start from zero
-        hipLaunchKernelGGL((zero_fill_kernel<T>), dim3((unsigned)ceil_div(rows, 256)), dim3(256), 0, s, rows, y);
-    const bool vec = (reinterpret_cast<uintptr_t>(Aj) % 16 == 0) && (reinterpret_cast<uintptr_t>(Ax) % 16 == 0);
-    with_bool(vec, [&](auto VEC) {
-        hipLaunchKernelGGL((csr_balanced_kernel<T, decltype(VEC)::value>), dim3((unsigned)grid64), dim3(kBalBlock), 0, s, rows, nnz, Ap, Aj, Ax,
-                           x, y, tiles, per, accumulate, chunks, cpx, swz);
+    tile_launch g; // (of the chunks: they, not the tiles, are dealt to the XCDs)
+    if (int st = tile_launch_for(chunks, c.xcd_swizzle, "csr_balanced", &g)) return st;
+    if (!A.accumulate) // rows split across tiles are completed with atomics: they start from zero
+        hipLaunchKernelGGL((zero_fill_kernel<T>), dim3((unsigned)ceil_div(rows, 256)), dim3(256), 0, s, rows, A.y);
+    with_bool(aligned16(A.Aj, A.Ax), [&](auto VEC) {
+        hipLaunchKernelGGL((csr_balanced_kernel<T, decltype(VEC)::value>), dim3(g.grid), dim3(kBalBlock), 0, s, rows, nnz, A.Ap, A.Aj, A.Ax,
+                           A.x, A.y, tiles, per, A.accumulate, g.tiles, g.tiles_per_xcd, g.swizzle);
     });
     return CMI_SUCCESS;
 }
 
 // `plan` (may be NULL): the matrix's resolved launch shape and row-length profile (plan.hip).  Without one the table's
 // row-tile kernel runs whatever the row lengths -- nothing is measured, allocated or waited for inside a multiply.
+// `d` (common.h dot_request): the caller wants <y, w> too.
 template <typename T>
-static int spmv_csr(int dtype, int64_t rows, int64_t cols, int64_t nnz, const int *Ap, const int *Aj, const T *Ax,
-                    const T *x, T *y, int accumulate, const cmi_config *user, void *stream, const T *w = nullptr,
-                    double *dot_partial = nullptr, int *dot_partials = nullptr, const cmi_plan *plan = nullptr)
+static int spmv_csr(int dtype, const csr_operands<T> &A, const cmi_config *user, void *stream, const dot_request<T> &d = {}, const cmi_plan *plan = nullptr)
 {
-    // w != nullptr: the caller wants <y, w> too.  *dot_partials = number of per-tile partials the kernel
-    // left in dot_partial, or 0 when the selected kernel cannot fuse it (the caller then runs a plain dot).
-    if (dot_partials) *dot_partials = 0;
+    const int64_t rows = A.rows, cols = A.cols, nnz = A.nnz;
+    d.left(0);
     if (rows < 0 || cols < 0 || nnz < 0) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_csr: negative size");
     // The ceiling: nnz <= INT32_MAX - 65536.  Every kernel keeps entry positions in int; the largest any lane forms is the last
     // entry plus one tile (csr_stream: 1024 x 4 x 4 = 16384; its long-row path: block x 4 = 4096; wave tiles: 64 x 10; wavev /
@@ -1846,7 +1810,7 @@ static int spmv_csr(int dtype, int64_t rows, int64_t cols, int64_t nnz, const in
     if (rows > INT32_MAX || cols > INT32_MAX || nnz > INT32_MAX - 65536)
         return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_csr: sizes exceed the int32 index type");
     if (rows == 0) return CMI_SUCCESS;
-    if (!Ap || !y || (nnz > 0 && (!Aj || !Ax || !x)))
+    if (!A.Ap || !A.y || (nnz > 0 && (!A.Aj || !A.Ax || !A.x)))
         return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_csr: null array");
     cmi_config c;
     int64_t known_max_len = -1; // the matrix's longest row: known only through a plan
@@ -1857,8 +1821,7 @@ static int spmv_csr(int dtype, int64_t rows, int64_t cols, int64_t nnz, const in
         // or x.  Arrays that are not 16-byte aligned (offset views, sliced tensors) then run the table's row-tile kernel, which takes any
         // alignment -- as they did before those kernels existed.  A kernel the caller ASKED for keeps its hard error below.
         if ((c.kernel == CMI_CSR_STREAM_WAVEV || c.kernel == CMI_CSR_STREAM_WAVEX || c.kernel == CMI_CSR_STREAM_WAVER) && !plan->kernel_asked) {
-            const bool aligned = reinterpret_cast<uintptr_t>(Aj) % 16 == 0 && reinterpret_cast<uintptr_t>(Ax) % 16 == 0 &&
-                                 (c.kernel != CMI_CSR_STREAM_WAVEX || reinterpret_cast<uintptr_t>(x) % 16 == 0);
+            const bool aligned = aligned16(A.Aj, A.Ax) && (c.kernel != CMI_CSR_STREAM_WAVEX || aligned16(A.x));
             if (!aligned) select_config(CMI_FORMAT_CSR, dtype, rows, cols, nnz, nullptr, &c);
         }
     } else {
@@ -1888,25 +1851,21 @@ static int spmv_csr(int dtype, int64_t rows, int64_t cols, int64_t nnz, const in
     // the y-store hint and load hints in the vector kernels measured no effect: r02_cg_y_store_policy.txt,
     // r02_cg_vector_load_policy.txt).  Only for a matrix that does not itself fit the cache: see select_config's residency rule,
     // tuning.hip.
-    if (w && dot_partial && nnz * (int64_t)(sizeof(int) + sizeof(T)) > kInfinityCacheBytes + kInfinityCacheBytes / 4) pol |= kPolLoadNT;
+    if (d.asked() && nnz * (int64_t)(sizeof(int) + sizeof(T)) > kInfinityCacheBytes + kInfinityCacheBytes / 4) pol |= kPolLoadNT;
 
     int st;
     switch (c.kernel) {
-    case CMI_CSR_SCALAR: st = launch_scalar(c, pol, s, rows, Ap, Aj, Ax, x, y, accumulate); break;
-    case CMI_CSR_VECTOR: st = launch_vector(c, pol, s, rows, Ap, Aj, Ax, x, y, accumulate); break;
-    case CMI_CSR_STREAM:
-        st = launch_stream(c, user, plan, known_max_len, pol, s, rows, nnz, Ap, Aj, Ax, x, y, accumulate, w, dot_partial, dot_partials);
-        break;
-    case CMI_CSR_STREAM_WAVE: st = launch_wave(c, plan, pol, s, rows, Ap, Aj, Ax, x, y, accumulate, w, dot_partial, dot_partials); break;
-    case CMI_CSR_STREAM_WAVEV: st = launch_wavev(c, plan, pol, s, cols, nnz, Ap, Aj, Ax, x, y, accumulate, w, dot_partial, dot_partials); break;
-    case CMI_CSR_STREAM_WAVEX:
-        st = launch_wavex(c, plan, pol, s, rows, cols, nnz, Ap, Aj, Ax, x, y, accumulate, w, dot_partial, dot_partials);
-        break;
+    case CMI_CSR_SCALAR: st = launch_scalar(c, pol, s, A); break;
+    case CMI_CSR_VECTOR: st = launch_vector(c, pol, s, A); break;
+    case CMI_CSR_STREAM: st = launch_stream(c, user, plan, known_max_len, pol, s, A, d); break;
+    case CMI_CSR_STREAM_WAVE: st = launch_wave(c, plan, pol, s, A, d); break;
+    case CMI_CSR_STREAM_WAVEV: st = launch_wavev(c, plan, pol, s, A, d); break;
+    case CMI_CSR_STREAM_WAVEX: st = launch_wavex(c, plan, pol, s, A, d); break;
     case CMI_CSR_STREAM_WAVER:
-    case CMI_CSR_STREAM_PACKED: return launch_runs(c, plan, pol, s, Ap, Aj, Ax, x, y, accumulate, w, dot_partial, dot_partials); // (checks its launch)
-    case CMI_CSR_STREAM_C16: return launch_c16(c, plan, pol, s, Ap, Ax, x, y, accumulate, w, dot_partial, dot_partials);         // (checks its launch)
-    case CMI_CSR_STREAM_PIPE: st = launch_pipe(c, pol, s, rows, nnz, Ap, Aj, Ax, x, y, accumulate); break;
-    case CMI_CSR_BALANCED: st = launch_balanced(c, s, rows, nnz, Ap, Aj, Ax, x, y, accumulate); break;
+    case CMI_CSR_STREAM_PACKED: return launch_runs(c, plan, pol, s, A, d); // (checks its launch)
+    case CMI_CSR_STREAM_C16: return launch_c16(c, plan, pol, s, A, d);     // (checks its launch)
+    case CMI_CSR_STREAM_PIPE: st = launch_pipe(c, pol, s, A); break;
+    case CMI_CSR_BALANCED: st = launch_balanced(c, s, A); break;
     default: return fail(CMI_ERROR_NOT_SUPPORTED, "cmi_spmv_csr: config.kernel is not a CSR kernel");
     }
     if (st) return st;
@@ -1920,13 +1879,13 @@ CMI_API int cmi_spmv_csr_f64(int64_t num_rows, int64_t num_cols, int64_t num_ent
                              const int32_t *Aj, const double *Ax, const double *x, double *y, int accumulate,
                              const cmi_config *cfg, void *stream)
 {
-    return cmi::spmv_csr<double>(CMI_F64, num_rows, num_cols, num_entries, Ap, Aj, Ax, x, y, accumulate, cfg, stream);
+    return cmi::spmv_csr<double>(CMI_F64, {num_rows, num_cols, num_entries, Ap, Aj, Ax, x, y, accumulate}, cfg, stream);
 }
 CMI_API int cmi_spmv_csr_f32(int64_t num_rows, int64_t num_cols, int64_t num_entries, const int32_t *Ap,
                              const int32_t *Aj, const float *Ax, const float *x, float *y, int accumulate,
                              const cmi_config *cfg, void *stream)
 {
-    return cmi::spmv_csr<float>(CMI_F32, num_rows, num_cols, num_entries, Ap, Aj, Ax, x, y, accumulate, cfg, stream);
+    return cmi::spmv_csr<float>(CMI_F32, {num_rows, num_cols, num_entries, Ap, Aj, Ax, x, y, accumulate}, cfg, stream);
 }
 
 namespace cmi {
@@ -1936,25 +1895,31 @@ static int plan_is_csr(const cmi_plan *plan, int dtype, const char *who)
     if (plan->format != CMI_FORMAT_CSR || plan->dtype != dtype) { set_error("%s: the plan was made for another format or value type", who); return CMI_ERROR_INVALID_VALUE; }
     return CMI_SUCCESS;
 }
+// the operands of a multiply through a plan: the sizes are the plan's
+template <typename T> static csr_operands<T> plan_operands(const cmi_plan *plan, const int *Ap, const int *Aj, const T *Ax, const T *x, T *y, int accumulate)
+{
+    return {plan->rows, plan->cols, plan->nnz, Ap, Aj, Ax, x, y, accumulate};
+}
 
 // y <- A x and *dot_dev <- <y, w> in one pass where the selected kernel can (csr_stream, aligned
 // arrays); otherwise the plain SpMV followed by the library's dot.  Either way deterministic.
 template <typename T>
-static int spmv_csr_dot(int dtype, int64_t rows, int64_t cols, int64_t nnz, const int *Ap, const int *Aj, const T *Ax, const T *x,
-                        T *y, const T *w, double *dot_dev, void *workspace, const cmi_config *cfg, void *stream, const cmi_plan *plan)
+static int spmv_csr_dot(int dtype, const csr_operands<T> &A, const T *w, double *dot_dev, void *workspace, const cmi_config *cfg, void *stream,
+                        const cmi_plan *plan)
 {
-    if ((!w && rows > 0) || !dot_dev || !workspace) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_csr_dot: null w, result or workspace");
+    if (dot_args_missing(w, A.rows, dot_dev, workspace)) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_csr_dot: null w, result or workspace");
     int partials = 0;
-    const int st = spmv_csr<T>(dtype, rows, cols, nnz, Ap, Aj, Ax, x, y, 0, cfg, stream, w, (double *)workspace, &partials, plan);
-    if (st) return st;
-    if (partials > 0) {
-        const int st2 = reduce_partials_f64(partials, (double *)workspace, dot_dev, as_stream(stream));
-        if (st2) return st2;
-        CMI_LAUNCH_CHECK("csr spmv dot");
-        return CMI_SUCCESS;
-    }
-    if constexpr (std::is_same<T, double>::value) return cmi_blas_dot_f64(rows, y, w, dot_dev, workspace, stream);
-    else return cmi_blas_dotd_f32(rows, y, w, dot_dev, workspace, stream);
+    if (int st = spmv_csr<T>(dtype, A, cfg, stream, {w, (double *)workspace, &partials}, plan)) return st;
+    return finish_dot(partials, A.rows, A.y, w, dot_dev, workspace, stream);
+}
+// y <- A x and the per-tile partials of <y, w> LEFT in the workspace (no fold): the fold rides at the front of
+// cmi_cg_update_fold_* (blas1.hip).  *npartials = their count, or 0 when the plan's kernel cannot fuse the dot (y is computed;
+// the caller then runs cmi_blas_dot_* and the plain cmi_cg_update_*).
+template <typename T>
+static int spmv_csr_dot_partials(int dtype, const cmi_plan *plan, const csr_operands<T> &A, const T *w, void *workspace, int *npartials, void *stream)
+{
+    if ((!w && A.rows > 0) || !workspace || !npartials) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_csr_dot_plan_partials: null w, workspace or count");
+    return spmv_csr<T>(dtype, A, nullptr, stream, {w, (double *)workspace, npartials}, plan);
 }
 } // namespace cmi
 
@@ -1962,56 +1927,51 @@ CMI_API int cmi_spmv_csr_plan_f64(const cmi_plan *plan, const int32_t *Ap, const
                                   const double *x, double *y, int accumulate, void *stream)
 {
     if (int st = cmi::plan_is_csr(plan, CMI_F64, "cmi_spmv_csr_plan_f64")) return st;
-    return cmi::spmv_csr<double>(CMI_F64, plan->rows, plan->cols, plan->nnz, Ap, Aj, Ax, x, y, accumulate, nullptr, stream, nullptr, nullptr, nullptr, plan);
+    return cmi::spmv_csr<double>(CMI_F64, cmi::plan_operands(plan, Ap, Aj, Ax, x, y, accumulate), nullptr, stream, {}, plan);
 }
 CMI_API int cmi_spmv_csr_plan_f32(const cmi_plan *plan, const int32_t *Ap, const int32_t *Aj, const float *Ax,
                                   const float *x, float *y, int accumulate, void *stream)
 {
     if (int st = cmi::plan_is_csr(plan, CMI_F32, "cmi_spmv_csr_plan_f32")) return st;
-    return cmi::spmv_csr<float>(CMI_F32, plan->rows, plan->cols, plan->nnz, Ap, Aj, Ax, x, y, accumulate, nullptr, stream, nullptr, nullptr, nullptr, plan);
+    return cmi::spmv_csr<float>(CMI_F32, cmi::plan_operands(plan, Ap, Aj, Ax, x, y, accumulate), nullptr, stream, {}, plan);
 }
 
 CMI_API int cmi_spmv_csr_dot_f64(int64_t num_rows, int64_t num_cols, int64_t num_entries, const int32_t *Ap,
                                  const int32_t *Aj, const double *Ax, const double *x, double *y, const double *w,
                                  double *dot_dev, void *workspace, const cmi_config *cfg, void *stream)
 {
-    return cmi::spmv_csr_dot<double>(CMI_F64, num_rows, num_cols, num_entries, Ap, Aj, Ax, x, y, w, dot_dev, workspace, cfg, stream, nullptr);
+    return cmi::spmv_csr_dot<double>(CMI_F64, {num_rows, num_cols, num_entries, Ap, Aj, Ax, x, y, 0}, w, dot_dev, workspace, cfg, stream, nullptr);
 }
 CMI_API int cmi_spmv_csr_dot_f32(int64_t num_rows, int64_t num_cols, int64_t num_entries, const int32_t *Ap,
                                  const int32_t *Aj, const float *Ax, const float *x, float *y, const float *w,
                                  double *dot_dev, void *workspace, const cmi_config *cfg, void *stream)
 {
-    return cmi::spmv_csr_dot<float>(CMI_F32, num_rows, num_cols, num_entries, Ap, Aj, Ax, x, y, w, dot_dev, workspace, cfg, stream, nullptr);
+    return cmi::spmv_csr_dot<float>(CMI_F32, {num_rows, num_cols, num_entries, Ap, Aj, Ax, x, y, 0}, w, dot_dev, workspace, cfg, stream, nullptr);
 }
 CMI_API int cmi_spmv_csr_dot_plan_f64(const cmi_plan *plan, const int32_t *Ap, const int32_t *Aj, const double *Ax,
                                       const double *x, double *y, const double *w, double *dot_dev, void *workspace, void *stream)
 {
     if (int st = cmi::plan_is_csr(plan, CMI_F64, "cmi_spmv_csr_dot_plan_f64")) return st;
-    return cmi::spmv_csr_dot<double>(CMI_F64, plan->rows, plan->cols, plan->nnz, Ap, Aj, Ax, x, y, w, dot_dev, workspace, nullptr, stream, plan);
+    return cmi::spmv_csr_dot<double>(CMI_F64, cmi::plan_operands(plan, Ap, Aj, Ax, x, y, 0), w, dot_dev, workspace, nullptr, stream, plan);
 }
 CMI_API int cmi_spmv_csr_dot_plan_f32(const cmi_plan *plan, const int32_t *Ap, const int32_t *Aj, const float *Ax,
                                       const float *x, float *y, const float *w, double *dot_dev, void *workspace, void *stream)
 {
     if (int st = cmi::plan_is_csr(plan, CMI_F32, "cmi_spmv_csr_dot_plan_f32")) return st;
-    return cmi::spmv_csr_dot<float>(CMI_F32, plan->rows, plan->cols, plan->nnz, Ap, Aj, Ax, x, y, w, dot_dev, workspace, nullptr, stream, plan);
+    return cmi::spmv_csr_dot<float>(CMI_F32, cmi::plan_operands(plan, Ap, Aj, Ax, x, y, 0), w, dot_dev, workspace, nullptr, stream, plan);
 }
 
-// y <- A x and the per-tile partials of <y, w> LEFT in the workspace (no fold): the fold rides at the front of
-// cmi_cg_update_fold_* (blas1.hip).  *npartials = their count, or 0 when the plan's kernel cannot fuse the dot (y is computed;
-// the caller then runs cmi_blas_dot_* and the plain cmi_cg_update_*).
 CMI_API int cmi_spmv_csr_dot_plan_partials_f64(const cmi_plan *plan, const int32_t *Ap, const int32_t *Aj, const double *Ax,
                                                const double *x, double *y, const double *w, void *workspace, int *npartials, void *stream)
 {
     if (int st = cmi::plan_is_csr(plan, CMI_F64, "cmi_spmv_csr_dot_plan_partials_f64")) return st;
-    if ((!w && plan->rows > 0) || !workspace || !npartials) return cmi::fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_csr_dot_plan_partials: null w, workspace or count");
-    return cmi::spmv_csr<double>(CMI_F64, plan->rows, plan->cols, plan->nnz, Ap, Aj, Ax, x, y, 0, nullptr, stream, w, (double *)workspace, npartials, plan);
+    return cmi::spmv_csr_dot_partials<double>(CMI_F64, plan, cmi::plan_operands(plan, Ap, Aj, Ax, x, y, 0), w, workspace, npartials, stream);
 }
 CMI_API int cmi_spmv_csr_dot_plan_partials_f32(const cmi_plan *plan, const int32_t *Ap, const int32_t *Aj, const float *Ax,
                                                const float *x, float *y, const float *w, void *workspace, int *npartials, void *stream)
 {
     if (int st = cmi::plan_is_csr(plan, CMI_F32, "cmi_spmv_csr_dot_plan_partials_f32")) return st;
-    if ((!w && plan->rows > 0) || !workspace || !npartials) return cmi::fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_csr_dot_plan_partials: null w, workspace or count");
-    return cmi::spmv_csr<float>(CMI_F32, plan->rows, plan->cols, plan->nnz, Ap, Aj, Ax, x, y, 0, nullptr, stream, w, (double *)workspace, npartials, plan);
+    return cmi::spmv_csr_dot_partials<float>(CMI_F32, plan, cmi::plan_operands(plan, Ap, Aj, Ax, x, y, 0), w, workspace, npartials, stream);
 }
 
 // Longest row of a CSR matrix (device pass + read-back; synchronises the stream).  A plan does this itself;

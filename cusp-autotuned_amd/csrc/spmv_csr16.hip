@@ -417,88 +417,57 @@ csr_stream16_kernel(int64_t num_rows, int64_t num_entries, int num_cols, const i
 }
 
 template <typename T>
-static int csr16_multiply(const cmi_plan *p, const int *Ap, const T *Ax, const T *x, T *y, int accumulate, hipStream_t s,
-                          const T *w, double *dot_partial, int *dot_partials, int pol, int swizzle)
+int csr16_multiply(const cmi_plan *p, const csr_operands<T> &A, const dot_request<T> &d, int pol, int swizzle, hipStream_t s)
 {
     const cmi_config &c = p->cfg;
     const int block = c.block_size, ipt = c.items_per_thread, rpb = c.rows_per_block;
     const int64_t rows = p->rows, nnz = p->nnz;
-    if (p->csr16_packed) { // CMI_CSR_STREAM_PACKED on stencil-like rows: packed wave tiles (above); Ap / Ax are not read
+    tile_launch g;
+    if (p->csr16_wave_k > 0) { // the copy is tiled per wave: the wave-tile kernels, four waves (four tiles of the copy) per workgroup
+        const bool packed = (bool)p->csr16_packed; // CMI_CSR_STREAM_PACKED on stencil-like rows: packed wave tiles (above); Ap / Ax are not read
         const int K = p->csr16_wave_k, wblock = 256;
-        const int64_t wtiles = ceil_div(rows, (int64_t)wblock);
-        const int64_t wtpx = ceil_div(wtiles, kXcds);
-        const int wswz = swizzle < 0 ? 0 : swizzle;
-        const int64_t wgrid = padded_grid(wtiles, wswz);
-        if (wgrid > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream_packed: grid too large");
+        if (int st = tile_launch_for(ceil_div(rows, (int64_t)wblock), swizzle, packed ? "csr_stream_packed" : "csr_stream_c16", &g)) return st;
         const size_t wlds = (size_t)wblock * K * sizeof(T);
-        const bool wdot = w && dot_partial && wtiles <= kPartialCapacity;
+        const bool wdot = d.fits(g.tiles);
         with_policy(pol, [&](auto P) {
             with_int<2, 3, 4, 5, 6, 7, 8, 9, 10>(K, [&](auto KK) { // (csr16_wave_k: the longest row, 2..10, plan.hip wave_tiles_fit)
                 with_bool(wdot, [&](auto DOT) {
-                    hipLaunchKernelGGL((csr_wave16p_kernel<T, decltype(KK)::value, decltype(P)::value, decltype(DOT)::value>), dim3((unsigned)wgrid), dim3(wblock),
-                                       wlds, s, rows, p->csr16_packed.get(), x, y, wtiles, wtpx, wswz, accumulate, w, dot_partial);
+                    if (packed)
+                        hipLaunchKernelGGL((csr_wave16p_kernel<T, decltype(KK)::value, decltype(P)::value, decltype(DOT)::value>), dim3(g.grid), dim3(wblock),
+                                           wlds, s, rows, p->csr16_packed.get(), A.x, A.y, g.tiles, g.tiles_per_xcd, g.swizzle, A.accumulate, d.w, d.partial);
+                    else
+                        hipLaunchKernelGGL((csr_wave16_kernel<T, decltype(KK)::value, decltype(P)::value, decltype(DOT)::value>), dim3(g.grid), dim3(wblock),
+                                           wlds, s, rows, A.Ap, p->csr16_cols.get(), p->csr16_base.get(), A.Ax, A.x, A.y, g.tiles, g.tiles_per_xcd, g.swizzle,
+                                           A.accumulate, d.w, d.partial);
                 });
             });
         });
-        CMI_LAUNCH_CHECK("csr_wave16p spmv");
-        if (wdot && dot_partials) *dot_partials = (int)wtiles;
+        if (packed) CMI_LAUNCH_CHECK("csr_wave16p spmv");
+        else CMI_LAUNCH_CHECK("csr_wave16 spmv");
+        if (wdot) d.left(g.tiles);
         return CMI_SUCCESS;
     }
-    if (p->csr16_wave_k > 0) { // the copy is tiled per wave: the wave-tile kernel, four waves (four tiles of the copy) per workgroup
-        const int K = p->csr16_wave_k, wblock = 256;
-        const int64_t wtiles = ceil_div(rows, (int64_t)wblock);
-        const int64_t wtpx = ceil_div(wtiles, kXcds);
-        const int wswz = swizzle < 0 ? 0 : swizzle;
-        const int64_t wgrid = padded_grid(wtiles, wswz);
-        if (wgrid > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream_c16: grid too large");
-        const size_t wlds = (size_t)wblock * K * sizeof(T);
-        const bool wdot = w && dot_partial && wtiles <= kPartialCapacity;
-        with_policy(pol, [&](auto P) {
-            with_int<2, 3, 4, 5, 6, 7, 8, 9, 10>(K, [&](auto KK) { // (csr16_wave_k: the longest row, 2..10, plan.hip wave_tiles_fit)
-                with_bool(wdot, [&](auto DOT) {
-                    hipLaunchKernelGGL((csr_wave16_kernel<T, decltype(KK)::value, decltype(P)::value, decltype(DOT)::value>), dim3((unsigned)wgrid), dim3(wblock),
-                                       wlds, s, rows, Ap, p->csr16_cols.get(), p->csr16_base.get(), Ax, x, y, wtiles, wtpx, wswz, accumulate, w, dot_partial);
-                });
-            });
-        });
-        CMI_LAUNCH_CHECK("csr_wave16 spmv");
-        if (wdot && dot_partials) *dot_partials = (int)wtiles;
-        return CMI_SUCCESS;
-    }
-    const int64_t tiles = ceil_div(rows, rpb);
-    const int64_t tpx = ceil_div(tiles, kXcds);
-    const int swz = swizzle < 0 ? 0 : swizzle;
-    const int64_t grid64 = padded_grid(tiles, swz);
-    if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream_c16: grid too large");
+    if (int st = tile_launch_for(ceil_div(rows, rpb), swizzle, "csr_stream_c16", &g)) return st;
     const size_t lds = (size_t)block * ipt * 4 * sizeof(T);
     if (lds > 160 * 1024) return fail(CMI_ERROR_INVALID_VALUE, "csr_stream_c16: tile does not fit 160 KiB of LDS");
-    const bool dot = w && dot_partial && tiles <= kPartialCapacity;
+    const bool dot = d.fits(g.tiles);
     const int strided = (c.nontemporal & kPolStrided) != 0;
     bool launched = false;
     with_policy(pol, [&](auto P) {
         launched = with_int<1, 2, 4>(ipt, [&](auto I) {
             with_bool(dot, [&](auto DOT) {
-                hipLaunchKernelGGL((csr_stream16_kernel<T, decltype(I)::value, decltype(P)::value, decltype(DOT)::value>), dim3((unsigned)grid64),
-                                   dim3(block), lds, s, rows, nnz, (int)p->cols, Ap, p->csr16_cols.get(), p->csr16_base.get(), Ax, x, y, rpb, tiles, tpx, swz,
-                                   accumulate, strided, w, dot_partial);
+                hipLaunchKernelGGL((csr_stream16_kernel<T, decltype(I)::value, decltype(P)::value, decltype(DOT)::value>), dim3(g.grid),
+                                   dim3(block), lds, s, rows, nnz, (int)p->cols, A.Ap, p->csr16_cols.get(), p->csr16_base.get(), A.Ax, A.x, A.y, rpb, g.tiles,
+                                   g.tiles_per_xcd, g.swizzle, A.accumulate, strided, d.w, d.partial);
             });
         });
     });
     if (!launched) return fail(CMI_ERROR_NOT_SUPPORTED, "csr_stream_c16: items_per_thread must be 1, 2 or 4");
     CMI_LAUNCH_CHECK("csr_stream_c16 spmv");
-    if (dot && dot_partials) *dot_partials = (int)tiles;
+    if (dot) d.left(g.tiles);
     return CMI_SUCCESS;
 }
-
-int csr16_multiply_f64(const cmi_plan *p, const int *Ap, const double *Ax, const double *x, double *y, int accumulate,
-                       hipStream_t s, const double *w, double *dot_partial, int *dot_partials, int pol, int swizzle)
-{
-    return csr16_multiply<double>(p, Ap, Ax, x, y, accumulate, s, w, dot_partial, dot_partials, pol, swizzle);
-}
-int csr16_multiply_f32(const cmi_plan *p, const int *Ap, const float *Ax, const float *x, float *y, int accumulate,
-                       hipStream_t s, const float *w, double *dot_partial, int *dot_partials, int pol, int swizzle)
-{
-    return csr16_multiply<float>(p, Ap, Ax, x, y, accumulate, s, w, dot_partial, dot_partials, pol, swizzle);
-}
+template int csr16_multiply<double>(const cmi_plan *, const csr_operands<double> &, const dot_request<double> &, int, int, hipStream_t);
+template int csr16_multiply<float>(const cmi_plan *, const csr_operands<float> &, const dot_request<float> &, int, int, hipStream_t);
 
 } // namespace cmi

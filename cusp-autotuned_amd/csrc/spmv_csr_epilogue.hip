@@ -140,7 +140,7 @@ template <typename T, int FORM>
 static int epilogue_launch(int64_t rows, const int *Ap, const int *Aj, const T *Ax, const T *x, T p0, T p1, const T *u, const T *v, T *out,
                            void *stream)
 {
-    const bool vec = reinterpret_cast<uintptr_t>(Aj) % 16 == 0 && reinterpret_cast<uintptr_t>(Ax) % 16 == 0;
+    const bool vec = aligned16(Aj, Ax);
     const dim3 grid((unsigned)ceil_div(rows, kEpiBlock)); // rows <= INT32_MAX
     with_bool(vec, [&](auto VEC) {
         hipLaunchKernelGGL((csr_epilogue_kernel<T, FORM, decltype(VEC)::value>), grid, dim3(kEpiBlock), 0, as_stream(stream), rows, Ap, Aj, Ax,

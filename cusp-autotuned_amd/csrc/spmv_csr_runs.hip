@@ -427,47 +427,34 @@ csr_waver_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t 
 }
 
 template <typename T>
-static int csr_runs_multiply(const cmi_plan *p, const int *Ap, const int *Aj, const T *Ax, const T *x, T *y, int accumulate, hipStream_t s,
-                             const T *w, double *dot_partial, int *dot_partials, int pol, int swz_in)
+int csr_runs_multiply(const cmi_plan *p, const csr_operands<T> &A, const dot_request<T> &d, int pol, int swizzle, hipStream_t s)
 {
     if (!p->runs_start || !p->runs_pieces) return fail(CMI_ERROR_NOT_SUPPORTED, "CMI_CSR_STREAM_WAVER / _PACKED run through a plan of cmi_plan_create_csr only");
     const bool packed = p->cfg.kernel == CMI_CSR_STREAM_PACKED;
     if (packed && !p->runs_packed) return fail(CMI_ERROR_NOT_SUPPORTED, "CMI_CSR_STREAM_PACKED: the plan holds no packed copy (cmi_plan_create_csr_values)");
-    if (!packed && reinterpret_cast<uintptr_t>(Ax) % 16 != 0) return fail(CMI_ERROR_INVALID_VALUE, "csr_waver: Ax must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(x) % sizeof(T) != 0) return fail(CMI_ERROR_INVALID_VALUE, "csr_waver: x must be aligned to its element size");
+    if (!packed && !aligned16(A.Ax)) return fail(CMI_ERROR_INVALID_VALUE, "csr_waver: Ax must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(A.x) % sizeof(T) != 0) return fail(CMI_ERROR_INVALID_VALUE, "csr_waver: x must be aligned to its element size");
     const int V = p->cfg.items_per_thread;
     if (V != 1 && V != 2 && V != 4) return fail(CMI_ERROR_NOT_SUPPORTED, "csr_waver: items_per_thread must be 1, 2 or 4");
-    const int64_t tiles = ceil_div(p->wave_tiles, (int64_t)4);
-    const int64_t tpx = ceil_div(tiles, kXcds);
-    const int swz = swz_in < 0 ? 0 : swz_in;
-    const int64_t grid64 = padded_grid(tiles, swz);
-    if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "csr_waver: grid too large");
-    const bool dot = w && dot_partial && tiles <= kPartialCapacity;
+    tile_launch g;
+    if (int st = tile_launch_for(ceil_div(p->wave_tiles, (int64_t)4), swizzle, "csr_waver", &g)) return st;
+    const bool dot = d.fits(g.tiles);
     with_policy(pol, [&](auto P) {
         with_int<1, 2, 4>(V, [&](auto VV) {
             with_bool(packed, [&](auto PK) {
                 with_bool(dot, [&](auto DOT) {
                     hipLaunchKernelGGL((csr_waver_kernel<T, decltype(VV)::value, decltype(P)::value, decltype(DOT)::value, decltype(PK)::value>),
-                                       dim3((unsigned)grid64), dim3(256), 0, s, p->runs_start.get(), p->wave_tiles, p->nnz, (int)p->cols, Ap, Aj, p->runs_pieces.get(),
-                                       Ax, p->runs_packed.get(), x, y, tiles, tpx, swz, accumulate, w, dot_partial);
+                                       dim3(g.grid), dim3(256), 0, s, p->runs_start.get(), p->wave_tiles, p->nnz, (int)p->cols, A.Ap, A.Aj, p->runs_pieces.get(),
+                                       A.Ax, p->runs_packed.get(), A.x, A.y, g.tiles, g.tiles_per_xcd, g.swizzle, A.accumulate, d.w, d.partial);
                 });
             });
         });
     });
-    if (dot && dot_partials) *dot_partials = (int)tiles;
     CMI_LAUNCH_CHECK("csr_waver");
+    if (dot) d.left(g.tiles);
     return CMI_SUCCESS;
 }
-
-int csr_runs_multiply_f64(const cmi_plan *p, const int *Ap, const int *Aj, const double *Ax, const double *x, double *y, int accumulate, hipStream_t s,
-                          const double *w, double *dot_partial, int *dot_partials, int pol, int swz)
-{
-    return csr_runs_multiply<double>(p, Ap, Aj, Ax, x, y, accumulate, s, w, dot_partial, dot_partials, pol, swz);
-}
-int csr_runs_multiply_f32(const cmi_plan *p, const int *Ap, const int *Aj, const float *Ax, const float *x, float *y, int accumulate, hipStream_t s,
-                          const float *w, double *dot_partial, int *dot_partials, int pol, int swz)
-{
-    return csr_runs_multiply<float>(p, Ap, Aj, Ax, x, y, accumulate, s, w, dot_partial, dot_partials, pol, swz);
-}
+template int csr_runs_multiply<double>(const cmi_plan *, const csr_operands<double> &, const dot_request<double> &, int, int, hipStream_t);
+template int csr_runs_multiply<float>(const cmi_plan *, const csr_operands<float> &, const dot_request<float> &, int, int, hipStream_t);
 
 } // namespace cmi

@@ -330,10 +330,9 @@ dia_row2_kernel(int64_t num_rows, int64_t num_cols, int num_diagonals, int64_t p
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 static int spmv_ell(int dtype, int64_t rows, int64_t cols, int64_t width, int64_t pitch, const int *Aj, const T *Ax,
-                    const int *row_lengths, const T *x, T *y, int accumulate, const cmi_config *user, void *stream,
-                    const T *wdot = nullptr, double *dot_partial = nullptr, int *dot_partials = nullptr)
+                    const int *row_lengths, const T *x, T *y, int accumulate, const cmi_config *user, void *stream, const dot_request<T> &d = {})
 {
-    if (dot_partials) *dot_partials = 0; // > 0: the kernel left that many partials of <y, wdot> in dot_partial
+    d.left(0);
     if (rows < 0 || cols < 0 || width < 0) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_ell: negative size");
     if (rows > INT32_MAX || cols > INT32_MAX || width > INT32_MAX)
         return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_ell: sizes exceed the int32 index type");
@@ -353,11 +352,9 @@ static int spmv_ell(int dtype, int64_t rows, int64_t cols, int64_t width, int64_
     if (rpl == 2 && !(pitch % 2 == 0 && reinterpret_cast<uintptr_t>(Aj) % 8 == 0 &&
                       reinterpret_cast<uintptr_t>(Ax) % (2 * sizeof(T)) == 0))
         rpl = 1;
-    // a fused dot leaves one partial per workgroup: widen the workgroups until they fit the workspace
-    if (wdot && dot_partial)
-        while (block < 1024 && ceil_div(rows, (int64_t)block * rpl) > kPartialCapacity) block *= 2;
+    if (d.asked()) block = widen_block_for_partials(block, rows, rpl);
     const int lanes = ell_lanes_per_row(c, rows, width);
-    if (lanes > 1) { // (a fused dot falls back to the separate dot: *dot_partials stays 0)
+    if (lanes > 1) { // (a fused dot falls back to the separate dot: the count stays 0)
         const int R = block / lanes;
         const int64_t g64 = ceil_div(rows, (int64_t)R);
         if (g64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_ell: grid too large");
@@ -373,40 +370,32 @@ static int spmv_ell(int dtype, int64_t rows, int64_t cols, int64_t width, int64_
         CMI_LAUNCH_CHECK("ell slices spmv");
         return CMI_SUCCESS;
     }
-    const int64_t tiles = ceil_div(rows, (int64_t)block * rpl); // one-shot grid (see spmv_csr.hip grid_for), padded to chunk rounds
-    const int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
-    const int64_t tpx = ceil_div(tiles, kXcds);
-    const int64_t grid64 = padded_grid(tiles, swz);
-    if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_ell: grid too large");
-    const int grid = (int)grid64;
+    tile_launch g; // one-shot grid (see spmv_csr.hip grid_for), padded to chunk rounds
+    if (int st = tile_launch_for(ceil_div(rows, (int64_t)block * rpl), c.xcd_swizzle, "cmi_spmv_ell", &g)) return st;
     const int w = (int)width;
-    const bool dot = wdot && dot_partial && tiles <= kPartialCapacity; // one partial per tile (a double, whatever T)
+    const bool dot = d.fits(g.tiles); // one partial per tile (a double, whatever T)
     with_policy(pol, [&](auto P) {
         with_int<1, 2>(rpl, [&](auto RPL) {
             with_bool(ellr, [&](auto ELLR) {
                 with_bool(dot, [&](auto DOT) {
                     hipLaunchKernelGGL((ell_row_kernel<T, decltype(RPL)::value, decltype(ELLR)::value, decltype(P)::value, decltype(DOT)::value>),
-                                       dim3(grid), dim3(block), 0, s, rows, w, pitch, Aj, Ax, row_lengths, x, y, accumulate, tiles, tpx, swz, wdot,
-                                       dot_partial);
+                                       dim3(g.grid), dim3(block), 0, s, rows, w, pitch, Aj, Ax, row_lengths, x, y, accumulate, g.tiles, g.tiles_per_xcd,
+                                       g.swizzle, d.w, d.partial);
                 });
             });
         });
     });
-    if (dot) {
-        CMI_LAUNCH_CHECK("ell spmv dot");
-        if (dot_partials) *dot_partials = (int)tiles;
-        return CMI_SUCCESS;
-    }
-    CMI_LAUNCH_CHECK("ell spmv");
+    if (dot) CMI_LAUNCH_CHECK("ell spmv dot");
+    else CMI_LAUNCH_CHECK("ell spmv");
+    if (dot) d.left(g.tiles);
     return CMI_SUCCESS;
 }
 
 template <typename T>
 static int spmv_dia(int dtype, int64_t rows, int64_t cols, int64_t ndiag, int64_t pitch, const int *offsets,
-                    const T *vals, const T *x, T *y, int accumulate, const cmi_config *user, void *stream,
-                    const T *wdot = nullptr, double *dot_partial = nullptr, int *dot_partials = nullptr)
+                    const T *vals, const T *x, T *y, int accumulate, const cmi_config *user, void *stream, const dot_request<T> &d = {})
 {
-    if (dot_partials) *dot_partials = 0;
+    d.left(0);
     if (rows < 0 || cols < 0 || ndiag < 0) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_dia: negative size");
     if (rows > INT32_MAX || cols > INT32_MAX || ndiag > INT32_MAX)
         return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_dia: sizes exceed the int32 index type");
@@ -421,26 +410,43 @@ static int spmv_dia(int dtype, int64_t rows, int64_t cols, int64_t ndiag, int64_
     const int pol = c.nontemporal & 3;
     int rpl = c.items_per_thread >= 2 ? 2 : 1;
     if (rpl == 2 && !(pitch % 2 == 0 && reinterpret_cast<uintptr_t>(vals) % (2 * sizeof(T)) == 0)) rpl = 1;
-    if (wdot && dot_partial) // one partial per workgroup: widen the workgroups until they fit the workspace
-        while (block < 1024 && ceil_div(rows, (int64_t)block * rpl) > kPartialCapacity) block *= 2;
-    const int64_t tiles = ceil_div(rows, (int64_t)block * rpl);
-    const int swz = c.xcd_swizzle < 0 ? 0 : c.xcd_swizzle;
-    const int64_t tpx = ceil_div(tiles, kXcds);
-    const int64_t grid64 = padded_grid(tiles, swz);
-    if (grid64 > INT32_MAX) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_dia: grid too large");
-    const int grid = (int)grid64, nd = (int)ndiag;
-    const bool dot = wdot && dot_partial && tiles <= kPartialCapacity;
+    if (d.asked()) block = widen_block_for_partials(block, rows, rpl);
+    tile_launch g;
+    if (int st = tile_launch_for(ceil_div(rows, (int64_t)block * rpl), c.xcd_swizzle, "cmi_spmv_dia", &g)) return st;
+    const int nd = (int)ndiag;
+    const bool dot = d.fits(g.tiles);
     with_policy(pol, [&](auto P) {
         with_bool(dot, [&](auto DOT) {
             constexpr int POL = decltype(P)::value;
             constexpr bool D = decltype(DOT)::value;
-            if (rpl == 1) hipLaunchKernelGGL((dia_row_kernel<T, POL, D>), dim3(grid), dim3(block), 0, s, rows, cols, nd, pitch, offsets, vals, x, y, accumulate, tiles, tpx, swz, wdot, dot_partial);
-            else          hipLaunchKernelGGL((dia_row2_kernel<T, POL, D>), dim3(grid), dim3(block), 0, s, rows, cols, nd, pitch, offsets, vals, x, y, accumulate, tiles, tpx, swz, wdot, dot_partial);
+            if (rpl == 1) hipLaunchKernelGGL((dia_row_kernel<T, POL, D>), dim3(g.grid), dim3(block), 0, s, rows, cols, nd, pitch, offsets, vals, x, y, accumulate, g.tiles, g.tiles_per_xcd, g.swizzle, d.w, d.partial);
+            else          hipLaunchKernelGGL((dia_row2_kernel<T, POL, D>), dim3(g.grid), dim3(block), 0, s, rows, cols, nd, pitch, offsets, vals, x, y, accumulate, g.tiles, g.tiles_per_xcd, g.swizzle, d.w, d.partial);
         });
     });
     CMI_LAUNCH_CHECK("dia spmv");
-    if (dot && dot_partials) *dot_partials = (int)tiles;
+    if (dot) d.left(g.tiles);
     return CMI_SUCCESS;
+}
+
+// y <- A x and *dot_dev <- <y, w> (a double, whatever T: the partials are doubles) in one pass (see cmi_spmv_csr_dot_f64); when the
+// launch shape cannot fuse the dot (more workgroups than the workspace holds partials), the plain SpMV followed by the library's dot.
+template <typename T>
+static int spmv_ell_dot(int dtype, int64_t rows, int64_t cols, int64_t width, int64_t pitch, const int *Aj, const T *Ax, const int *row_lengths,
+                        const T *x, T *y, const T *w, double *dot_dev, void *workspace, const cmi_config *cfg, void *stream)
+{
+    if (dot_args_missing(w, rows, dot_dev, workspace)) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_ell_dot: null w, result or workspace");
+    int partials = 0;
+    if (int st = spmv_ell<T>(dtype, rows, cols, width, pitch, Aj, Ax, row_lengths, x, y, 0, cfg, stream, {w, (double *)workspace, &partials})) return st;
+    return finish_dot(partials, rows, y, w, dot_dev, workspace, stream);
+}
+template <typename T>
+static int spmv_dia_dot(int dtype, int64_t rows, int64_t cols, int64_t ndiag, int64_t pitch, const int *offsets, const T *vals, const T *x, T *y,
+                        const T *w, double *dot_dev, void *workspace, const cmi_config *cfg, void *stream)
+{
+    if (dot_args_missing(w, rows, dot_dev, workspace)) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_dia_dot: null w, result or workspace");
+    int partials = 0;
+    if (int st = spmv_dia<T>(dtype, rows, cols, ndiag, pitch, offsets, vals, x, y, 0, cfg, stream, {w, (double *)workspace, &partials})) return st;
+    return finish_dot(partials, rows, y, w, dot_dev, workspace, stream);
 }
 
 } // namespace cmi
@@ -470,56 +476,27 @@ CMI_API int cmi_spmv_dia_f32(int64_t num_rows, int64_t num_cols, int64_t num_dia
     return cmi::spmv_dia<float>(CMI_F32, num_rows, num_cols, num_diagonals, pitch, diagonal_offsets, values, x, y, accumulate, cfg, stream);
 }
 
-// y <- A x and *dot_dev <- <y, w> in one pass (see cmi_spmv_csr_dot_f64); when the launch shape cannot fuse the
-// dot (more workgroups than the workspace holds partials), the plain SpMV followed by cmi_blas_dot_f64.
 CMI_API int cmi_spmv_ell_dot_f64(int64_t num_rows, int64_t num_cols, int64_t num_entries_per_row, int64_t pitch,
                                  const int32_t *Aj, const double *Ax, const int32_t *row_lengths, const double *x,
                                  double *y, const double *w, double *dot_dev, void *workspace, const cmi_config *cfg, void *stream)
 {
-    if ((!w && num_rows > 0) || !dot_dev || !workspace) return cmi::fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_ell_dot: null w, result or workspace");
-    int partials = 0;
-    const int st = cmi::spmv_ell<double>(CMI_F64, num_rows, num_cols, num_entries_per_row, pitch, Aj, Ax, row_lengths, x, y, 0, cfg, stream,
-                                         w, (double *)workspace, &partials);
-    if (st) return st;
-    if (partials > 0) return cmi::reduce_partials_f64(partials, (double *)workspace, dot_dev, cmi::as_stream(stream));
-    return cmi_blas_dot_f64(num_rows, y, w, dot_dev, workspace, stream);
+    return cmi::spmv_ell_dot<double>(CMI_F64, num_rows, num_cols, num_entries_per_row, pitch, Aj, Ax, row_lengths, x, y, w, dot_dev, workspace, cfg, stream);
 }
-
-// float matrices: the same, the scalar stays a double (partials are doubles; the fallback is cmi_blas_dotd_f32)
 CMI_API int cmi_spmv_ell_dot_f32(int64_t num_rows, int64_t num_cols, int64_t num_entries_per_row, int64_t pitch,
                                  const int32_t *Aj, const float *Ax, const int32_t *row_lengths, const float *x,
                                  float *y, const float *w, double *dot_dev, void *workspace, const cmi_config *cfg, void *stream)
 {
-    if ((!w && num_rows > 0) || !dot_dev || !workspace) return cmi::fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_ell_dot: null w, result or workspace");
-    int partials = 0;
-    const int st = cmi::spmv_ell<float>(CMI_F32, num_rows, num_cols, num_entries_per_row, pitch, Aj, Ax, row_lengths, x, y, 0, cfg, stream,
-                                        w, (double *)workspace, &partials);
-    if (st) return st;
-    if (partials > 0) return cmi::reduce_partials_f64(partials, (double *)workspace, dot_dev, cmi::as_stream(stream));
-    return cmi_blas_dotd_f32(num_rows, y, w, dot_dev, workspace, stream);
+    return cmi::spmv_ell_dot<float>(CMI_F32, num_rows, num_cols, num_entries_per_row, pitch, Aj, Ax, row_lengths, x, y, w, dot_dev, workspace, cfg, stream);
+}
+CMI_API int cmi_spmv_dia_dot_f64(int64_t num_rows, int64_t num_cols, int64_t num_diagonals, int64_t pitch,
+                                 const int32_t *diagonal_offsets, const double *values, const double *x, double *y,
+                                 const double *w, double *dot_dev, void *workspace, const cmi_config *cfg, void *stream)
+{
+    return cmi::spmv_dia_dot<double>(CMI_F64, num_rows, num_cols, num_diagonals, pitch, diagonal_offsets, values, x, y, w, dot_dev, workspace, cfg, stream);
 }
 CMI_API int cmi_spmv_dia_dot_f32(int64_t num_rows, int64_t num_cols, int64_t num_diagonals, int64_t pitch,
                                  const int32_t *diagonal_offsets, const float *values, const float *x, float *y,
                                  const float *w, double *dot_dev, void *workspace, const cmi_config *cfg, void *stream)
 {
-    if ((!w && num_rows > 0) || !dot_dev || !workspace) return cmi::fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_dia_dot: null w, result or workspace");
-    int partials = 0;
-    const int st = cmi::spmv_dia<float>(CMI_F32, num_rows, num_cols, num_diagonals, pitch, diagonal_offsets, values, x, y, 0, cfg, stream,
-                                        w, (double *)workspace, &partials);
-    if (st) return st;
-    if (partials > 0) return cmi::reduce_partials_f64(partials, (double *)workspace, dot_dev, cmi::as_stream(stream));
-    return cmi_blas_dotd_f32(num_rows, y, w, dot_dev, workspace, stream);
-}
-
-CMI_API int cmi_spmv_dia_dot_f64(int64_t num_rows, int64_t num_cols, int64_t num_diagonals, int64_t pitch,
-                                 const int32_t *diagonal_offsets, const double *values, const double *x, double *y,
-                                 const double *w, double *dot_dev, void *workspace, const cmi_config *cfg, void *stream)
-{
-    if ((!w && num_rows > 0) || !dot_dev || !workspace) return cmi::fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_dia_dot: null w, result or workspace");
-    int partials = 0;
-    const int st = cmi::spmv_dia<double>(CMI_F64, num_rows, num_cols, num_diagonals, pitch, diagonal_offsets, values, x, y, 0, cfg, stream,
-                                         w, (double *)workspace, &partials);
-    if (st) return st;
-    if (partials > 0) return cmi::reduce_partials_f64(partials, (double *)workspace, dot_dev, cmi::as_stream(stream));
-    return cmi_blas_dot_f64(num_rows, y, w, dot_dev, workspace, stream);
+    return cmi::spmv_dia_dot<float>(CMI_F32, num_rows, num_cols, num_diagonals, pitch, diagonal_offsets, values, x, y, w, dot_dev, workspace, cfg, stream);
 }
