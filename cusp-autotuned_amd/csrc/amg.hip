@@ -26,16 +26,6 @@ __device__ __forceinline__ float amg_sqrt(float v) { return sqrtf(v); }
 __device__ __forceinline__ double amg_abs(double v) { return fabs(v); }
 __device__ __forceinline__ float amg_abs(float v) { return fabsf(v); }
 
-// out[0 .. n] = exclusive prefix sums of in[0 .. n] (in[n] must be 0: the total lands in out[n]); `temp` keeps the temporary
-static hipError_t amg_offsets(device_array<unsigned char> &temp, const int *in, int *out, int64_t n, hipStream_t s)
-{
-    size_t bytes = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, bytes, in, out, 0, (size_t)(n + 1), rocprim::plus<int>(), s);
-    if (e == hipSuccess) e = temp.alloc(bytes);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(temp.get(), bytes, in, out, 0, (size_t)(n + 1), rocprim::plus<int>(), s);
-    return e;
-}
-
 // ---- (a) symmetric strength of connection ---------------------------------------------------------------------------------
 // |A_ij| >= theta * sqrt(|A_ii| |A_jj|): product and square root in T, the product with theta and the comparison in double
 // (symmetric_strength.h:72 with its `const double theta`).  A NaN on either side compares false: the entry is dropped.
@@ -164,19 +154,14 @@ static int strength_symmetric(int64_t num_rows, int64_t num_cols, int64_t num_en
     T *const diag = diag_block.get();
     int *const count = count_block.get();
     int st = CMI_SUCCESS;
-    hipLaunchKernelGGL((strength_diagonal_kernel<T>), dim3(amg_blocks(num_rows)), dim3(kAmgBlock), 0, s, num_rows, num_entries, Ap, Aj, Ax, diag);
-    e = hipGetLastError();
+    e = launch(strength_diagonal_kernel<T>, amg_blocks(num_rows), kAmgBlock, 0, s, num_rows, num_entries, Ap, Aj, Ax, diag);
     if (e != hipSuccess) st = hip_fail(e, "launch strength diagonal");
     if (st == CMI_SUCCESS) {
-        hipLaunchKernelGGL((strength_kernel<T, false>), dim3(amg_blocks(num_rows + 1)), dim3(kAmgBlock), 0, s, num_rows, num_entries, Ap, Aj, Ax, (const T *)diag,
-                           theta, count, (const int *)nullptr, (int *)nullptr, (T *)nullptr, capacity);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = amg_offsets(scan_temp, count, Sp, num_rows, s);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL((strength_kernel<T, true>), dim3(amg_blocks(num_rows)), dim3(kAmgBlock), 0, s, num_rows, num_entries, Ap, Aj, Ax, (const T *)diag,
-                               theta, (int *)nullptr, (const int *)Sp, Sj, Sx, capacity);
-            e = hipGetLastError();
-        }
+        e = launch(strength_kernel<T, false>, amg_blocks(num_rows + 1), kAmgBlock, 0, s, num_rows, num_entries, Ap, Aj, Ax, diag, theta, count, nullptr, nullptr,
+                   nullptr, capacity);
+        if (e == hipSuccess) e = exclusive_offsets(scan_temp, count, Sp, num_rows, s);
+        if (e == hipSuccess)
+            e = launch(strength_kernel<T, true>, amg_blocks(num_rows), kAmgBlock, 0, s, num_rows, num_entries, Ap, Aj, Ax, diag, theta, nullptr, Sp, Sj, Sx, capacity);
         if (e != hipSuccess) st = hip_fail(e, "cmi_csr_strength_symmetric");
     }
     // the scratch is released when this returns: everything enqueued above must have finished with it
@@ -336,32 +321,23 @@ static int aggregates_fit(int64_t n, int64_t num_aggregates, const int *aggregat
     if (e == hipSuccess) e = bad.block.alloc(1);
     uint32_t *const key = key_block.get(), *const key_sorted = key_sorted_block.get(), *const rows = rows_block.get();
     int *const keep = keep_block.get();
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, temp_bytes, (const uint32_t *)key, key_sorted, position, rows, (unsigned)n, 0u, end_bit, s);
+    // sized and allocated here, run behind the check of the ids: nothing of the caller's is touched before every block is there
+    auto sort = [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, (const uint32_t *)key, key_sorted, position, rows, (unsigned)n, 0u, end_bit, s); };
+    if (e == hipSuccess) e = temp_size(sort, &temp_bytes);
     if (e == hipSuccess) e = temp.alloc(temp_bytes);
     if (e != hipSuccess) return hip_fail(e, "cmi_aggregates_fit: scratch");
     e = hipMemsetAsync(bad.dev(), 0, sizeof(int), s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(fit_keys_kernel, dim3(amg_blocks(n + 1)), dim3(kAmgBlock), 0, s, n, num_aggregates, aggregates, key, keep, bad.dev());
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess) e = launch(fit_keys_kernel, amg_blocks(n + 1), kAmgBlock, 0, s, n, num_aggregates, aggregates, key, keep, bad.dev());
     if (e == hipSuccess) e = bad.fetch(s); // the flag is read once, before anything of the caller's is written
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(s); // (the blocks go when this returns)
         return hip_fail(e, "cmi_aggregates_fit: checking the aggregate ids");
     }
     if (bad.host[0]) return fail(CMI_ERROR_INVALID_VALUE, "cmi_aggregates_fit: an aggregate id lies outside [-1, num_aggregates)");
-    e = rocprim::radix_sort_pairs(temp.get(), temp_bytes, (const uint32_t *)key, key_sorted, position, rows, (unsigned)n, 0u, end_bit, s);
-    if (e == hipSuccess) e = amg_offsets(scan_temp, keep, Tp, n, s);
-    if (e == hipSuccess && num_aggregates > 0) {
-        hipLaunchKernelGGL((fit_norms_kernel<T>), dim3(amg_blocks(num_aggregates)), dim3(kAmgBlock), 0, s, n, num_aggregates, (const uint32_t *)key_sorted,
-                           (const uint32_t *)rows, B, R);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess && num_aggregates > 0) {
-        hipLaunchKernelGGL((fit_fill_kernel<T>), dim3(amg_blocks(n)), dim3(kAmgBlock), 0, s, n, num_aggregates, aggregates, B, (const T *)R, (const int *)Tp, Tj, Tx,
-                           capacity);
-        e = hipGetLastError();
-    }
+    e = sort(temp.get(), temp_bytes);
+    if (e == hipSuccess) e = exclusive_offsets(scan_temp, keep, Tp, n, s);
+    if (e == hipSuccess && num_aggregates > 0) e = launch(fit_norms_kernel<T>, amg_blocks(num_aggregates), kAmgBlock, 0, s, n, num_aggregates, key_sorted, rows, B, R);
+    if (e == hipSuccess && num_aggregates > 0) e = launch(fit_fill_kernel<T>, amg_blocks(n), kAmgBlock, 0, s, n, num_aggregates, aggregates, B, R, Tp, Tj, Tx, capacity);
     const hipError_t e2 = hipStreamSynchronize(s);
     if (e == hipSuccess) e = e2;
     return e == hipSuccess ? CMI_SUCCESS : hip_fail(e, "cmi_aggregates_fit");
@@ -451,23 +427,19 @@ static int csr_elementwise(int64_t num_rows, int64_t num_cols, int64_t a_entries
     if (e != hipSuccess) return hip_fail(e, "cmi_csr_elementwise: scratch");
     int *const count = count_block.get();
     e = hipMemsetAsync(unsorted.dev(), 0, sizeof(int), s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL((elementwise_kernel<T, false>), dim3(amg_blocks(num_rows + 1)), dim3(kAmgBlock), 0, s, num_rows, num_cols, a_entries, Ap, Aj, Ax, b_entries,
-                           Bp, Bj, Bx, op, count, unsorted.dev(), (const int *)nullptr, (int *)nullptr, (T *)nullptr, capacity);
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess)
+        e = launch(elementwise_kernel<T, false>, amg_blocks(num_rows + 1), kAmgBlock, 0, s, num_rows, num_cols, a_entries, Ap, Aj, Ax, b_entries, Bp, Bj, Bx, op, count,
+                   unsorted.dev(), nullptr, nullptr, nullptr, capacity);
     if (e == hipSuccess) e = unsorted.fetch(s); // the flag is read once, before anything of the caller's is written
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(s); // (the blocks go when this returns)
         return hip_fail(e, "cmi_csr_elementwise: counting");
     }
     if (unsorted.host[0]) return CMI_SUCCESS; // *sorted_host == 0: the caller sorts, or takes its host path
-    e = amg_offsets(scan_temp, count, Cp, num_rows, s);
-    if (e == hipSuccess && num_rows > 0) {
-        hipLaunchKernelGGL((elementwise_kernel<T, true>), dim3(amg_blocks(num_rows)), dim3(kAmgBlock), 0, s, num_rows, num_cols, a_entries, Ap, Aj, Ax, b_entries, Bp,
-                           Bj, Bx, op, (int *)nullptr, (int *)nullptr, (const int *)Cp, Cj, Cx, capacity);
-        e = hipGetLastError();
-    }
+    e = exclusive_offsets(scan_temp, count, Cp, num_rows, s);
+    if (e == hipSuccess && num_rows > 0)
+        e = launch(elementwise_kernel<T, true>, amg_blocks(num_rows), kAmgBlock, 0, s, num_rows, num_cols, a_entries, Ap, Aj, Ax, b_entries, Bp, Bj, Bx, op, nullptr,
+                   nullptr, Cp, Cj, Cx, capacity);
     const hipError_t e2 = hipStreamSynchronize(s);
     if (e == hipSuccess) e = e2;
     if (e != hipSuccess) return hip_fail(e, "cmi_csr_elementwise");

@@ -1,9 +1,7 @@
 // amg_shared.h -- what the set-up translation units of smoothed aggregation (amg.hip, mis.hip) share: the size ceiling, the
 // launch shape of one lane per row and the clamp of a row offset.
 #pragma once
-#include "common.h"
-
-#include <rocprim/rocprim.hpp>
+#include "setup_scan.h"
 
 namespace cmi {
 

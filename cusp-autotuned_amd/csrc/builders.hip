@@ -14,7 +14,7 @@
 // the grid.  The CSR row therefore holds, in ascending column order, {r-m | iy>0}, {r-1 | ix>0}, r,
 // {r+1 | ix<m-1}, {r+m | iy<n-1}; its offset has the closed form used below, so every lane writes
 // its row independently (no scan).
-#include "common.h"
+#include "setup_scan.h"
 
 namespace cmi {
 
@@ -279,11 +279,8 @@ CMI_API int cmi_csr_diagonals(int64_t num_rows, int64_t num_cols, const int32_t 
     device_counters<unsigned long long> counter;
     hipError_t e = counter.open(s);
     if (e == hipSuccess) e = hipMemsetAsync(slot_map, 0, (size_t)map_len * sizeof(int), s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(dia_flag_kernel, dim3(grid_1d(num_rows * 8)), dim3(256), 0, s, num_rows, Ap, Aj, slot_map);
-        hipLaunchKernelGGL(dia_list_kernel, dim3(grid_1d(map_len)), dim3(256), 0, s, num_rows, map_len, slot_map, diag_list, capacity, counter.dev());
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess) e = launch(dia_flag_kernel, grid_1d(num_rows * 8), 256, 0, s, num_rows, Ap, Aj, slot_map);
+    if (e == hipSuccess) e = launch(dia_list_kernel, grid_1d(map_len), 256, 0, s, num_rows, map_len, slot_map, diag_list, capacity, counter.dev());
     if (e == hipSuccess) e = counter.fetch(s);
     if (e != hipSuccess) return hip_fail(e, "cmi_csr_diagonals");
     *num_diagonals_host = (int64_t)counter.host[0];
@@ -381,12 +378,9 @@ CMI_API int cmi_csr_column_span(int64_t num_entries, const int32_t *Aj, int32_t 
     span.host[1] = INT32_MIN;
     hipError_t e = span.block.alloc(2);
     if (e == hipSuccess) e = hipMemcpyAsync(span.dev(), span.host, sizeof(span.host), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        int64_t blocks = ceil_div(num_entries, 256 * 8);
-        if (blocks > kCus * 8) blocks = kCus * 8;
-        hipLaunchKernelGGL(column_span_kernel, dim3((unsigned)blocks), dim3(256), 0, s, num_entries, Aj, span.dev());
-        e = hipGetLastError();
-    }
+    int64_t blocks = ceil_div(num_entries, 256 * 8);
+    if (blocks > kCus * 8) blocks = kCus * 8;
+    if (e == hipSuccess) e = launch(column_span_kernel, (unsigned)blocks, 256, 0, s, num_entries, Aj, span.dev());
     if (e == hipSuccess) e = span.fetch(s);
     if (e != hipSuccess) return hip_fail(e, "cmi_csr_column_span");
     *min_host = span.host[0];
@@ -425,10 +419,7 @@ CMI_API int cmi_csr_interior_rows(int64_t num_rows, const int32_t *Ap, const int
     edge.host[1] = (int)num_rows;
     hipError_t e = edge.block.alloc(2);
     if (e == hipSuccess) e = hipMemcpyAsync(edge.dev(), edge.host, sizeof(edge.host), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(interior_rows_kernel, dim3(grid_1d(num_rows)), dim3(256), 0, s, num_rows, Ap, Aj, col_lo, col_hi, num_rows / 2, edge.dev());
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess) e = launch(interior_rows_kernel, grid_1d(num_rows), 256, 0, s, num_rows, Ap, Aj, col_lo, col_hi, num_rows / 2, edge.dev());
     if (e == hipSuccess) e = edge.fetch(s);
     if (e != hipSuccess) return hip_fail(e, "cmi_csr_interior_rows");
     *first_host = (int64_t)edge.host[0] + 1;
@@ -481,10 +472,7 @@ CMI_API int cmi_coo_row_offsets(int64_t num_rows, int64_t num_entries, const int
     hipStream_t s = as_stream(stream);
     device_counters<int> flag;
     hipError_t e = flag.open(s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(coo_row_offsets_kernel, dim3(grid_1d(num_entries + 1)), dim3(256), 0, s, num_rows, num_entries, Ai, Ap, flag.dev());
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess) e = launch(coo_row_offsets_kernel, grid_1d(num_entries + 1), 256, 0, s, num_rows, num_entries, Ai, Ap, flag.dev());
     if (e == hipSuccess) e = flag.fetch(s);
     if (e != hipSuccess) return hip_fail(e, "cmi_coo_row_offsets");
     *sorted_host = flag.host[0] == 0;
@@ -504,72 +492,14 @@ CMI_API int cmi_ell_row_lengths(int64_t num_rows, int64_t width, int64_t pitch, 
 }
 
 // ---------------------------------------------------------------------------------------------
-// ELL -> CSR and DIA -> CSR on the device (reference conversions/ell_to_other.h, dia_to_other.h:107-160: keep the
+// ELL -> CSR, DIA -> CSR and HYB -> CSR on the device (reference conversions/ell_to_other.h, dia_to_other.h:107-160: keep the
 // entries with a valid column -- DIA: and a non-zero value -- in row-major order): count per row, exclusive scan,
-// scatter.  Setup-time code: the scan is the plain three-pass one (tile sums, scan of the sums, apply).
+// scatter (to_csr below).
 // ---------------------------------------------------------------------------------------------
 namespace cmi {
 
-constexpr int kScanTile = 2048; // 256 lanes x 8
-constexpr int64_t kScanMaxCount = INT32_MAX / kScanTile; // per-row counts up to this keep a tile's int32 sum exact
-
-__global__ void __launch_bounds__(256) scan_tile_sums_kernel(int64_t n, const int *__restrict__ in, int *__restrict__ sums)
-{
-    __shared__ int slots[256 / kWave];
-    const int64_t base = (int64_t)blockIdx.x * kScanTile;
-    int acc = 0;
-    for (int k = 0; k < 8; k++) {
-        const int64_t i = base + threadIdx.x * 8 + k;
-        if (i < n) acc += in[i];
-    }
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) acc += __shfl_down(acc, o);
-    if ((threadIdx.x & (kWave - 1)) == 0) slots[threadIdx.x / kWave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) sums[blockIdx.x] = slots[0] + slots[1] + slots[2] + slots[3];
-}
-
-// one workgroup: sums[] -> exclusive scan in place, the grand total to *total.  The running total is kept in 64 bits:
-// a total beyond INT32_MAX (rows*width or rows*diagonals can exceed it) is reported as *total = -1, never wrapped.
-__global__ void __launch_bounds__(256) scan_sums_kernel(int64_t ntiles, int *__restrict__ sums, int *__restrict__ total)
-{
-    __shared__ long long buf[256];
-    long long carry = 0;
-    for (int64_t base = 0; base < ntiles; base += 256) {
-        const int64_t i = base + threadIdx.x;
-        const long long v = i < ntiles ? sums[i] : 0;
-        buf[threadIdx.x] = v;
-        __syncthreads();
-        for (int o = 1; o < 256; o <<= 1) { // Hillis-Steele inclusive scan of 256 values
-            const long long t = (int)threadIdx.x >= o ? buf[threadIdx.x - o] : 0;
-            __syncthreads();
-            buf[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (i < ntiles) sums[i] = (int)(carry + buf[threadIdx.x] - v); // meaningless past an overflow; the caller stops on total < 0
-        const long long chunk = buf[255];
-        __syncthreads();
-        carry += chunk;
-    }
-    if (threadIdx.x == 0) *total = carry > (long long)INT32_MAX ? -1 : (int)carry;
-}
-
-__global__ void __launch_bounds__(256) scan_apply_kernel(int64_t n, const int *__restrict__ in, const int *__restrict__ sums, int *__restrict__ out)
-{
-    __shared__ int wave_tot[256 / kWave];
-    const int64_t base = (int64_t)blockIdx.x * kScanTile + threadIdx.x * 8;
-    int v[8], local = 0;
-    for (int k = 0; k < 8; k++) { v[k] = base + k < n ? in[base + k] : 0; local += v[k]; }
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    int incl = local; // inclusive scan of the lanes' totals inside the wave
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) { const int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
-    if (lane == kWave - 1) wave_tot[wave] = incl;
-    __syncthreads();
-    int off = sums[blockIdx.x] + incl - local;
-    for (int w = 0; w < wave; w++) off += wave_tot[w];
-    for (int k = 0; k < 8; k++) { if (base + k < n) out[base + k] = off; off += v[k]; }
-}
+// the widest ELL part and the most diagonals a conversion to CSR takes (a refusal the ABI has always made: INT32_MAX / 2048)
+constexpr int64_t kToCsrMaxSlots = INT32_MAX / 2048;
 
 __global__ void __launch_bounds__(256)
 ell_valid_counts_kernel(int64_t num_rows, int width, int64_t pitch, const int *__restrict__ ell_Aj, int *__restrict__ counts)
@@ -629,22 +559,50 @@ dia_to_csr_kernel(int64_t num_rows, int64_t num_cols, int nd, int64_t pitch, con
     }
 }
 
-// out[0..n] <- exclusive scan of in[0..n) (out[n] = the total); returns the total to the host.  Synchronises the stream.
-static int exclusive_scan_i32(int64_t n, const int *in, int *out, int64_t *total_host, hipStream_t s)
+struct widen_count { __host__ __device__ long long operator()(int v) const { return v; } };
+
+// The host side of a conversion to CSR.  `count` leaves every row's number of kept entries in counts[0 .. rows) (the caller's
+// scratch of rows + 1 ints); Ap[0 .. rows] receives their exclusive sums and *nnz_host the total, which is summed in 64 bits as
+// well: beyond INT32_MAX the offsets have wrapped and nothing is written through them.  A fill call (`fill`: Aj and Ax given;
+// without them the call only sizes) whose capacity holds the entries then runs `scatter`.  Both are callables that return their
+// launch's error.  Synchronises the stream.
+template <typename Count, typename Scatter>
+static int to_csr(const char *who, int64_t rows, int *counts, int *Ap, bool fill, int64_t capacity, int64_t *nnz_host, hipStream_t s, Count &&count,
+                  Scatter &&scatter)
 {
-    const int64_t ntiles = ceil_div(n > 0 ? n : 1, (int64_t)kScanTile);
-    device_array<int> sums;
-    CMI_HIP(sums.alloc((size_t)ntiles));
-    hipLaunchKernelGGL(scan_tile_sums_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, n, in, sums.get());
-    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(256), 0, s, ntiles, sums.get(), out + n);
-    hipLaunchKernelGGL(scan_apply_kernel, dim3((unsigned)ntiles), dim3(256), 0, s, n, in, sums.get(), out);
-    hipError_t e = hipGetLastError();
-    int total = 0;
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, out + n, sizeof(int), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return hip_fail(e, "exclusive scan");
-    if (total < 0) return fail(CMI_ERROR_NOT_SUPPORTED, "conversion to CSR: more than INT32_MAX entries (int32 row offsets cannot address them)");
-    if (total_host) *total_host = total;
+    device_array<unsigned char> temp; // the sum's temporary, then the scan's: one block of the larger size, both run on `s`
+    device_counters<long long> total; // (not opened: the sum overwrites it)
+    CMI_HIP(total.block.alloc(1));
+    auto sum = [&](void *t, size_t &b) {
+        return rocprim::reduce(t, b, rocprim::make_transform_iterator((const int *)counts, widen_count()), total.dev(), 0ll, (size_t)rows + 1, rocprim::plus<long long>(), s);
+    };
+    auto scan = offsets_scan((const int *)counts, Ap, rows, s);
+    size_t sum_bytes = 0, scan_bytes = 0;
+    const char *step = who; // what a HIP error is reported under
+    hipError_t e = hipMemsetAsync(counts + rows, 0, sizeof(int), s);
+    if (e == hipSuccess && rows > 0) e = count();
+    if (e == hipSuccess) e = temp_size(sum, &sum_bytes);
+    if (e == hipSuccess) e = temp_size(scan, &scan_bytes);
+    if (e == hipSuccess) e = temp.alloc(sum_bytes > scan_bytes ? sum_bytes : scan_bytes);
+    if (e == hipSuccess) e = sum(temp.get(), sum_bytes);
+    if (e == hipSuccess) {
+        step = "exclusive scan";
+        e = scan(temp.get(), scan_bytes);
+    }
+    if (e == hipSuccess) e = total.fetch(s);
+    if (e != hipSuccess) return hip_fail(e, step);
+    if (total.host[0] > INT32_MAX) return fail(CMI_ERROR_NOT_SUPPORTED, "conversion to CSR: more than INT32_MAX entries (int32 row offsets cannot address them)");
+    *nnz_host = total.host[0];
+    if (!fill) return CMI_SUCCESS;
+    if (*nnz_host > capacity) {
+        set_error("%s: capacity is smaller than the entry count", who);
+        return CMI_ERROR_INVALID_VALUE;
+    }
+    if (*nnz_host > 0) {
+        e = scatter();
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return hip_fail(e, who);
+    }
     return CMI_SUCCESS;
 }
 
@@ -652,40 +610,28 @@ template <typename T>
 static int ell_to_csr(int64_t rows, int64_t width, int64_t pitch, const int *eAj, const T *eAx, int *Ap, int *Aj, T *Ax,
                       int64_t capacity, int64_t *nnz_host, void *stream)
 {
-    if (rows < 0 || width < 0 || width > kScanMaxCount || (width > 0 && pitch < rows)) return fail(CMI_ERROR_INVALID_VALUE, "cmi_ell_to_csr: bad size");
+    if (rows < 0 || width < 0 || width > kToCsrMaxSlots || (width > 0 && pitch < rows)) return fail(CMI_ERROR_INVALID_VALUE, "cmi_ell_to_csr: bad size");
     if (!Ap || !nnz_host || (rows > 0 && width > 0 && (!eAj || !eAx))) return fail(CMI_ERROR_INVALID_VALUE, "cmi_ell_to_csr: null array");
     hipStream_t s = as_stream(stream);
-    device_array<int> count_block;
-    CMI_HIP(count_block.alloc((size_t)(rows > 0 ? rows : 1)));
-    int *const counts = count_block.get();
-    if (rows > 0) hipLaunchKernelGGL(ell_valid_counts_kernel, dim3(grid_1d(rows)), dim3(256), 0, s, rows, (int)width, pitch, eAj, counts);
-    int st = exclusive_scan_i32(rows, counts, Ap, nnz_host, s);
-    if (st == CMI_SUCCESS && Aj && Ax && *nnz_host > capacity) st = fail(CMI_ERROR_INVALID_VALUE, "cmi_ell_to_csr: capacity is smaller than the entry count");
-    if (st == CMI_SUCCESS && *nnz_host > 0 && Aj && Ax) { // Aj == NULL: a sizing call
-        hipLaunchKernelGGL((ell_to_csr_kernel<T>), dim3(grid_1d(rows)), dim3(256), 0, s, rows, (int)width, pitch, eAj, eAx, Ap, Aj, Ax);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) st = fail(CMI_ERROR_HIP, "cmi_ell_to_csr: scatter failed");
-    }
-    return st;
+    device_array<int> counts;
+    CMI_HIP(counts.alloc((size_t)rows + 1));
+    return to_csr("cmi_ell_to_csr", rows, counts.get(), Ap, Aj && Ax, capacity, nnz_host, s,
+                  [&] { return launch(ell_valid_counts_kernel, grid_1d(rows), 256, 0, s, rows, (int)width, pitch, eAj, counts.get()); },
+                  [&] { return launch(ell_to_csr_kernel<T>, grid_1d(rows), 256, 0, s, rows, (int)width, pitch, eAj, eAx, Ap, Aj, Ax); });
 }
 
 template <typename T>
 static int dia_to_csr(int64_t rows, int64_t cols, int64_t nd, int64_t pitch, const int *offsets, const T *vals, int *Ap, int *Aj, T *Ax,
                       int64_t capacity, int64_t *nnz_host, void *stream)
 {
-    if (rows < 0 || cols < 0 || nd < 0 || nd > kScanMaxCount || (nd > 0 && pitch < rows)) return fail(CMI_ERROR_INVALID_VALUE, "cmi_dia_to_csr: bad size");
+    if (rows < 0 || cols < 0 || nd < 0 || nd > kToCsrMaxSlots || (nd > 0 && pitch < rows)) return fail(CMI_ERROR_INVALID_VALUE, "cmi_dia_to_csr: bad size");
     if (!Ap || !nnz_host || (rows > 0 && nd > 0 && (!offsets || !vals))) return fail(CMI_ERROR_INVALID_VALUE, "cmi_dia_to_csr: null array");
     hipStream_t s = as_stream(stream);
-    device_array<int> count_block;
-    CMI_HIP(count_block.alloc((size_t)(rows > 0 ? rows : 1)));
-    int *const counts = count_block.get();
-    if (rows > 0) hipLaunchKernelGGL((dia_valid_counts_kernel<T>), dim3(grid_1d(rows)), dim3(256), 0, s, rows, cols, (int)nd, pitch, offsets, vals, counts);
-    int st = exclusive_scan_i32(rows, counts, Ap, nnz_host, s);
-    if (st == CMI_SUCCESS && Aj && Ax && *nnz_host > capacity) st = fail(CMI_ERROR_INVALID_VALUE, "cmi_dia_to_csr: capacity is smaller than the entry count");
-    if (st == CMI_SUCCESS && *nnz_host > 0 && Aj && Ax) {
-        hipLaunchKernelGGL((dia_to_csr_kernel<T>), dim3(grid_1d(rows)), dim3(256), 0, s, rows, cols, (int)nd, pitch, offsets, vals, Ap, Aj, Ax);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) st = fail(CMI_ERROR_HIP, "cmi_dia_to_csr: scatter failed");
-    }
-    return st;
+    device_array<int> counts;
+    CMI_HIP(counts.alloc((size_t)rows + 1));
+    return to_csr("cmi_dia_to_csr", rows, counts.get(), Ap, Aj && Ax, capacity, nnz_host, s,
+                  [&] { return launch(dia_valid_counts_kernel<T>, grid_1d(rows), 256, 0, s, rows, cols, (int)nd, pitch, offsets, vals, counts.get()); },
+                  [&] { return launch(dia_to_csr_kernel<T>, grid_1d(rows), 256, 0, s, rows, cols, (int)nd, pitch, offsets, vals, Ap, Aj, Ax); });
 }
 
 // HYB -> CSR: a row's ELL entries, then its COO entries (the order hyb_matrix keeps: the first K entries of a row live in
@@ -722,34 +668,25 @@ template <typename T>
 static int hyb_to_csr(int64_t rows, int64_t width, int64_t pitch, const int *eAj, const T *eAx, int64_t ncoo, const int *cAi,
                       const int *cAj, const T *cAx, int *Ap, int *Aj, T *Ax, int64_t capacity, int64_t *nnz_host, void *stream)
 {
-    if (rows < 0 || width < 0 || width > kScanMaxCount / 2 || ncoo < 0 || ncoo > INT32_MAX / 2 || (width > 0 && pitch < rows))
+    if (rows < 0 || width < 0 || width > kToCsrMaxSlots / 2 || ncoo < 0 || ncoo > INT32_MAX / 2 || (width > 0 && pitch < rows))
         return fail(CMI_ERROR_INVALID_VALUE, "cmi_hyb_to_csr: bad size");
     if (!Ap || !nnz_host || (rows > 0 && width > 0 && (!eAj || !eAx)) || (ncoo > 0 && (!cAi || !cAj || !cAx)))
         return fail(CMI_ERROR_INVALID_VALUE, "cmi_hyb_to_csr: null array");
     hipStream_t s = as_stream(stream);
-    device_array<int> block; // [rows + 1] COO row offsets | [rows] counts | order flag
+    device_array<int> block; // [rows + 1] COO row offsets | [rows + 1] counts | order flag
     const size_t n1 = (size_t)rows + 1;
     CMI_HIP(block.alloc(2 * n1 + 1));
     int *coo_off = block.get(), *counts = coo_off + n1, *flag = coo_off + 2 * n1;
-    int st = CMI_SUCCESS, unsorted = 0;
+    int unsorted = 0;
     hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(coo_row_offsets_kernel, dim3(grid_1d(ncoo + 1)), dim3(256), 0, s, rows, ncoo, cAi, coo_off, flag);
-        e = hipMemcpyAsync(&unsorted, flag, sizeof(int), hipMemcpyDeviceToHost, s);
-    }
+    if (e == hipSuccess) e = launch(coo_row_offsets_kernel, grid_1d(ncoo + 1), 256, 0, s, rows, ncoo, cAi, coo_off, flag);
+    if (e == hipSuccess) e = hipMemcpyAsync(&unsorted, flag, sizeof(int), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) st = hip_fail(e, "cmi_hyb_to_csr");
-    else if (unsorted) st = fail(CMI_ERROR_NOT_SUPPORTED, "cmi_hyb_to_csr: the COO part is not sorted by row");
-    if (st == CMI_SUCCESS) {
-        if (rows > 0) hipLaunchKernelGGL(hyb_counts_kernel, dim3(grid_1d(rows)), dim3(256), 0, s, rows, (int)width, pitch, eAj, coo_off, counts);
-        st = exclusive_scan_i32(rows, counts, Ap, nnz_host, s);
-    }
-    if (st == CMI_SUCCESS && Aj && Ax && *nnz_host > capacity) st = fail(CMI_ERROR_INVALID_VALUE, "cmi_hyb_to_csr: capacity is smaller than the entry count");
-    if (st == CMI_SUCCESS && *nnz_host > 0 && Aj && Ax) {
-        hipLaunchKernelGGL((hyb_to_csr_kernel<T>), dim3(grid_1d(rows)), dim3(256), 0, s, rows, (int)width, pitch, eAj, eAx, coo_off, cAj, cAx, Ap, Aj, Ax);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) st = fail(CMI_ERROR_HIP, "cmi_hyb_to_csr: scatter failed");
-    }
-    return st;
+    if (e != hipSuccess) return hip_fail(e, "cmi_hyb_to_csr");
+    if (unsorted) return fail(CMI_ERROR_NOT_SUPPORTED, "cmi_hyb_to_csr: the COO part is not sorted by row");
+    return to_csr("cmi_hyb_to_csr", rows, counts, Ap, Aj && Ax, capacity, nnz_host, s,
+                  [&] { return launch(hyb_counts_kernel, grid_1d(rows), 256, 0, s, rows, (int)width, pitch, eAj, coo_off, counts); },
+                  [&] { return launch(hyb_to_csr_kernel<T>, grid_1d(rows), 256, 0, s, rows, (int)width, pitch, eAj, eAx, coo_off, cAj, cAx, Ap, Aj, Ax); });
 }
 
 } // namespace cmi
@@ -817,10 +754,7 @@ CMI_API int cmi_hyb_entries_per_row(int dtype, int64_t num_rows, const int32_t *
     hipStream_t s = as_stream(stream);
     device_counters<unsigned int, kHybCap + 1> bins;
     hipError_t e = bins.open(s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(row_length_histogram_kernel, dim3(grid_1d(num_rows)), dim3(256), 0, s, num_rows, Ap, bins.dev());
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess) e = launch(row_length_histogram_kernel, grid_1d(num_rows), 256, 0, s, num_rows, Ap, bins.dev());
     if (e == hipSuccess) e = bins.fetch(s);
     if (e != hipSuccess) return hip_fail(e, "cmi_hyb_entries_per_row");
     const unsigned int *const hist = bins.host;
@@ -878,12 +812,9 @@ template <typename T> static int count_zeros(int64_t n, const T *v, int64_t *cou
     hipStream_t s = as_stream(stream);
     device_counters<unsigned long long> zeros;
     hipError_t e = zeros.open(s);
-    if (e == hipSuccess) {
-        int64_t blocks = ceil_div(n, 256 * 8);
-        if (blocks > kCus * 16) blocks = kCus * 16;
-        hipLaunchKernelGGL((count_zeros_kernel<T>), dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(256), 0, s, n, v, zeros.dev());
-        e = hipGetLastError();
-    }
+    int64_t blocks = ceil_div(n, 256 * 8);
+    if (blocks > kCus * 16) blocks = kCus * 16;
+    if (e == hipSuccess) e = launch(count_zeros_kernel<T>, (unsigned)(blocks < 1 ? 1 : blocks), 256, 0, s, n, v, zeros.dev());
     if (e == hipSuccess) e = zeros.fetch(s);
     if (e != hipSuccess) return hip_fail(e, "cmi_count_zeros");
     *count_host = (int64_t)zeros.host[0];

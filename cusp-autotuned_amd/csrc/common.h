@@ -110,6 +110,16 @@ template <typename W, int N = 1> struct device_counters {
     }
 };
 
+// Enqueue `kernel` and report the launch: the one checked launch of set-up code (`if (e == hipSuccess) e = launch(...)`).  The
+// parameter types come from the kernel's own signature and the arguments convert to them as in any call, so a call site
+// passes nullptr, a T * where the kernel takes const T *, or an unsigned where grid and block are dim3, without a cast.
+template <typename... P, typename... A>
+inline hipError_t launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, A &&...args)
+{
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, s, std::forward<A>(args)...);
+    return hipGetLastError();
+}
+
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // tuning table lookup (tuning.hip)

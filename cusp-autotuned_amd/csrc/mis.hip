@@ -110,10 +110,8 @@ static hipError_t ring_launch(int mode, int64_t num_rows, int64_t num_entries, c
                               hipStream_t s)
 {
     const dim3 grid(amg_blocks(num_rows)), block(kAmgBlock);
-    if (mode == kRingPlain) hipLaunchKernelGGL((ring_max_kernel<kRingPlain>), grid, block, 0, s, num_rows, num_entries, Ap, Aj, x, z, state, bad);
-    else if (mode == kRingLastOfRound) hipLaunchKernelGGL((ring_max_kernel<kRingLastOfRound>), grid, block, 0, s, num_rows, num_entries, Ap, Aj, x, z, state, bad);
-    else hipLaunchKernelGGL((ring_max_kernel<kRingBoost>), grid, block, 0, s, num_rows, num_entries, Ap, Aj, x, z, state, bad);
-    return hipGetLastError();
+    const auto kernel = mode == kRingPlain ? ring_max_kernel<kRingPlain> : (mode == kRingLastOfRound ? ring_max_kernel<kRingLastOfRound> : ring_max_kernel<kRingBoost>);
+    return launch(kernel, grid, block, 0, s, num_rows, num_entries, Ap, Aj, x, z, state, bad);
 }
 
 // ---- MIS(k): the round loop ---------------------------------------------------------------------------------------------------
@@ -191,9 +189,7 @@ static int mis_states(mis_arena &arena, int64_t n, int64_t nnz, const int *Ap, c
     key_t *keys[3] = {nullptr, nullptr, nullptr};
     for (int a = 0; a < (k >= 2 ? 3 : 2); a++) keys[a] = arena.take<key_t>((size_t)n);
     if (!state || !counters || !keys[0] || !keys[1] || (k >= 2 && !keys[2])) return fail(CMI_ERROR_ALLOC, "maximal independent set: scratch reservation too small");
-    hipError_t e;
-    hipLaunchKernelGGL(mis_start_kernel, dim3(amg_blocks(n)), dim3(kAmgBlock), 0, s, n, seed, state, keys[0]);
-    e = hipGetLastError();
+    hipError_t e = launch(mis_start_kernel, amg_blocks(n), kAmgBlock, 0, s, n, seed, state, keys[0]);
     int rounds = 0, host[kCounters] = {0, 0, 0};
     while (e == hipSuccess) {
         e = hipMemsetAsync(counters, 0, kCounters * sizeof(int), s);
@@ -204,10 +200,7 @@ static int mis_states(mis_arena &arena, int64_t n, int64_t nnz, const int *Ap, c
             e = ring_launch(ring == k ? kRingLastOfRound : kRingPlain, n, nnz, Ap, Aj, from, to, state, counters + kCountBad, s);
             from = to;
         }
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(mis_finish_kernel, dim3(amg_blocks(n)), dim3(kAmgBlock), 0, s, n, seed, (const key_t *)to, state, keys[0], counters);
-            e = hipGetLastError();
-        }
+        if (e == hipSuccess) e = launch(mis_finish_kernel, amg_blocks(n), kAmgBlock, 0, s, n, seed, to, state, keys[0], counters);
         if (e == hipSuccess) e = hipMemcpyAsync(host, counters, sizeof(host), hipMemcpyDeviceToHost, s);
         const hipError_t e2 = hipStreamSynchronize(s); // the one host read of the round
         if (e == hipSuccess) e = e2;
@@ -270,8 +263,7 @@ static int maximal_independent_set(int64_t num_rows, int64_t num_entries, const 
             return r;
         }
     } else *set_size = num_rows; // every node, no sweep (state stays null)
-    hipLaunchKernelGGL(mis_flags_kernel, dim3(amg_blocks(num_rows)), dim3(kAmgBlock), 0, s, num_rows, num_rows, (const int *)state, stencil);
-    hipError_t e = hipGetLastError();
+    hipError_t e = launch(mis_flags_kernel, amg_blocks(num_rows), kAmgBlock, 0, s, num_rows, num_rows, state, stencil);
     const hipError_t e2 = hipStreamSynchronize(s); // the scratch is released when this returns
     if (e == hipSuccess) e = e2;
     return e == hipSuccess ? CMI_SUCCESS : hip_fail(e, who);
@@ -327,7 +319,7 @@ static int mis_aggregate(int64_t num_rows, int64_t num_entries, const int *Ap, c
     const int64_t n = num_rows;
     mis_arena arena;
     size_t scan_bytes = 0; // of one exclusive scan of n + 1 ints (both scans have this shape)
-    hipError_t e = rocprim::exclusive_scan(nullptr, scan_bytes, (const int *)nullptr, (int *)nullptr, 0, (size_t)(n + 1), rocprim::plus<int>(), s);
+    hipError_t e = temp_size(offsets_scan<int>(nullptr, nullptr, n, s), &scan_bytes);
     if (e == hipSuccess)
         e = arena.open(mis_states_bytes(n, 2) + 5 * mis_arena::padded((size_t)(n + 1) * sizeof(int)) + mis_arena::padded((size_t)n * sizeof(int)) +
                                 mis_arena::padded(scan_bytes));
@@ -341,33 +333,19 @@ static int mis_aggregate(int64_t num_rows, int64_t num_entries, const int *Ap, c
     int *keep = arena.take<int>((size_t)n + 1), *renumbered = arena.take<int>((size_t)n + 1), *first = arena.take<int>((size_t)n);
     void *scan_temp = arena.take<char>(scan_bytes ? scan_bytes : 1);
     if (!flag || !number || !members || !keep || !renumbered || !first || !scan_temp) return fail(CMI_ERROR_ALLOC, "cmi_csr_mis_aggregate: scratch reservation too small");
-    // out[0 .. n] = exclusive prefix sums of in[0 .. n] (in[n] is 0: the total lands in out[n])
-    auto offsets = [&](const int *in, int *out) { return rocprim::exclusive_scan(scan_temp, scan_bytes, in, out, 0, (size_t)(n + 1), rocprim::plus<int>(), s); };
+    // exclusive_offsets() in the arena's block, sized above
+    auto offsets = [&](const int *in, int *out) { return offsets_scan(in, out, n, s)(scan_temp, scan_bytes); };
     const dim3 grid(amg_blocks(n)), grid1(amg_blocks(n + 1)), block(kAmgBlock);
-    hipLaunchKernelGGL(aggregate_keys_kernel, grid, block, 0, s, n, (const int *)state, keys[0]);
-    e = hipGetLastError();
+    e = launch(aggregate_keys_kernel, grid, block, 0, s, n, state, keys[0]);
     if (e == hipSuccess) e = ring_launch(kRingBoost, n, num_entries, Ap, Aj, keys[0], keys[1], state, nullptr, s);
     if (e == hipSuccess) e = ring_launch(kRingPlain, n, num_entries, Ap, Aj, keys[1], keys[2], state, nullptr, s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(mis_flags_kernel, grid1, block, 0, s, n, n + 1, (const int *)state, flag);
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess) e = launch(mis_flags_kernel, grid1, block, 0, s, n, n + 1, state, flag);
     if (e == hipSuccess) e = offsets(flag, number);
     if (e == hipSuccess) e = hipMemsetAsync(members, 0, (size_t)(n + 1) * sizeof(int), s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(aggregate_first_kernel, grid, block, 0, s, n, (const key_t *)keys[2], (const int *)number, first, members);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(aggregate_keep_kernel, grid1, block, 0, s, n, (const int *)members, keep);
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess) e = launch(aggregate_first_kernel, grid, block, 0, s, n, keys[2], number, first, members);
+    if (e == hipSuccess) e = launch(aggregate_keep_kernel, grid1, block, 0, s, n, members, keep);
     if (e == hipSuccess) e = offsets(keep, renumbered);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(aggregate_final_kernel, grid, block, 0, s, n, (const int *)first, (const int *)keep, (const int *)renumbered, (const int *)flag,
-                           aggregates, mis);
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess) e = launch(aggregate_final_kernel, grid, block, 0, s, n, first, keep, renumbered, flag, aggregates, mis);
     int count = 0;
     if (e == hipSuccess) e = hipMemcpyAsync(&count, renumbered + n, sizeof(int), hipMemcpyDeviceToHost, s);
     const hipError_t e2 = hipStreamSynchronize(s); // the scratch is released when this returns

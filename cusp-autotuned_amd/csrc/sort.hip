@@ -12,9 +12,7 @@
 // the permutation and a copy back into the caller's arrays.  Stable = entries of one row keep their storage order, so the
 // row sums of the sorted matrix are the chains the reference's host loop (sequential/multiply/coo_spmv.h) forms on the
 // unsorted one: bit-identical products AND sums.  Only the key bits that can differ are sorted (ceil(log2(rows)) [+ columns]).
-#include "common.h"
-
-#include <rocprim/rocprim.hpp>
+#include "setup_scan.h"
 
 namespace cmi {
 
@@ -81,10 +79,7 @@ static int coo_order(int64_t num_rows, int64_t n, const int *Ai, const int *Aj, 
     if (n == 0) return CMI_SUCCESS;
     device_counters<int> flags;
     hipError_t e = flags.open(s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(coo_order_kernel, dim3(grid_1d(n)), dim3(256), 0, s, num_rows, n, Ai, Aj, flags.dev());
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess) e = launch(coo_order_kernel, grid_1d(n), 256, 0, s, num_rows, n, Ai, Aj, flags.dev());
     if (e == hipSuccess) e = flags.fetch(s);
     if (e != hipSuccess) return hip_fail(e, "cmi_coo_is_sorted");
     *flags_host = flags.host[0];
@@ -110,7 +105,6 @@ static int coo_sort(int64_t num_rows, int64_t num_cols, int64_t n, int *Ai, int 
     device_array<int> rows_block;
     device_array<uint64_t> keys_block, keys_sorted_block;
     device_array<T> vals_block;
-    size_t temp_bytes = 0;
     hipError_t e = perm_block.alloc((size_t)n);
     uint32_t *const perm = perm_block.get();
     if (e != hipSuccess) return hip_fail(e, "cmi_coo_sort_by_row: scratch");
@@ -120,44 +114,29 @@ static int coo_sort(int64_t num_rows, int64_t num_cols, int64_t n, int *Ai, int 
         const unsigned end_bit = (unsigned)bits_for(num_rows);
         e = rows_block.alloc((size_t)n);
         int *const rows_sorted = rows_block.get();
-        if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, temp_bytes, (const uint32_t *)Ai, (uint32_t *)rows_sorted, position, perm, size, 0u, end_bit, s);
-        if (e == hipSuccess) e = temp.alloc(temp_bytes);
-        if (e == hipSuccess) e = rocprim::radix_sort_pairs(temp.get(), temp_bytes, (const uint32_t *)Ai, (uint32_t *)rows_sorted, position, perm, size, 0u, end_bit, s);
+        if (e == hipSuccess) e = with_temp(temp, [&](void *t, size_t &b) {
+            return rocprim::radix_sort_pairs(t, b, (const uint32_t *)Ai, (uint32_t *)rows_sorted, position, perm, size, 0u, end_bit, s);
+        });
         if (e == hipSuccess) e = hipMemcpyAsync(Ai, rows_sorted, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, s);
         // the row scratch is free again once its copy has been enqueued behind it on the stream: reuse it for the columns
         int *const cols_sorted = rows_sorted;
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(gather_kernel<int>, dim3(grid_1d(n)), dim3(256), 0, s, n, perm, (const int *)Aj, cols_sorted);
-            e = hipGetLastError();
-        }
+        if (e == hipSuccess) e = launch(gather_kernel<int>, grid_1d(n), 256, 0, s, n, perm, Aj, cols_sorted);
         if (e == hipSuccess) e = hipMemcpyAsync(Aj, cols_sorted, (size_t)n * sizeof(int), hipMemcpyDeviceToDevice, s);
         if (e == hipSuccess) e = vals_block.alloc((size_t)n);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(gather_kernel<T>, dim3(grid_1d(n)), dim3(256), 0, s, n, perm, (const T *)Ax, vals_block.get());
-            e = hipGetLastError();
-        }
+        if (e == hipSuccess) e = launch(gather_kernel<T>, grid_1d(n), 256, 0, s, n, perm, Ax, vals_block.get());
         if (e == hipSuccess) e = hipMemcpyAsync(Ax, vals_block.get(), (size_t)n * sizeof(T), hipMemcpyDeviceToDevice, s);
     } else {
         const unsigned end_bit = 32u + (unsigned)bits_for(num_rows);
         e = keys_block.alloc((size_t)n);
         if (e == hipSuccess) e = keys_sorted_block.alloc((size_t)n);
         uint64_t *const keys = keys_block.get(), *const keys_sorted = keys_sorted_block.get();
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(pack_row_col_kernel, dim3(grid_1d(n)), dim3(256), 0, s, n, (const int *)Ai, (const int *)Aj, keys);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, temp_bytes, (const uint64_t *)keys, keys_sorted, position, perm, size, 0u, end_bit, s);
-        if (e == hipSuccess) e = temp.alloc(temp_bytes);
-        if (e == hipSuccess) e = rocprim::radix_sort_pairs(temp.get(), temp_bytes, (const uint64_t *)keys, keys_sorted, position, perm, size, 0u, end_bit, s);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(unpack_row_col_kernel, dim3(grid_1d(n)), dim3(256), 0, s, n, (const uint64_t *)keys_sorted, Ai, Aj);
-            e = hipGetLastError();
-        }
+        if (e == hipSuccess) e = launch(pack_row_col_kernel, grid_1d(n), 256, 0, s, n, Ai, Aj, keys);
+        if (e == hipSuccess) e = with_temp(temp, [&](void *t, size_t &b) {
+            return rocprim::radix_sort_pairs(t, b, (const uint64_t *)keys, keys_sorted, position, perm, size, 0u, end_bit, s);
+        });
+        if (e == hipSuccess) e = launch(unpack_row_col_kernel, grid_1d(n), 256, 0, s, n, keys_sorted, Ai, Aj);
         T *const vals_sorted = (T *)keys; // (8 bytes per entry, no longer read)
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(gather_kernel<T>, dim3(grid_1d(n)), dim3(256), 0, s, n, perm, (const T *)Ax, vals_sorted);
-            e = hipGetLastError();
-        }
+        if (e == hipSuccess) e = launch(gather_kernel<T>, grid_1d(n), 256, 0, s, n, perm, Ax, vals_sorted);
         if (e == hipSuccess) e = hipMemcpyAsync(Ax, vals_sorted, (size_t)n * sizeof(T), hipMemcpyDeviceToDevice, s);
     }
     // the blocks are released when this returns: everything enqueued above must have finished with it

@@ -30,13 +30,11 @@
 //
 // Workgroup- or wave-private LDS tiles for short rows (the AMG case) are NOT implemented: cmi_spgemm_info reports 0 rows in
 // tiles and cmi_spgemm_limits a tile size of 0.
-#include "common.h"
+#include "setup_scan.h"
 
 #include <algorithm>
 #include <new>
 #include <vector>
-
-#include <rocprim/rocprim.hpp>
 
 namespace cmi {
 
@@ -223,16 +221,15 @@ static int spgemm_csr(int64_t m, int64_t k, int64_t n, int64_t a_entries, const 
     device_array<uint32_t> perm_block, seg_block;
     device_array<T> vals_block;
     device_array<unsigned char> temp, sort_temp;
-    size_t temp_bytes = 0;
     hipError_t e = entry_block.alloc((size_t)a_entries + 1);
     if (e == hipSuccess) e = row_block.alloc((size_t)m + 1);
     if (e != hipSuccess) return hip_fail(e, "cmi_spgemm_csr: scratch");
     int64_t *const entry_start = entry_block.get(), *const row_start = row_block.get();
     hipLaunchKernelGGL(spgemm_entry_products_kernel, dim3(capped_grid(a_entries + 1)), dim3(256), 0, s, a_entries, k, b_entries, Aj, Bp, entry_start);
     CMI_LAUNCH_CHECK("spgemm entry products");
-    e = rocprim::exclusive_scan(nullptr, temp_bytes, entry_start, entry_start, (int64_t)0, (size_t)(a_entries + 1), rocprim::plus<int64_t>(), s);
-    if (e == hipSuccess) e = temp.alloc(temp_bytes);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(temp.get(), temp_bytes, entry_start, entry_start, (int64_t)0, (size_t)(a_entries + 1), rocprim::plus<int64_t>(), s);
+    e = with_temp(temp, [&](void *t, size_t &b) {
+        return rocprim::exclusive_scan(t, b, entry_start, entry_start, (int64_t)0, (size_t)(a_entries + 1), rocprim::plus<int64_t>(), s);
+    });
     if (e != hipSuccess) return hip_fail(e, "cmi_spgemm_csr: scan of the product counts");
     hipLaunchKernelGGL(spgemm_row_products_kernel, dim3(capped_grid(m + 1)), dim3(256), 0, s, m, a_entries, Ap, entry_start, row_start);
     CMI_LAUNCH_CHECK("spgemm row products");
@@ -304,8 +301,13 @@ static int spgemm_csr(int64_t m, int64_t k, int64_t n, int64_t a_entries, const 
     uint64_t *const keys = keys_block.get(), *const keys_sorted = keys_sorted_block.get();
     uint32_t *const perm = perm_block.get(), *const seg = seg_block.get();
     T *const vals = vals_block.get();
-    if (e == hipSuccess) e = rocprim::radix_sort_pairs(nullptr, sort_bytes, (const uint64_t *)keys, keys_sorted, position, perm, (unsigned)cap, 0u, 64u, s);
-    if (e == hipSuccess) e = rocprim::inclusive_scan(nullptr, scan_bytes, seg, seg, cap, rocprim::plus<uint32_t>(), s);
+    // the two rocPRIM calls of a slab, sized once for the largest slab and every key bit into ONE block (they run one after the other)
+    size_t count = cap;
+    unsigned end_bit = 64u;
+    auto sort = [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, (const uint64_t *)keys, keys_sorted, position, perm, (unsigned)count, 0u, end_bit, s); };
+    auto number_heads = [&](void *t, size_t &b) { return rocprim::inclusive_scan(t, b, seg, seg, count, rocprim::plus<uint32_t>(), s); };
+    if (e == hipSuccess) e = temp_size(sort, &sort_bytes);
+    if (e == hipSuccess) e = temp_size(number_heads, &scan_bytes);
     if (e == hipSuccess) e = sort_temp.alloc(std::max(sort_bytes, scan_bytes));
     if (e != hipSuccess) return hip_fail(e, "cmi_spgemm_csr: slab scratch");
     uint32_t *starts = reinterpret_cast<uint32_t *>(keys); // (the unsorted keys are dead once the sort has run)
@@ -316,16 +318,13 @@ static int spgemm_csr(int64_t m, int64_t k, int64_t n, int64_t a_entries, const 
     int st = CMI_SUCCESS;
     for (size_t b = 0; b + 1 < cut.size() && st == CMI_SUCCESS; b++) {
         const int64_t r0 = cut[b], r1 = cut[b + 1], P = start[r1] - start[r0];
-        const unsigned end_bit = (unsigned)(col_bits + spgemm_bits_for(r1 - r0)); // (P >= 1: W >= 1 and a slab ends at the last row it can hold)
+        count = (size_t)P;
+        end_bit = (unsigned)(col_bits + spgemm_bits_for(r1 - r0)); // (P >= 1: W >= 1 and a slab ends at the last row it can hold)
         size_t sb = sort_bytes, cb = scan_bytes;
-        hipLaunchKernelGGL(spgemm_expand_kernel<T>, dim3(blocks_for(P)), dim3(256), 0, s, P, start[r0], (int)r0, (int)r1, a_entries, Ap, Aj, Ax, Bp, Bj, Bx, (const int64_t *)entry_start, col_bits, col_mask, keys, vals);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = rocprim::radix_sort_pairs(sort_temp.get(), sb, (const uint64_t *)keys, keys_sorted, position, perm, (unsigned)P, 0u, end_bit, s);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(spgemm_heads_kernel, dim3(blocks_for(P)), dim3(256), 0, s, P, (const uint64_t *)keys_sorted, seg);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = rocprim::inclusive_scan(sort_temp.get(), cb, seg, seg, (size_t)P, rocprim::plus<uint32_t>(), s);
+        e = launch(spgemm_expand_kernel<T>, blocks_for(P), 256, 0, s, P, start[r0], (int)r0, (int)r1, a_entries, Ap, Aj, Ax, Bp, Bj, Bx, entry_start, col_bits, col_mask, keys, vals);
+        if (e == hipSuccess) e = sort(sort_temp.get(), sb);
+        if (e == hipSuccess) e = launch(spgemm_heads_kernel, blocks_for(P), 256, 0, s, P, keys_sorted, seg);
+        if (e == hipSuccess) e = number_heads(sort_temp.get(), cb);
         uint32_t unique = 0;
         if (e == hipSuccess) e = hipMemcpyAsync(&unique, seg + (P - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -348,12 +347,9 @@ static int spgemm_csr(int64_t m, int64_t k, int64_t n, int64_t a_entries, const 
             st = fail(CMI_ERROR_ALLOC, "cmi_spgemm_csr: out of host memory");
             break;
         }
-        hipLaunchKernelGGL(spgemm_starts_kernel, dim3(blocks_for(P)), dim3(256), 0, s, P, (const uint64_t *)keys_sorted, (const uint32_t *)seg, starts);
-        hipLaunchKernelGGL(spgemm_sum_kernel<T>, dim3(blocks_for(U)), dim3(256), 0, s, U, P, (const uint64_t *)keys_sorted, (const uint32_t *)perm,
-                           (const uint32_t *)starts, (const T *)vals, col_mask, Cj, Cx);
-        hipLaunchKernelGGL(spgemm_row_offsets_kernel, dim3(blocks_for(r1 - r0)), dim3(256), 0, s, r1 - r0, P, (int)r0, entries, col_bits,
-                           (const uint64_t *)keys_sorted, (const uint32_t *)seg, r->Cp.get());
-        e = hipGetLastError();
+        e = launch(spgemm_starts_kernel, blocks_for(P), 256, 0, s, P, keys_sorted, seg, starts);
+        if (e == hipSuccess) e = launch(spgemm_sum_kernel<T>, blocks_for(U), 256, 0, s, U, P, keys_sorted, perm, starts, vals, col_mask, Cj, Cx);
+        if (e == hipSuccess) e = launch(spgemm_row_offsets_kernel, blocks_for(r1 - r0), 256, 0, s, r1 - r0, P, (int)r0, entries, col_bits, keys_sorted, seg, r->Cp.get());
         if (e != hipSuccess) { st = hip_fail(e, "launch spgemm compress"); break; }
         entries += U;
         r->slabs++;

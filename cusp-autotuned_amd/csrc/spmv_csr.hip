@@ -537,8 +537,7 @@ int wave_partition_build(cmi_plan *p, const int *Ap, int k, hipStream_t s, int q
     device_array<int32_t> start;
     hipError_t e = start.alloc((size_t)(tiles + 1) * 2);
     if (e != hipSuccess) return hip_fail(e, "cmi_plan_create: wave partition");
-    hipLaunchKernelGGL(wave_partition_kernel, dim3((unsigned)ceil_div(rows + 1, 256)), dim3(256), 0, s, rows, Ap, q, tiles, start.get());
-    e = hipGetLastError();
+    e = launch(wave_partition_kernel, (unsigned)ceil_div(rows + 1, 256), 256, 0, s, rows, Ap, q, tiles, start.get());
     if (e == hipSuccess) e = hipStreamSynchronize(s); // (the plan is complete when cmi_plan_create returns, like every other plan)
     if (e != hipSuccess) return hip_fail(e, "cmi_plan_create: wave partition");
     p->wave_row_start = std::move(start);
@@ -659,22 +658,15 @@ int wavev_cols16_build(cmi_plan *p, const int *Aj, hipStream_t s)
         (void)hipGetLastError();
         shift.reset();
     }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(wavev_cols16_scan_kernel, dim3(grid), dim3(256), 0, s, p->wave_row_start.get(), tiles, Aj, base.get(), flag.dev(), shift.get(), L > 0 ? L : 1,
-                           shift_div_mul(L > 0 ? L : 1));
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess)
+        e = launch(wavev_cols16_scan_kernel, grid, 256, 0, s, p->wave_row_start.get(), tiles, Aj, base.get(), flag.dev(), shift.get(), L > 0 ? L : 1, shift_div_mul(L > 0 ? L : 1));
     if (e == hipSuccess) e = flag.fetch(s);
     if (e == hipSuccess && flag.host[0] == 0) {
         e = cols16.alloc((size_t)nnz + 8); // (zero padding: a vector load at the last entry stays inside the allocation)
         if (e == hipSuccess) e = hipMemsetAsync(cols16.get() + nnz, 0, 8 * sizeof(uint16_t), s);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(wavev_cols16_encode_kernel, dim3(grid), dim3(256), 0, s, p->wave_row_start.get(), tiles, Aj, base.get(), cols16.get());
-            e = hipGetLastError();
-        }
+        if (e == hipSuccess) e = launch(wavev_cols16_encode_kernel, grid, 256, 0, s, p->wave_row_start.get(), tiles, Aj, base.get(), cols16.get());
         if (e == hipSuccess && shift) {
-            hipLaunchKernelGGL(wavev_shift_count_kernel, dim3((unsigned)ceil_div(tiles, (int64_t)256)), dim3(256), 0, s, p->wave_row_start.get(), tiles, shift.get(), counts.dev());
-            e = hipGetLastError();
+            e = launch(wavev_shift_count_kernel, (unsigned)ceil_div(tiles, (int64_t)256), 256, 0, s, p->wave_row_start.get(), tiles, shift.get(), counts.dev());
             if (e == hipSuccess) e = counts.fetch(s);
         } else if (e == hipSuccess)
             e = hipStreamSynchronize(s);
@@ -1420,12 +1412,9 @@ int measure_row_lengths(int64_t rows, const int *Ap, hipStream_t s, int64_t *max
 {
     device_counters<unsigned long long, 4> out; // {longest row, entries in long rows, Ap[0], Ap[rows]}
     hipError_t e = out.open(s);
-    if (e == hipSuccess) {
-        int64_t blocks = ceil_div(rows, 256 * 4);
-        if (blocks > kCus * 8) blocks = kCus * 8;
-        hipLaunchKernelGGL(max_row_length_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(256), 0, s, rows, Ap, out.dev());
-        e = hipGetLastError();
-    }
+    int64_t blocks = ceil_div(rows, 256 * 4);
+    if (blocks > kCus * 8) blocks = kCus * 8;
+    if (e == hipSuccess) e = launch(max_row_length_kernel, (unsigned)(blocks < 1 ? 1 : blocks), 256, 0, s, rows, Ap, out.dev());
     if (e == hipSuccess) e = out.fetch(s);
     if (e != hipSuccess) return hip_fail(e, "row-length profile");
     *max_len = (int64_t)out.host[0];
@@ -1471,12 +1460,9 @@ int measure_column_locality(int64_t rows, int64_t cols, const int *Ap, const int
 {
     device_counters<unsigned long long, 2> out;
     hipError_t e = out.open(s);
-    if (e == hipSuccess) {
-        int64_t blocks = ceil_div(rows, 256);
-        if (blocks > kCus * 16) blocks = kCus * 16;
-        hipLaunchKernelGGL(column_locality_kernel, dim3((unsigned)(blocks < 1 ? 1 : blocks)), dim3(256), 0, s, rows, cols, Ap, Aj, halfwin, out.dev());
-        e = hipGetLastError();
-    }
+    int64_t blocks = ceil_div(rows, 256);
+    if (blocks > kCus * 16) blocks = kCus * 16;
+    if (e == hipSuccess) e = launch(column_locality_kernel, (unsigned)(blocks < 1 ? 1 : blocks), 256, 0, s, rows, cols, Ap, Aj, halfwin, out.dev());
     if (e == hipSuccess) e = out.fetch(s);
     if (e != hipSuccess) return hip_fail(e, "column locality profile");
     *inside = (int64_t)out.host[0];

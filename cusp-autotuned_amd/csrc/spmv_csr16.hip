@@ -84,19 +84,13 @@ int csr16_build(cmi_plan *p, const int *Ap, const int *Aj, hipStream_t s, int wa
     device_counters<int> flag; // != 0: a tile does not qualify
     hipError_t e = base.alloc((size_t)tiles);
     if (e == hipSuccess) e = flag.open(s);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(csr16_scan_kernel, dim3((unsigned)tiles), dim3(wave_k > 0 ? 64 : 256), 0, s, rows, Ap, Aj, rpb, pass_entries, base.get(), flag.dev());
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess) e = launch(csr16_scan_kernel, (unsigned)tiles, wave_k > 0 ? 64 : 256, 0, s, rows, Ap, Aj, rpb, pass_entries, base.get(), flag.dev());
     if (e == hipSuccess) e = flag.fetch(s);
     if (e == hipSuccess && flag.host[0] == 0) {
         // (nnz rounded up to whole 8-byte vectors + one: the kernel's last vector load stays inside the allocation)
         e = cols16.alloc((size_t)nnz + 8);
         if (e == hipSuccess) e = hipMemsetAsync(cols16.get(), 0, cols16.bytes(), s);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(csr16_encode_kernel, dim3((unsigned)tiles), dim3(wave_k > 0 ? 64 : 256), 0, s, rows, Ap, Aj, rpb, base.get(), cols16.get());
-            e = hipGetLastError();
-        }
+        if (e == hipSuccess) e = launch(csr16_encode_kernel, (unsigned)tiles, wave_k > 0 ? 64 : 256, 0, s, rows, Ap, Aj, rpb, base.get(), cols16.get());
         if (e == hipSuccess) e = hipStreamSynchronize(s);
     }
     if (e != hipSuccess) return hip_fail(e, "cmi_plan_create: 16-bit column copy");
@@ -162,12 +156,9 @@ int csr16_pack(cmi_plan *p, const int *Ap, const void *values, hipStream_t s)
     const int64_t bytes = wtiles * pack16_span(k, vbytes);
     device_array<unsigned char> buf;
     hipError_t e = buf.alloc((size_t)bytes);
-    if (e == hipSuccess) {
-        const unsigned grid = (unsigned)ceil_div(wtiles, 4);
-        if (p->dtype == CMI_F64) hipLaunchKernelGGL((csr16_pack_kernel<double>), dim3(grid), dim3(256), 0, s, p->rows, wtiles, k, Ap, p->csr16_cols.get(), p->csr16_base.get(), (const double *)values, buf.get());
-        else hipLaunchKernelGGL((csr16_pack_kernel<float>), dim3(grid), dim3(256), 0, s, p->rows, wtiles, k, Ap, p->csr16_cols.get(), p->csr16_base.get(), (const float *)values, buf.get());
-        e = hipGetLastError();
-    }
+    const unsigned grid = (unsigned)ceil_div(wtiles, 4);
+    if (e == hipSuccess && p->dtype == CMI_F64) e = launch(csr16_pack_kernel<double>, grid, 256, 0, s, p->rows, wtiles, k, Ap, p->csr16_cols.get(), p->csr16_base.get(), (const double *)values, buf.get());
+    else if (e == hipSuccess) e = launch(csr16_pack_kernel<float>, grid, 256, 0, s, p->rows, wtiles, k, Ap, p->csr16_cols.get(), p->csr16_base.get(), (const float *)values, buf.get());
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return hip_fail(e, "cmi_plan_create: packed wave tiles");
     p->csr16_cols.reset(); // (only now: the packed buffer is complete)

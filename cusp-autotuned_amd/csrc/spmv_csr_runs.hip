@@ -22,8 +22,7 @@
 // in ONE plan-owned buffer -- [pieces | pad to 16 | values | pad to 16] -- so that a wave's requests are one contiguous span of HBM
 // (one stream reads at 7.1-7.3 TB/s, two arrays side by side at 6.4-6.6).  The plan then owns a copy of the values:
 // refresh the values => make a new plan (cmi_plan_validate checks them).
-#include "common.h"
-#include <rocprim/rocprim.hpp>
+#include "setup_scan.h"
 
 namespace cmi {
 
@@ -176,13 +175,11 @@ runs_pack_kernel(int64_t tiles, int32_t *__restrict__ start, const int *__restri
     if (lane == 0) start[4 * t + 3] = off16[t];
 }
 
-static int device_exclusive_scan(const int *in, int *out, size_t n, hipStream_t s)
+// counts[0 .. n] -> their exclusive sums, in place, and the stream idle: the host reads them, and the temporary goes on return
+static int offsets_in_place(int *counts, int64_t n, hipStream_t s)
 {
-    size_t bytes = 0;
-    device_array<unsigned char> tmp;
-    hipError_t e = rocprim::exclusive_scan(nullptr, bytes, in, out, 0, n, rocprim::plus<int>(), s);
-    if (e == hipSuccess) e = tmp.alloc(bytes ? bytes : 16);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(tmp.get(), bytes, in, out, 0, n, rocprim::plus<int>(), s);
+    device_array<unsigned char> temp;
+    hipError_t e = exclusive_offsets(temp, counts, counts, n, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     return e == hipSuccess ? (int)CMI_SUCCESS : hip_fail(e, "cmi_plan_create: run-compressed columns (scan)");
 }
@@ -215,15 +212,12 @@ int csr_runs_build(cmi_plan *p, const int *Ap, const int *Aj, int v, double min_
     // where pieces of 3 have none; profiles/r04_long_rows_pmc.json: LDS index unit 71 % busy on ldoor-like).  Cap 3 when it costs at most
     // 3 % more pieces than cap 4, unless `cap_asked` (a plan's config.threads_per_row, else the rule's cap) is 3 or 4.  One walk counts both.
     int cap = kRunCap;
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL((runs_tile_kernel<false>), dim3(tgrid), dim3(256), 0, s, rows, Ap, Aj, rpb, kRunCap, count, count3, totals.dev(), (const int *)nullptr, (uint32_t *)nullptr);
-        e = hipGetLastError();
-    }
+    if (e == hipSuccess) e = launch(runs_tile_kernel<false>, tgrid, 256, 0, s, rows, Ap, Aj, rpb, kRunCap, count, count3, totals.dev(), nullptr, nullptr);
     if (e == hipSuccess) e = totals.fetch(s);
     if (e == hipSuccess && (cap_asked == 3 || (cap_asked != 4 && (double)totals.host[1] <= 1.03 * (double)totals.host[0]))) cap = 3;
     int *chosen = cap == 3 ? count3 : count; // the per-row counts that are scanned, in place, into piece offsets
     int st = e == hipSuccess ? (int)CMI_SUCCESS : hip_fail(e, "cmi_plan_create: run-compressed columns");
-    if (st == CMI_SUCCESS) st = device_exclusive_scan(chosen, chosen, (size_t)rows + 1, s); // chosen[r] <- pieces before row r
+    if (st == CMI_SUCCESS) st = offsets_in_place(chosen, rows, s); // chosen[r] <- pieces before row r
     const int total = (int)(cap == 3 ? totals.host[1] : totals.host[0]); // (= chosen[rows]: the totals were summed by the same walk)
     device_array<uint32_t> pieces;
     device_array<int32_t> start;
@@ -234,11 +228,8 @@ int csr_runs_build(cmi_plan *p, const int *Ap, const int *Aj, int v, double min_
         e = pieces.alloc((size_t)total + 64);
         if (e == hipSuccess) e = hipMemsetAsync(pieces.get() + total, 0, 64 * sizeof(uint32_t), s);
         if (e == hipSuccess) e = start.alloc((size_t)(tiles + 1) * 4);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL((runs_tile_kernel<true>), dim3(tgrid), dim3(256), 0, s, rows, Ap, Aj, rpb, cap, (int *)nullptr, (int *)nullptr, (unsigned long long *)nullptr, (const int *)chosen, pieces.get());
-            hipLaunchKernelGGL(runs_partition_kernel, dim3((unsigned)ceil_div(rows + 1, 256)), dim3(256), 0, s, rows, Ap, (const int *)chosen, q, tiles, start.get());
-            e = hipGetLastError();
-        }
+        if (e == hipSuccess) e = launch(runs_tile_kernel<true>, tgrid, 256, 0, s, rows, Ap, Aj, rpb, cap, nullptr, nullptr, nullptr, chosen, pieces.get());
+        if (e == hipSuccess) e = launch(runs_partition_kernel, (unsigned)ceil_div(rows + 1, 256), 256, 0, s, rows, Ap, chosen, q, tiles, start.get());
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) st = hip_fail(e, "cmi_plan_create: run-compressed columns");
     }
@@ -249,12 +240,9 @@ int csr_runs_build(cmi_plan *p, const int *Ap, const int *Aj, int v, double min_
         e = spans.alloc((size_t)tiles + 1);
         int *const span = spans.get();
         if (e == hipSuccess) e = hipMemsetAsync(span + tiles, 0, sizeof(int), s);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(runs_span_kernel, dim3((unsigned)ceil_div(tiles, 256)), dim3(256), 0, s, tiles, start.get(), p->dtype == CMI_F64 ? 2 : 4, span);
-            e = hipGetLastError();
-        }
+        if (e == hipSuccess) e = launch(runs_span_kernel, (unsigned)ceil_div(tiles, 256), 256, 0, s, tiles, start.get(), p->dtype == CMI_F64 ? 2 : 4, span);
         if (e != hipSuccess) st = hip_fail(e, "cmi_plan_create: packed tiles");
-        if (st == CMI_SUCCESS) st = device_exclusive_scan(span, span, (size_t)tiles + 1, s);
+        if (st == CMI_SUCCESS) st = offsets_in_place(span, tiles, s);
         int end16 = 0;
         if (st == CMI_SUCCESS) {
             e = hipMemcpy(&end16, span + tiles, sizeof(int), hipMemcpyDeviceToHost);
@@ -264,12 +252,9 @@ int csr_runs_build(cmi_plan *p, const int *Ap, const int *Aj, int v, double min_
         if (st == CMI_SUCCESS) {
             e = packed.alloc((size_t)end16 * 16 + 64 * 16); // (+ slack: a wave's clamped request never leaves the buffer)
             if (e == hipSuccess) e = hipMemsetAsync(packed.get() + (size_t)end16 * 16, 0, 64 * 16, s);
-            if (e == hipSuccess) {
-                const unsigned grid = (unsigned)ceil_div(tiles + 1, 4);
-                if (p->dtype == CMI_F64) hipLaunchKernelGGL((runs_pack_kernel<double>), dim3(grid), dim3(256), 0, s, tiles, start.get(), span, pieces.get(), (const double *)values, packed.get());
-                else hipLaunchKernelGGL((runs_pack_kernel<float>), dim3(grid), dim3(256), 0, s, tiles, start.get(), span, pieces.get(), (const float *)values, packed.get());
-                e = hipGetLastError();
-            }
+            const unsigned grid = (unsigned)ceil_div(tiles + 1, 4);
+            if (e == hipSuccess && p->dtype == CMI_F64) e = launch(runs_pack_kernel<double>, grid, 256, 0, s, tiles, start.get(), span, pieces.get(), (const double *)values, packed.get());
+            else if (e == hipSuccess) e = launch(runs_pack_kernel<float>, grid, 256, 0, s, tiles, start.get(), span, pieces.get(), (const float *)values, packed.get());
             if (e == hipSuccess) e = hipStreamSynchronize(s);
             if (e != hipSuccess) st = hip_fail(e, "cmi_plan_create: packed tiles");
         }
