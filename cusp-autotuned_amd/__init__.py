@@ -30,6 +30,7 @@ from .binding import (  # noqa: F401
     csr_abs_row_sums, ell_abs_row_sums, dia_abs_row_sums, random_fill, blas_scal_recip,
     csr_strength_symmetric, csr_scale_rows, aggregates_fit, csr_elementwise, relax_jacobi_presmooth,
     csr_ring_max, maximal_independent_set, mis_aggregate,
+    bfs_levels_per_read, breadth_first_search, pseudo_peripheral_vertex, symmetric_rcm, gather, scatter,
     Comm, OP_SUM, OP_MAX, OP_MIN, csr_column_span,
 )
 from .matrices import (  # noqa: F401

@@ -267,6 +267,14 @@ def _declare(L):
     L.cmi_csr_ring_max_u64.argtypes = [i64, i64, vp, vp, vp, vp, vp]
     L.cmi_csr_maximal_independent_set.argtypes = [i64, i64, vp, vp, c_int, ctypes.c_uint64, vp, POINTER(c_int64), POINTER(c_int), vp]
     L.cmi_csr_mis_aggregate.argtypes = [i64, i64, vp, vp, ctypes.c_uint64, vp, vp, POINTER(c_int64), vp]
+    # breadth-first search, pseudo-peripheral vertex, level ordering, gather / scatter (csrc/bfs.hip)
+    L.cmi_bfs_levels_per_read.argtypes = []
+    L.cmi_csr_breadth_first_search.argtypes = [i64, i64, vp, vp, i64, c_int, vp, POINTER(c_int64), POINTER(c_int), vp]
+    L.cmi_csr_pseudo_peripheral_vertex.argtypes = [i64, i64, vp, vp, i64, vp, POINTER(c_int64), POINTER(c_int), vp]
+    L.cmi_csr_symmetric_rcm.argtypes = [i64, i64, vp, vp, i64, vp, POINTER(c_int64), vp]
+    for suf in ("i32", "f32", "f64"):
+        getattr(L, f"cmi_gather_{suf}").argtypes = [i64, i64, vp, vp, vp, vp]
+        getattr(L, f"cmi_scatter_{suf}").argtypes = [i64, i64, vp, vp, vp, vp]
 
 
 def lib():
@@ -560,6 +568,70 @@ def mis_aggregate(C, seed=0, stream=None):
     count = c_int64(0)
     check(lib().cmi_csr_mis_aggregate(num_rows, Aj.numel(), _ptr(Ap), _ptr(Aj), int(seed), _ptr(aggregates), _ptr(mis), byref(count), _stream(stream)))
     return aggregates, mis, int(count.value)
+
+
+def bfs_levels_per_read():
+    """cmi_bfs_levels_per_read: the expansion launches of a search between two host reads of its counters."""
+    return int(lib().cmi_bfs_levels_per_read())
+
+
+def breadth_first_search(n, Ap, Aj, src, mark_levels=True, stream=None):
+    """cmi_csr_breadth_first_search from `src` on the stored pattern (n, Ap, Aj) of a square CSR matrix, edges directed along
+    the rows.  Returns (labels int32, reached, depth): the levels (-1: not reached), or with mark_levels=False the
+    predecessors (-2 the source, -1 not reached, else the smallest-numbered vertex of the previous level with an edge to it)."""
+    import torch
+    n, Ap, Aj = _pattern((n, Ap, Aj), "breadth_first_search")
+    labels = torch.empty(n, dtype=torch.int32, device=Ap.device)
+    reached, depth = c_int64(0), c_int(0)
+    check(lib().cmi_csr_breadth_first_search(n, Aj.numel(), _ptr(Ap), _ptr(Aj), int(src), int(bool(mark_levels)), _ptr(labels), byref(reached), byref(depth),
+                                             _stream(stream)))
+    return labels, int(reached.value), int(depth.value)
+
+
+def pseudo_peripheral_vertex(n, Ap, Aj, start=0, stream=None):
+    """cmi_csr_pseudo_peripheral_vertex: searches from `start` until the depth stops growing.  Returns (vertex, levels int32
+    of the last search, searches)."""
+    import torch
+    n, Ap, Aj = _pattern((n, Ap, Aj), "pseudo_peripheral_vertex")
+    levels = torch.empty(n, dtype=torch.int32, device=Ap.device)
+    vertex, searches = c_int64(0), c_int(0)
+    check(lib().cmi_csr_pseudo_peripheral_vertex(n, Aj.numel(), _ptr(Ap), _ptr(Aj), int(start), _ptr(levels), byref(vertex), byref(searches), _stream(stream)))
+    return int(vertex.value), levels, int(searches.value)
+
+
+def symmetric_rcm(n, Ap, Aj, start=0, stream=None):
+    """cmi_csr_symmetric_rcm: the level ordering from a pseudo-peripheral vertex.  Returns (permutation int32 with
+    permutation[v] = the new number of v, vertex)."""
+    import torch
+    n, Ap, Aj = _pattern((n, Ap, Aj), "symmetric_rcm")
+    permutation = torch.empty(n, dtype=torch.int32, device=Ap.device)
+    vertex = c_int64(0)
+    check(lib().cmi_csr_symmetric_rcm(n, Aj.numel(), _ptr(Ap), _ptr(Aj), int(start), _ptr(permutation), byref(vertex), _stream(stream)))
+    return permutation, int(vertex.value)
+
+
+def _map_copy(kind, map, x, m, stream):
+    import torch
+    _need(map, "map", torch.int32)
+    _need(x, "x")
+    suffix = "i32" if x.dtype == torch.int32 else _suffix(x)
+    n = map.numel()
+    if x.numel() != (m if kind == "gather" else n):
+        raise ValueError(f"{kind}: x must have {'m' if kind == 'gather' else 'as many'} elements{'' if kind == 'gather' else ' as map'}")
+    out = torch.empty(n if kind == "gather" else m, dtype=x.dtype, device=x.device)
+    check(getattr(lib(), f"cmi_{kind}_{suffix}")(n, int(m), _ptr(map), _ptr(x), _ptr(out), _stream(stream)))
+    return out
+
+
+def gather(map, x, m, stream=None):
+    """cmi_gather_*: out[i] = x[map[i]]; x has m elements (int32, float32 or float64), map is int32 with entries in [0, m)."""
+    return _map_copy("gather", map, x, m, stream)
+
+
+def scatter(map, x, m, stream=None):
+    """cmi_scatter_*: out[map[i]] = x[i]; out has m elements (those no entry names are left uninitialised), map is int32 with
+    entries in [0, m)."""
+    return _map_copy("scatter", map, x, m, stream)
 
 
 def _plan_handle(plan):

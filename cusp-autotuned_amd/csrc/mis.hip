@@ -158,31 +158,15 @@ __global__ void __launch_bounds__(kAmgBlock) mis_flags_kernel(int64_t n, int64_t
     if (i < count) flag[i] = (i < n && (!state || state[i] == kStateIn)) ? 1 : 0;
 }
 
-// One device allocation per call, carved in 256-byte steps: a dozen allocate / free pairs of N-sized arrays cost more than
-// the sweeps they serve.  take() returns null once the reservation is used up (the caller sized it: a bug, reported as one).
-struct mis_arena {
-    device_array<char> block; // released with the arena, on every path out of the call
-    size_t used = 0;
-    static size_t padded(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-    hipError_t open(size_t bytes) { return block.alloc(bytes); }
-    template <typename T> T *take(size_t count)
-    {
-        const size_t bytes = padded(count * sizeof(T));
-        if (!block || used + bytes > block.bytes()) return nullptr;
-        T *p = reinterpret_cast<T *>(block.get() + used);
-        used += bytes;
-        return p;
-    }
-};
 static size_t mis_states_bytes(int64_t n, int k)
 {
-    return mis_arena::padded((size_t)n * sizeof(int)) + mis_arena::padded(kCounters * sizeof(int)) + (k >= 2 ? 3 : 2) * mis_arena::padded((size_t)n * sizeof(key_t));
+    return device_arena::padded((size_t)n * sizeof(int)) + device_arena::padded(kCounters * sizeof(int)) + (k >= 2 ? 3 : 2) * device_arena::padded((size_t)n * sizeof(key_t));
 }
 
 // The states of MIS(k), k >= 1, on n >= 1 nodes, left in *state_out (taken from `arena`, which holds mis_states_bytes(n, k) at
 // least, as are the key arrays handed back for reuse).  INVALID_VALUE on a column out of range, NOT_SUPPORTED beyond n + 1
 // rounds; the stream is idle on return.
-static int mis_states(mis_arena &arena, int64_t n, int64_t nnz, const int *Ap, const int *Aj, int k, uint64_t seed, int **state_out, key_t *keys_out[3],
+static int mis_states(device_arena &arena, int64_t n, int64_t nnz, const int *Ap, const int *Aj, int k, uint64_t seed, int **state_out, key_t *keys_out[3],
                       int64_t *set_size, int *rounds_out, hipStream_t s)
 {
     int *state = arena.take<int>((size_t)n), *counters = arena.take<int>(kCounters);
@@ -251,7 +235,7 @@ static int maximal_independent_set(int64_t num_rows, int64_t num_entries, const 
     *set_size = 0;
     *rounds = 0;
     if (num_rows == 0) return CMI_SUCCESS;
-    mis_arena arena;
+    device_arena arena;
     int *state = nullptr;
     if (k > 0) {
         const hipError_t ea = arena.open(mis_states_bytes(num_rows, k));
@@ -317,12 +301,12 @@ static int mis_aggregate(int64_t num_rows, int64_t num_entries, const int *Ap, c
     if (num_rows == 0) return CMI_SUCCESS;
     hipStream_t s = as_stream(stream);
     const int64_t n = num_rows;
-    mis_arena arena;
+    device_arena arena;
     size_t scan_bytes = 0; // of one exclusive scan of n + 1 ints (both scans have this shape)
     hipError_t e = temp_size(offsets_scan<int>(nullptr, nullptr, n, s), &scan_bytes);
     if (e == hipSuccess)
-        e = arena.open(mis_states_bytes(n, 2) + 5 * mis_arena::padded((size_t)(n + 1) * sizeof(int)) + mis_arena::padded((size_t)n * sizeof(int)) +
-                                mis_arena::padded(scan_bytes));
+        e = arena.open(mis_states_bytes(n, 2) + 5 * device_arena::padded((size_t)(n + 1) * sizeof(int)) + device_arena::padded((size_t)n * sizeof(int)) +
+                                device_arena::padded(scan_bytes));
     if (e != hipSuccess) return hip_fail(e, "cmi_csr_mis_aggregate: scratch");
     int *state = nullptr, rounds = 0;
     key_t *keys[3];

@@ -608,6 +608,74 @@ int cmi_csr_maximal_independent_set(int64_t num_rows, int64_t num_entries, const
                                     int32_t *stencil, int64_t *set_size, int *rounds, void *stream);
 int cmi_csr_mis_aggregate(int64_t num_rows, int64_t num_entries, const int32_t *Ap, const int32_t *Aj, uint64_t seed, int32_t *aggregates,
                           int32_t *mis, int64_t *num_aggregates, void *stream);
+/* Breadth-first search, a pseudo-peripheral vertex, the level ordering behind cusp::graph::symmetric_rcm, and the gather /
+ * scatter through an index map that cusp::permutation_matrix uses (bfs.hip).  All integer work or pure data
+ * movement: exact in any order.  The graph is the stored pattern of a square CSR matrix: every stored entry of row u is an
+ * edge u -> column whatever its value (an explicit zero is an edge), columns may repeat, rows may be unsorted, a self-loop
+ * is harmless.  Edges are DIRECTED: the search follows rows, as the reference's host loop does.  A column equal to -1 is
+ * skipped, as in that loop; any other column outside [0, num_rows) is never used as an address.  Row offsets are clamped to
+ * [0, num_entries] before they address anything; a decreasing pair is an empty row.  Rejected with CMI_ERROR_INVALID_VALUE
+ * before any device call: negative sizes, sizes beyond the CSR ceiling (rows < INT32_MAX, entries <= INT32_MAX - 65536), null
+ * arrays or host words, a source / start vertex outside [0, num_rows) (so num_rows == 0 is always refused).
+ *
+ * cmi_csr_breadth_first_search:
+ *     labels[i] = -1 for every i;  *reached = 0;  *depth = -1
+ *     if num_entries == 0: return                                   (the reference's host behaviour)
+ *     level[src] = 0;  d = 0
+ *     while level d is not empty:
+ *         for u of level d, for jj in [Ap[u], Ap[u + 1]) with j = Aj[jj] != -1:
+ *             if level[j] is unset: level[j] = d + 1
+ *             if level[j] == d + 1: pred[j] = min(pred[j], u)
+ *         d += 1
+ *     *reached = the number of vertices with a level;  *depth = the largest level
+ *     mark_levels != 0: labels = level.   mark_levels == 0: labels[src] = -2, labels[j] = pred[j] for the other reached vertices.
+ *   The predecessor is THE SMALLEST-NUMBERED VERTEX OF THE PREVIOUS LEVEL THAT HAS AN EDGE TO j.  That rule is this library's
+ *   own and holds in both memory spaces of the header layer (one algorithm everywhere, as for the maximal independent set):
+ *   the reference's host loop records the first discoverer in queue order, and its device path whichever thread wins.
+ *   A column other than -1 outside the matrix in a row the search reaches: CMI_ERROR_INVALID_VALUE, labels all -1, the host
+ *   words as above.  In a row the search never reaches it is not looked at.
+ *   Method: one launch per level expands a frontier queue (a wave per 64 slots; a row of up to 64 entries on its own lane,
+ *   a longer row on the whole wave); a vertex is labelled by atomicCAS(&level[j], -1, d + 1) at device scope and the winner
+ *   is appended to the next queue, one atomicAdd per wave and step; predecessors are an atomicMin.  No kernel waits for
+ *   another workgroup.  Every launch takes its frontier's size from device memory and has a fixed grid, so a launch on an
+ *   empty frontier does nothing, and the host reads the counters once per cmi_bfs_levels_per_read() levels.  Scratch: 12 (16
+ *   with predecessors) bytes per vertex, ONE device allocation, released on every path out.  Synchronises the stream.
+ * cmi_csr_pseudo_peripheral_vertex: the reference's loop (cusp/system/detail/generic/graph/pseudo_peripheral.h),
+ *     x = start;  delta = 0;  *searches = 0
+ *     repeat:
+ *         levels = the levels of the search from x;  depth = their maximum;  *searches += 1
+ *         y = the vertex with levels[y] == depth whose row length Ap[y + 1] - Ap[y] (clamped as above) is smallest,
+ *             the smallest index among equals
+ *         if depth <= delta: *vertex = y; return
+ *         x = y;  delta = depth
+ *   with two deviations.  `start` is an argument (the reference draws rand() % num_rows).  The row lengths compared are those
+ *   of the last-level vertices themselves: the reference gathers row_lengths[0 .. count), the lengths of the FIRST count
+ *   vertices of the graph, which is a bug.  num_entries == 0: every level is -1, so vertex 0 after one search.  y is one
+ *   reduction of  row length << 32 | index  (an integer minimum).  levels (int32, device, num_rows) is written at the very end.
+ * cmi_csr_symmetric_rcm: levels as above from `start`; the vertices ordered by (level, index), vertices the last search did
+ *   not reach (level -1) first -- the reference's stable sort_by_key of the levels; permutation[v] = the position of v.  The
+ *   order is unique, so the device radix sort of  level + 1 << 32 | index  gives it.  Like the reference this is a LEVEL
+ *   ORDERING from a pseudo-peripheral vertex, not a reversed Cuthill-McKee with degree order inside the levels.  *vertex is
+ *   the pseudo-peripheral vertex.  Scratch: 28 bytes per vertex plus the sort's, one allocation.
+ * cmi_gather_* / cmi_scatter_*:
+ *     gather:   out[i] = in[map[i]]  for i < n          scatter:   out[map[i]] = in[i]  for i < n
+ *   with map entries in [0, m), m being the length of the array they index.  An entry outside is never used as an address;
+ *   after the launch the call returns CMI_ERROR_INVALID_VALUE (one flag read; the other elements have moved).  That a scatter
+ *   map holds no value twice is the caller's promise.  out must not be in.  n == 0: success, nothing done.
+ * Callers find the feature by the symbols (CMI_VERSION is unchanged). */
+int cmi_bfs_levels_per_read(void);
+int cmi_csr_breadth_first_search(int64_t num_rows, int64_t num_entries, const int32_t *Ap, const int32_t *Aj, int64_t src, int mark_levels,
+                                 int32_t *labels, int64_t *reached, int *depth, void *stream);
+int cmi_csr_pseudo_peripheral_vertex(int64_t num_rows, int64_t num_entries, const int32_t *Ap, const int32_t *Aj, int64_t start,
+                                     int32_t *levels, int64_t *vertex, int *searches, void *stream);
+int cmi_csr_symmetric_rcm(int64_t num_rows, int64_t num_entries, const int32_t *Ap, const int32_t *Aj, int64_t start, int32_t *permutation,
+                          int64_t *vertex, void *stream);
+int cmi_gather_i32(int64_t n, int64_t m, const int32_t *map, const int32_t *in, int32_t *out, void *stream);
+int cmi_gather_f32(int64_t n, int64_t m, const int32_t *map, const float *in, float *out, void *stream);
+int cmi_gather_f64(int64_t n, int64_t m, const int32_t *map, const double *in, double *out, void *stream);
+int cmi_scatter_i32(int64_t n, int64_t m, const int32_t *map, const int32_t *in, int32_t *out, void *stream);
+int cmi_scatter_f32(int64_t n, int64_t m, const int32_t *map, const float *in, float *out, void *stream);
+int cmi_scatter_f64(int64_t n, int64_t m, const int32_t *map, const double *in, double *out, void *stream);
 /* A CSR row sweep with a fixed elementwise write-back (spmv_csr_epilogue.hip): the smoothers that are an SpMV followed at
  * once by passes over the vector it wrote, in one launch.  s_i is row i's sum exactly as cmi_spmv_csr_* forms it: from
  * T(0), entries in storage order, multiply then add, by one lane; the same lane evaluates the expression once and
