@@ -172,6 +172,12 @@ def _declare(L):
     L.cmi_cg_direction_f32.argtypes = [i64, vp, vp, vp, vp, vp]
     L.cmi_cg_direction_x_f32.argtypes = [i64, vp, vp, vp, vp, vp, vp, vp]
     L.cmi_blas_dotd_f32.argtypes = [i64, vp, vp, vp, vp, vp]
+    for suf, sc in (("f64", c_double), ("f32", c_float)):   # the multi-shift solver steps (csrc/krylov_m.hip)
+        getattr(L, f"cmi_cg_m_coefficients_{suf}").argtypes = [i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        getattr(L, f"cmi_cg_m_update_xp_{suf}").argtypes = [i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        getattr(L, f"cmi_bicgstab_m_s_{suf}").argtypes = [i64, sc, sc, vp, vp, vp, vp]
+        getattr(L, f"cmi_bicgstab_m_coefficients_{suf}").argtypes = [i64, sc, sc, sc, sc, sc, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        getattr(L, f"cmi_bicgstab_m_update_xs_{suf}").argtypes = [i64, i64, i64] + [vp] * 14
     L.cmi_count_zeros_f64.argtypes = [i64, vp, POINTER(c_int64), vp]
     L.cmi_count_zeros_f32.argtypes = [i64, vp, POINTER(c_int64), vp]
     L.cmi_tuning_hyb_rule.argtypes = [c_int, POINTER(c_int), POINTER(c_double), POINTER(c_int64)]
@@ -1347,6 +1353,54 @@ def bicgstab_p(rho_new, rho, d1, d2, d3, r, AMp, p, stream=None):
     """beta = (rho_new/rho) (alpha/omega); p = r + beta (p - omega AMp)."""
     check(getattr(lib(), "cmi_bicgstab_p_" + _suffix(p))(p.numel(), _ptr(rho_new), _ptr(rho), _ptr(d1), _ptr(d2), _ptr(d3), _ptr(r), _ptr(AMp), _ptr(p),
                                                           _stream(stream)))
+
+
+# the multi-shift solver steps (csrc/krylov_m.hip): x, p_s and s_s hold shift s at [s ld, s ld + n); sigma and the per-shift coefficient
+# tensors hold num_shifts values of the vectors' dtype
+def _need_all(who, dtype, **tensors):
+    for name, t in tensors.items():
+        _need(t, f"{who}: {name}", dtype)
+
+
+def cg_m_coefficients(rsq_old, pAp, rsq_new, state, sigma, zeta_m1, zeta_0, beta_s, alpha_s, stream=None):
+    """beta_0 = -(rsq_old/pAp), alpha_0 = rsq_new/rsq_old (1-element float64 device tensors); per shift: the next zeta (clamped) and beta_s from
+    (state = previous (beta_0, alpha_0), zeta_m1, zeta_0, sigma), alpha_s, the rotation of zeta; then state <- (beta_0, alpha_0)."""
+    import torch
+    _need_all("cg_m_coefficients", torch.float64, rsq_old=rsq_old, pAp=pAp, rsq_new=rsq_new)
+    _need_all("cg_m_coefficients", state.dtype, state=state, sigma=sigma, zeta_m1=zeta_m1, zeta_0=zeta_0, beta_s=beta_s, alpha_s=alpha_s)
+    check(getattr(lib(), "cmi_cg_m_coefficients_" + _suffix(state))(sigma.numel(), _ptr(rsq_old), _ptr(pAp), _ptr(rsq_new), _ptr(state), _ptr(sigma), _ptr(zeta_m1),
+                                                                     _ptr(zeta_0), _ptr(beta_s), _ptr(alpha_s), _stream(stream)))
+
+
+def cg_m_update_xp(n, ld, state, beta_s, alpha_s, zeta_0, r, p0, x, p_s, stream=None):
+    """p0 <- r + state[1] p0 (p0 None: skipped); per shift x_s <- x_s - beta_s p_s (the old p_s), p_s <- zeta_0[s] r + alpha_s p_s."""
+    _need_all("cg_m_update_xp", r.dtype, state=state, beta_s=beta_s, alpha_s=alpha_s, zeta_0=zeta_0, r=r, p0=p0, x=x, p_s=p_s)
+    check(getattr(lib(), "cmi_cg_m_update_xp_" + _suffix(r))(int(n), beta_s.numel(), int(ld), _ptr(state), _ptr(beta_s), _ptr(alpha_s), _ptr(zeta_0), _ptr(r),
+                                                              _ptr(p0), _ptr(x), _ptr(p_s), _stream(stream)))
+
+
+def bicgstab_m_s(alpha_1, chi_0, r_1, As, s_0, stream=None):
+    """s_0 <- r_1 + alpha_1 (s_0 - chi_0 As); the scalars by value."""
+    _need_all("bicgstab_m_s", s_0.dtype, r_1=r_1, As=As, s_0=s_0)
+    check(getattr(lib(), "cmi_bicgstab_m_s_" + _suffix(s_0))(s_0.numel(), float(alpha_1), float(chi_0), _ptr(r_1), _ptr(As), _ptr(s_0), _stream(stream)))
+
+
+def bicgstab_m_coefficients(beta_m1, beta_0, alpha_old, alpha_new, chi_0, sigma, zeta_m1, zeta_0, rho_0, zeta_1, beta_s, chi_s, rho_1, alpha_s, stream=None):
+    """Per shift: zeta_1 (clamped) and beta_s from the old alpha, chi_s and rho_1, alpha_s from the new alpha; nothing rotates."""
+    _need_all("bicgstab_m_coefficients", sigma.dtype, sigma=sigma, zeta_m1=zeta_m1, zeta_0=zeta_0, rho_0=rho_0, zeta_1=zeta_1, beta_s=beta_s, chi_s=chi_s,
+              rho_1=rho_1, alpha_s=alpha_s)
+    check(getattr(lib(), "cmi_bicgstab_m_coefficients_" + _suffix(sigma))(sigma.numel(), float(beta_m1), float(beta_0), float(alpha_old), float(alpha_new),
+                                                                           float(chi_0), _ptr(sigma), _ptr(zeta_m1), _ptr(zeta_0), _ptr(rho_0), _ptr(zeta_1),
+                                                                           _ptr(beta_s), _ptr(chi_s), _ptr(rho_1), _ptr(alpha_s), _stream(stream)))
+
+
+def bicgstab_m_update_xs(n, ld, beta_s, chi_s, rho_0, zeta_m1, zeta_0, alpha_s, rho_1, zeta_1, r_0, r_1, w_1, x, s_s, stream=None):
+    """Per shift x_s and s_s (KERNEL_XS), then the rotation zeta_m1 <- zeta_0 <- zeta_1, rho_0 <- rho_1 (a tail launch of the same call)."""
+    _need_all("bicgstab_m_update_xs", x.dtype, beta_s=beta_s, chi_s=chi_s, rho_0=rho_0, zeta_m1=zeta_m1, zeta_0=zeta_0, alpha_s=alpha_s, rho_1=rho_1, zeta_1=zeta_1,
+              r_0=r_0, r_1=r_1, w_1=w_1, x=x, s_s=s_s)
+    check(getattr(lib(), "cmi_bicgstab_m_update_xs_" + _suffix(x))(int(n), beta_s.numel(), int(ld), _ptr(beta_s), _ptr(chi_s), _ptr(rho_0), _ptr(zeta_m1), _ptr(zeta_0),
+                                                                    _ptr(alpha_s), _ptr(rho_1), _ptr(zeta_1), _ptr(r_0), _ptr(r_1), _ptr(w_1), _ptr(x), _ptr(s_s),
+                                                                    _stream(stream)))
 
 
 def cr_xr(rz, yy, p, y, x, r, rr, workspace, update_r=True, stream=None, mirror=None):

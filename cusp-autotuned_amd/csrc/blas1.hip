@@ -9,14 +9,12 @@
 // leaves one partial per workgroup in the caller's workspace, stage 2 (one workgroup) folds them in
 // index order and writes the scalar to device memory -- no host sync, no atomics, no per-call
 // allocation (the reference's Thrust reductions allocate temporaries and synchronise every call).
-#include "common.h"
+#include "blas1_shared.h" // kBlasBlock, vec16, st_policy, stream_grid, fused_grid: shared with krylov_m.hip
 
 namespace cmi {
 
-constexpr int kBlasBlock = 256;
 constexpr int kCgStorePolicy = 1; // which vectors a CG step stores with the nt hint (bit 0 x, bit 1 p, bit 2 r): x; see the note in cg_update_kernel
 constexpr int kBlasMaxGrid = kCus * 8;   // reductions: 2048 partials
-constexpr int kFusedMaxGrid = 1 << 16;           // fused update+reduce kernels store too: near one-shot grids (one partial per workgroup; the folds take up to kPartialCapacity)
 
 // reductions: a fixed, capped grid (one partial per workgroup, deterministic tree)
 static int blas_grid(int64_t n, int per_thread)
@@ -25,21 +23,6 @@ static int blas_grid(int64_t n, int per_thread)
     if (b > kBlasMaxGrid) b = kBlasMaxGrid;
     return b < 1 ? 1 : (int)b;
 }
-
-// element-wise kernels that STORE: one-shot grid, a workgroup per chunk (tools/membench.hip: stores
-// from a capped grid-stride grid run at 4.5-5.0 TB/s, one-shot at 6.3-6.9 TB/s)
-static int stream_grid(int64_t n, int per_thread)
-{
-    int64_t b = ceil_div(n, (int64_t)kBlasBlock * per_thread);
-    const int64_t cap = (int64_t)1 << 22;
-    if (b > cap) b = cap;
-    return b < 1 ? 1 : (int)b;
-}
-
-// 16 bytes per lane: 2 doubles or 4 floats
-template <typename T> struct vec16;
-template <> struct vec16<double> { typedef double2v type; static constexpr int n = 2; };
-template <> struct vec16<float> { typedef float4v type; static constexpr int n = 4; };
 
 template <typename T>
 __global__ void __launch_bounds__(kBlasBlock)
@@ -224,13 +207,6 @@ int reduce_partials_f64(int npartial, double *workspace, double *result, hipStre
 // ---------------------------------------------------------------------------------------------
 // T = double or float; the scalars (<r,r>, <y,p>) are doubles in device memory for both (the partials of every
 // reduction here are doubles), alpha / beta are rounded to T once per kernel and the vectors are updated in T.
-// store with or without the nt hint by a run-time flag (uniform)
-template <typename V> __device__ __forceinline__ void st_policy(V *p, V v, bool nt)
-{
-    if (nt) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
-
 
 template <typename T>
 __global__ void __launch_bounds__(kBlasBlock)
@@ -574,13 +550,6 @@ CMI_API int cmi_blas_nrm2_f64(int64_t n, const double *x, double *r, void *ws, v
 CMI_API int cmi_blas_nrm2_f32(int64_t n, const float *x, float *r, void *ws, void *stream) { return dot_impl<float>(n, x, x, r, ws, stream, 1); }
 
 // ---- fused CG steps ----
-static int fused_grid(int64_t n, int per_thread)
-{
-    int64_t b = ceil_div(n, (int64_t)kBlasBlock * per_thread);
-    if (b > kFusedMaxGrid) b = kFusedMaxGrid;
-    return b < 1 ? 1 : (int)b;
-}
-
 namespace {
 
 template <typename T>

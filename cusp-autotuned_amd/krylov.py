@@ -149,6 +149,31 @@ class _SyncScalar:
         return float(self.src.item())
 
 
+def _multiply_dot(A, p, y, yp, ws):
+    """y <- A p and yp <- <y, p> (a double in device memory) for a one-GPU container: CSR / ELL / DIA fuse the dot for f64 and f32,
+    COO and HYB through their plans; everything else: the multiply, then a dot into a double."""
+    from . import binding as B
+    from .matrices import CooMatrix, CsrMatrix, DiaMatrix, EllMatrix, HybMatrix, multiply
+    if isinstance(A, CsrMatrix) and p.is_cuda:
+        B.spmv_csr_dot(A.num_rows, A.num_cols, A.row_offsets, A.column_indices, A.values, p, y, p, yp, ws,
+                       plan=A.plan() if A.num_entries > 0 else None)
+    elif isinstance(A, CooMatrix) and p.is_cuda and A.num_entries > 0:   # sorted entries: the CSR kernel's fused dot on the plan's offsets
+        B.spmv_coo_dot_plan(A.plan(), A.row_indices, A.column_indices, A.values, p, y, p, yp, ws)
+    elif isinstance(A, HybMatrix) and A.coo.num_entries == 0 and p.is_cuda:   # everything in the ELL part: its fused dot
+        e = A.ell
+        B.spmv_ell_dot(A.num_rows, A.num_cols, e.num_entries_per_row, e.pitch, e.column_indices, e.values, p, y, p, yp, ws)
+    elif isinstance(A, HybMatrix) and p.is_cuda and A.plan() is not None:   # one launch through the plan: its fused dot
+        B.spmv_hyb_dot_plan_args(A._plan_args, p, y, p, yp, ws)
+    elif isinstance(A, EllMatrix) and p.is_cuda:
+        B.spmv_ell_dot(A.num_rows, A.num_cols, A.num_entries_per_row, A.pitch, A.column_indices, A.values, p, y, p, yp, ws,
+                       row_lengths=A.row_lengths)
+    elif isinstance(A, DiaMatrix) and p.is_cuda:
+        B.spmv_dia_dot(A.num_rows, A.num_cols, A.diagonal_offsets.numel(), A.pitch, A.diagonal_offsets, A.values, p, y, p, yp, ws)
+    else:
+        multiply(A, p, y)
+        B.blas_dotd(y, p, yp, ws)
+
+
 def _cg_fused(A, x, b, monitor, ops, spmv, y, r, p, world, group):
     """Unpreconditioned CG with z == r folded away and the scalars resident on the device.
 
@@ -180,27 +205,10 @@ def _cg_fused(A, x, b, monitor, ops, spmv, y, r, p, world, group):
         return B.spmv_csr_dot_partials(A.plan(), A.row_offsets, A.column_indices, A.values, p, y, p, ops.ws)
 
     def spmv_dot():                              # y <- A p, yp <- <y, p>
-        if isinstance(A, ShardedCsr):            # CSR / ELL / DIA fuse the dot for f64 and f32 (the scalar is a double either way);
-                                                 # everything else: SpMV, then a dot into a double
+        if isinstance(A, ShardedCsr):
             A.multiply_dot(y, yp, ops.ws)        # p IS A.x_local
-        elif isinstance(A, CsrMatrix) and p.is_cuda:
-            B.spmv_csr_dot(A.num_rows, A.num_cols, A.row_offsets, A.column_indices, A.values, p, y, p, yp, ops.ws,
-                           plan=A.plan() if A.num_entries > 0 else None)
-        elif isinstance(A, CooMatrix) and p.is_cuda and A.num_entries > 0:   # sorted entries: the CSR kernel's fused dot on the plan's offsets
-            B.spmv_coo_dot_plan(A.plan(), A.row_indices, A.column_indices, A.values, p, y, p, yp, ops.ws)
-        elif isinstance(A, HybMatrix) and A.coo.num_entries == 0 and p.is_cuda:   # everything in the ELL part: its fused dot
-            e = A.ell
-            B.spmv_ell_dot(A.num_rows, A.num_cols, e.num_entries_per_row, e.pitch, e.column_indices, e.values, p, y, p, yp, ops.ws)
-        elif isinstance(A, HybMatrix) and p.is_cuda and A.plan() is not None:   # one launch through the plan: its fused dot
-            B.spmv_hyb_dot_plan_args(A._plan_args, p, y, p, yp, ops.ws)
-        elif isinstance(A, EllMatrix) and p.is_cuda:
-            B.spmv_ell_dot(A.num_rows, A.num_cols, A.num_entries_per_row, A.pitch, A.column_indices, A.values, p, y, p, yp, ops.ws,
-                           row_lengths=A.row_lengths)
-        elif isinstance(A, DiaMatrix) and p.is_cuda:
-            B.spmv_dia_dot(A.num_rows, A.num_cols, A.diagonal_offsets.numel(), A.pitch, A.diagonal_offsets, A.values, p, y, p, yp, ops.ws)
         else:
-            spmv(p, y)
-            B.blas_dotd(y, p, yp, ops.ws)
+            _multiply_dot(A, p, y, yp, ops.ws)
         reduce_(yp)
 
     # One-sided sharding ("peer" exchange): p is exchanged ONCE.  Afterwards every rank keeps the p
@@ -270,3 +278,92 @@ def _cg_fused(A, x, b, monitor, ops, spmv, y, r, p, world, group):
     if dev.type == "cuda":
         torch.cuda.current_stream(dev).synchronize()                # the discarded SpMV must not outlive y
     return monitor
+
+
+def cg_m(A, b, sigma, x=None, monitor=None, iteration_limit=500, relative_tolerance=1e-5, absolute_tolerance=0.0, fused=None):
+    """Multi-shift CG: solve (A + sigma_s I) x_s = b for every shift in `sigma` (a device vector of b's dtype) with ONE multiply per
+    iteration (reference cusp/krylov/detail/cg_m.inl; the C++ twin is cusp/krylov/cg_m.h).  A: a one-GPU matrices.* container, symmetric
+    positive definite.  x: optional device vector of n * num_shifts values (shift s at [s n, (s + 1) n)), zero-filled on entry.  The monitor
+    watches the residual of the unshifted system.  Returns (x viewed as num_shifts x n, the Monitor).
+
+    fused (default: unless $CMI_CG_M_FUSED is 0): multiply + <y,p>, cmi_cg_update (r, <r,r>), cmi_cg_m_coefficients, cmi_cg_m_update_xp --
+    four launches and one host read per iteration, the scalars doubles in device memory.  Otherwise cg_m.inl operation by operation: three
+    host reads per iteration, the per-shift coefficients formed on the host in b's dtype and uploaded for cmi_cg_m_update_xp."""
+    import os
+
+    import torch
+    from . import binding as B
+    from .matrices import multiply
+
+    if b.dtype not in (torch.float64, torch.float32) or sigma.dtype != b.dtype:
+        raise TypeError(f"cg_m: b and sigma must both be float64 or float32 device vectors, got {b.dtype} / {sigma.dtype}")
+    if A.num_rows != A.num_cols:
+        raise ValueError("cg_m: matrix must be square")
+    n, ns, dev = b.numel(), sigma.numel(), b.device
+    if n != A.num_rows:
+        raise ValueError("cg_m: b does not match the matrix")
+    if x is None:
+        x = torch.empty(n * ns, dtype=b.dtype, device=dev)
+    elif x.numel() != n * ns or x.dtype != b.dtype:
+        raise ValueError("cg_m: x must hold num_rows values of b's dtype per shift")
+    if fused is None:
+        fused = os.environ.get("CMI_CG_M_FUSED", "1") != "0"
+    ops = _Ops(dev, None, 1)
+    if monitor is None:
+        monitor = Monitor(ops.nrm2(b), iteration_limit, relative_tolerance, absolute_tolerance)
+    y, r, p0 = torch.empty_like(b), b.clone(), b.clone()
+    ps = b.repeat(ns) if ns else torch.empty(0, dtype=b.dtype, device=dev)
+    B.blas_fill(0.0, x)
+    out = x.view(ns, n)
+
+    if not fused:
+        import numpy as np
+        T = np.float64 if b.dtype == torch.float64 else np.float32
+        sg = sigma.cpu().numpy()
+        zm1, z0 = np.ones(ns, T), np.ones(ns, T)
+        beta_0, alpha_0 = T(1), T(0)
+        rsq_1 = T(ops.dot(r, r))
+        while not monitor.finished(ops.nrm2(r)):
+            rsq_0, beta_m1 = rsq_1, beta_0
+            multiply(A, p0, y)
+            beta_0 = T(-rsq_0 / T(ops.dot(p0, y)))
+            B.blas_axpy(float(beta_0), y, r)
+            with np.errstate(all="ignore"):
+                z1 = (z0 * zm1 * beta_m1 / (beta_0 * alpha_0 * (zm1 - z0) + beta_m1 * zm1 * (T(1) - beta_0 * sg))).astype(T)
+                beta_s = (beta_0 * z1 / z0).astype(T)
+                z1 = np.where(np.abs(z1) < T(1e-30), T(1e-18), z1).astype(T)
+                rsq_1 = T(ops.dot(r, r))
+                alpha_0 = T(rsq_1 / rsq_0)
+                B.blas_axpby(1.0, r, float(alpha_0), p0, p0)
+                alpha_s = (alpha_0 / beta_0 * z1 * beta_s / z0).astype(T)
+            if ns:
+                up = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (beta_s, alpha_s, z1)]
+                B.cg_m_update_xp(n, n, None, up[0], up[1], up[2], r, None, x, ps)
+            zm1, z0 = z0, z1
+            monitor.increment()
+        return out, monitor
+
+    rr = [torch.zeros(1, dtype=torch.float64, device=dev) for _ in range(2)]  # <r,r> ping-pong
+    yp = torch.zeros(1, dtype=torch.float64, device=dev)
+    state = torch.tensor([1.0, 0.0], dtype=b.dtype, device=dev)               # (beta_0, alpha_0) of the previous iteration
+    zm1, z0 = torch.ones(ns, dtype=b.dtype, device=dev), torch.ones(ns, dtype=b.dtype, device=dev)
+    beta_s, alpha_s = torch.empty_like(zm1), torch.empty_like(zm1)
+    rr_host = B.HostScalar() if dev.type == "cuda" else _SyncScalar()
+    mirror = rr_host if dev.type == "cuda" else None
+    B.blas_dotd(r, r, rr[0], ops.ws)
+    rr_host.fetch(rr[0])
+    cur = 0
+    while True:
+        _multiply_dot(A, p0, y, yp, ops.ws)                         # the multiply, queued before the host waits
+        if monitor.finished(math.sqrt(rr_host.wait())):             # the one host read per iteration
+            break
+        B.cg_update(rr[cur], yp, None, y, None, r, rr[cur ^ 1], ops.ws, mirror=mirror)   # r <- r + beta_0 y, <r,r>
+        if mirror is None:
+            rr_host.fetch(rr[cur ^ 1])
+        B.cg_m_coefficients(rr[cur], yp, rr[cur ^ 1], state, sigma, zm1, z0, beta_s, alpha_s)
+        B.cg_m_update_xp(n, n, state, beta_s, alpha_s, z0, r, p0, x, ps)
+        cur ^= 1
+        monitor.increment()
+    if dev.type == "cuda":
+        torch.cuda.current_stream(dev).synchronize()                # the discarded multiply must not outlive y
+    return out, monitor

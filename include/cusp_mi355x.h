@@ -1175,6 +1175,63 @@ int cmi_cg_direction_x_fold_f32(int64_t n, double *rr_new_dev, double *rr_host_m
 int cmi_blas_dotd_f32(int64_t n, const float *x, const float *y, double *result_dev, void *workspace, void *stream);
 
 /* ------------------------------------------------------------------------- */
+/* The steps of the multi-shift solvers cusp::krylov::cg_m and bicgstab_m (csrc/krylov_m.hip; reference cusp/krylov/detail/cg_m.inl,
+ * bicgstab_m.inl: the functors KERNEL_ZB, KERNEL_A, KERNEL_XP, KERNEL_S, KERNEL_CHIRHO, KERNEL_XS as thrust::for_each passes).  They solve
+ * (A + sigma_s I) x_s = b for num_shifts shifts with the multiplies of one system; x, p_s and s_s hold shift s at offset s * ld (ld >= n,
+ * 64-bit offsets), sigma and the per-shift coefficient arrays hold num_shifts values.  Every expression is the reference's, term for
+ * term and unfused.  No call allocates or synchronises.  Refused before any device call (CMI_ERROR_INVALID_VALUE, cmi_last_error): a
+ * negative n or num_shifts, a null array, ld < n, an output range that overlaps another output or an input.  n == 0 is a no-op.
+ *
+ * cmi_cg_m_coefficients_*: one small launch (one workgroup strided over the shifts: any num_shifts).  In T, with beta_m1 = state[0],
+ *   alpha_old = state[1], beta_0 = -(T)(*rsq_old_dev / *pAp_dev), alpha_0 = (T)(*rsq_new_dev / *rsq_old_dev) (each quotient formed in
+ *   double and rounded once: the -alpha of cmi_cg_update_* and the beta of cmi_cg_direction_*), per shift:
+ *     zeta_1 = zeta_0 zeta_m1 beta_m1 / (beta_0 alpha_old (zeta_m1 - zeta_0) + beta_m1 zeta_m1 (1 - beta_0 sigma))          (KERNEL_ZB)
+ *     beta_s = beta_0 zeta_1 / zeta_0;   |zeta_1| < 1e-30: zeta_1 = 1e-18 (the reference's clamp, after beta_s)
+ *     alpha_s = alpha_0 / beta_0 zeta_1 beta_s / zeta_0                                                                       (KERNEL_A)
+ *     zeta_m1 <- zeta_0, then zeta_0 <- zeta_1                                                                          (the rotation)
+ *   and then state <- (beta_0, alpha_0).  The caller starts with state = (1, 0) and every zeta = 1.  num_shifts == 0: only the state.
+ * cmi_cg_m_update_xp_*: the hot kernel.  p0 <- r + alpha_0 p0 (alpha_0 = state[1]; skipped when p0 == NULL, state may then be NULL);
+ *   for every shift x_s <- x_s - beta_s p_s with the OLD p_s, then p_s <- zeta_0[s] r + alpha_s p_s (KERNEL_XP with the rotated zeta).
+ *   r (and p0) are read once, whatever num_shifts; 16-byte accesses wherever r / p0 / x + s ld / p_s + s ld are 16-byte aligned,
+ *   element accesses where they are not.  The ld - n elements between two shifts are not touched.  num_shifts == 0: only p0.
+ *   With cmi_cg_update_* (x == NULL) a CG-M iteration is four launches: multiply + <y,p>, update + <r,r>, coefficients, update_xp.   */
+int cmi_cg_m_coefficients_f64(int64_t num_shifts, const double *rsq_old_dev, const double *pAp_dev, const double *rsq_new_dev, double *state,
+                              const double *sigma, double *zeta_m1, double *zeta_0, double *beta_s, double *alpha_s, void *stream);
+int cmi_cg_m_coefficients_f32(int64_t num_shifts, const double *rsq_old_dev, const double *pAp_dev, const double *rsq_new_dev, float *state,
+                              const float *sigma, float *zeta_m1, float *zeta_0, float *beta_s, float *alpha_s, void *stream);
+int cmi_cg_m_update_xp_f64(int64_t n, int64_t num_shifts, int64_t ld, const double *state, const double *beta_s, const double *alpha_s, const double *zeta_0,
+                           const double *r, double *p0, double *x, double *p_s, void *stream);
+int cmi_cg_m_update_xp_f32(int64_t n, int64_t num_shifts, int64_t ld, const float *state, const float *beta_s, const float *alpha_s, const float *zeta_0,
+                           const float *r, float *p0, float *x, float *p_s, void *stream);
+/* BiCGstab-M; the scalars of the unshifted system are passed by value in T (the header layer forms them on the host, as the reference does).
+ * cmi_bicgstab_m_s_*: s_0 <- r_1 + alpha_1 (s_0 - chi_0 As)                                                                     (KERNEL_S)
+ * cmi_bicgstab_m_coefficients_*: per shift, from the current zeta_m1, zeta_0, rho_0 (all three only read):
+ *     zeta_1, beta_s as above with (beta_m1, beta_0, alpha_old), the clamp;                                                   (KERNEL_ZB)
+ *     den = 1 + chi_0 sigma;  chi_s = chi_0 / den;  rho_1 = rho_0 / den;                                                  (KERNEL_CHIRHO)
+ *     alpha_s = alpha_new / beta_0 zeta_1 beta_s / zeta_0                                                                      (KERNEL_A)
+ *   It does NOT rotate: cmi_bicgstab_m_update_xs_* needs both generations of zeta and rho.
+ * cmi_bicgstab_m_update_xs_*: for every shift, with the OLD s_s in both lines                                                   (KERNEL_XS)
+ *     x_s <- x_s - beta_s s_s + chi_s rho_0 zeta_1 w_1
+ *     s_s <- zeta_1 rho_1 r_1 + alpha_s (s_s - chi_s rho_0 / beta_s (zeta_1 w_1 - zeta_0 r_0))
+ *   r_0, r_1, w_1 are read once per position.  The rotation for the next iteration -- zeta_m1 <- zeta_0, zeta_0 <- zeta_1, rho_0 <- rho_1 -- is a
+ *   one-line TAIL LAUNCH queued by the same call behind the update (inside the update kernel it would race with the workgroups that still
+ *   read zeta_0 and rho_0): zeta_m1, zeta_0 and rho_0 are therefore outputs.  Alignment rules as cmi_cg_m_update_xp_*.                       */
+int cmi_bicgstab_m_s_f64(int64_t n, double alpha_1, double chi_0, const double *r_1, const double *As, double *s_0, void *stream);
+int cmi_bicgstab_m_s_f32(int64_t n, float alpha_1, float chi_0, const float *r_1, const float *As, float *s_0, void *stream);
+int cmi_bicgstab_m_coefficients_f64(int64_t num_shifts, double beta_m1, double beta_0, double alpha_old, double alpha_new, double chi_0, const double *sigma,
+                                    const double *zeta_m1, const double *zeta_0, const double *rho_0, double *zeta_1, double *beta_s, double *chi_s,
+                                    double *rho_1, double *alpha_s, void *stream);
+int cmi_bicgstab_m_coefficients_f32(int64_t num_shifts, float beta_m1, float beta_0, float alpha_old, float alpha_new, float chi_0, const float *sigma,
+                                    const float *zeta_m1, const float *zeta_0, const float *rho_0, float *zeta_1, float *beta_s, float *chi_s, float *rho_1,
+                                    float *alpha_s, void *stream);
+int cmi_bicgstab_m_update_xs_f64(int64_t n, int64_t num_shifts, int64_t ld, const double *beta_s, const double *chi_s, double *rho_0, double *zeta_m1,
+                                 double *zeta_0, const double *alpha_s, const double *rho_1, const double *zeta_1, const double *r_0, const double *r_1,
+                                 const double *w_1, double *x, double *s_s, void *stream);
+int cmi_bicgstab_m_update_xs_f32(int64_t n, int64_t num_shifts, int64_t ld, const float *beta_s, const float *chi_s, float *rho_0, float *zeta_m1, float *zeta_0,
+                                 const float *alpha_s, const float *rho_1, const float *zeta_1, const float *r_0, const float *r_1, const float *w_1, float *x,
+                                 float *s_s, void *stream);
+
+/* ------------------------------------------------------------------------- */
 /* Multi-GPU: communicator and collectives of the row-block sharded SpMV / CG */
 /* (cmi_allgather_f64, cmi_allreduce_f64; 8(e): one process per   */
 /* GPU, matrices sharded by row blocks with GLOBAL column indices, an all-gather of x over   */
