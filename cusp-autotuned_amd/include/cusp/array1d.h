@@ -331,13 +331,11 @@ template <typename T, typename Dst> void fill_random(const random_array<T> &src,
 {
     for (size_t i = 0; i < src.size(); i++) dst[i] = static_cast<typename Dst::value_type>(src[i]);
 }
-inline int random_fill(size_t n, size_t seed, double *x) { return cmi_random_fill_f64(static_cast<int64_t>(n), seed, x, nullptr); }
-inline int random_fill(size_t n, size_t seed, float *x) { return cmi_random_fill_f32(static_cast<int64_t>(n), seed, x, nullptr); }
 template <typename T, typename Dst> void fill_random(const random_array<T> &src, Dst &dst, device_memory)
 {
     static_assert(std::is_same<T, typename Dst::value_type>::value && (std::is_same<T, double>::value || std::is_same<T, float>::value),
                   "cusp::copy(random_array<T>, x) into device_memory is implemented for x of the same type T = float or double");
-    check(random_fill(src.size(), src.seed(), dst.data()));
+    check(by_type<T>(cmi_random_fill_f64, cmi_random_fill_f32)(src.size(), src.seed(), dst.data(), nullptr));
 }
 } // namespace detail
 template <typename T, typename Dst> void copy_array(const random_array<T> &src, Dst &dst)

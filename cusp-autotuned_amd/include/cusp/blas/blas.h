@@ -41,33 +41,9 @@ template <typename X, typename Y> void same_size(const X &x, const Y &y)
     if (x.size() != y.size()) throw cusp::invalid_input_exception("cusp::blas: array sizes differ");
 }
 
-// C-ABI overload sets (double / float)
-inline int c_axpy(int64_t n, double a, const double *x, double *y) { return cmi_blas_axpy_f64(n, a, x, y, nullptr); }
-inline int c_axpy(int64_t n, float a, const float *x, float *y) { return cmi_blas_axpy_f32(n, a, x, y, nullptr); }
-inline int c_axpby(int64_t n, double a, const double *x, double b, const double *y, double *z) { return cmi_blas_axpby_f64(n, a, x, b, y, z, nullptr); }
-inline int c_axpby(int64_t n, float a, const float *x, float b, const float *y, float *z) { return cmi_blas_axpby_f32(n, a, x, b, y, z, nullptr); }
-inline int c_copy(int64_t n, const double *x, double *y) { return cmi_blas_copy_f64(n, x, y, nullptr); }
-inline int c_copy(int64_t n, const float *x, float *y) { return cmi_blas_copy_f32(n, x, y, nullptr); }
-inline int c_fill(int64_t n, double v, double *y) { return cmi_blas_fill_f64(n, v, y, nullptr); }
-inline int c_fill(int64_t n, float v, float *y) { return cmi_blas_fill_f32(n, v, y, nullptr); }
-inline int c_dot(int64_t n, const double *x, const double *y, double *r, void *ws) { return cmi_blas_dot_f64(n, x, y, r, ws, nullptr); }
-inline int c_dot(int64_t n, const float *x, const float *y, float *r, void *ws) { return cmi_blas_dot_f32(n, x, y, r, ws, nullptr); }
-inline int c_nrm2(int64_t n, const double *x, double *r, void *ws) { return cmi_blas_nrm2_f64(n, x, r, ws, nullptr); }
-inline int c_nrm2(int64_t n, const float *x, float *r, void *ws) { return cmi_blas_nrm2_f32(n, x, r, ws, nullptr); }
-
-inline int c_scal(int64_t n, double a, double *x) { return cmi_blas_scal_f64(n, a, x, nullptr); }
-inline int c_scal(int64_t n, float a, float *x) { return cmi_blas_scal_f32(n, a, x, nullptr); }
-inline int c_xmy(int64_t n, const double *x, const double *y, double *z) { return cmi_blas_xmy_f64(n, x, y, z, nullptr); }
-inline int c_xmy(int64_t n, const float *x, const float *y, float *z) { return cmi_blas_xmy_f32(n, x, y, z, nullptr); }
-inline int c_axpbypcz(int64_t n, double a, const double *x, double b, const double *y, double c, const double *z, double *o) { return cmi_blas_axpbypcz_f64(n, a, x, b, y, c, z, o, nullptr); }
-inline int c_axpbypcz(int64_t n, float a, const float *x, float b, const float *y, float c, const float *z, float *o) { return cmi_blas_axpbypcz_f32(n, a, x, b, y, c, z, o, nullptr); }
-inline int c_asum(int64_t n, const double *x, double *r, void *ws) { return cmi_blas_asum_f64(n, x, r, ws, nullptr); }
-inline int c_asum(int64_t n, const float *x, float *r, void *ws) { return cmi_blas_asum_f32(n, x, r, ws, nullptr); }
-inline int c_amax(int64_t n, const double *x, double *v, int64_t *i, void *ws) { return cmi_blas_amax_f64(n, x, v, i, ws, nullptr); }
-inline int c_amax(int64_t n, const float *x, float *v, int64_t *i, void *ws) { return cmi_blas_amax_f32(n, x, v, i, ws, nullptr); }
-
+using cusp::detail::by_type;
 template <typename V> struct require_real {
-    static_assert(std::is_same<V, double>::value || std::is_same<V, float>::value, "device_memory cusp::blas routines are implemented for float and double");
+    static_assert(cusp::detail::is_real<V>::value, "device_memory cusp::blas routines are implemented for float and double");
 };
 
 // ---- host ----
@@ -87,19 +63,20 @@ template <typename X, typename Y> typename X::value_type dot(const X &x, const Y
 }
 // ---- device ----
 template <typename X, typename Y, typename S> void axpy(const X &x, Y &y, S a, device_memory)
-{ require_real<typename Y::value_type>(); cusp::detail::check(c_axpy(x.size(), a, x.data(), y.data())); }
+{ require_real<typename Y::value_type>(); cusp::detail::check(by_type<typename Y::value_type>(cmi_blas_axpy_f64, cmi_blas_axpy_f32)(x.size(), a, x.data(), y.data(), nullptr)); }
 template <typename X, typename Y, typename Z, typename S> void axpby(const X &x, const Y &y, Z &z, S a, S b, device_memory)
-{ require_real<typename Z::value_type>(); cusp::detail::check(c_axpby(x.size(), a, x.data(), b, y.data(), z.data())); }
+{ require_real<typename Z::value_type>(); cusp::detail::check(by_type<typename Z::value_type>(cmi_blas_axpby_f64, cmi_blas_axpby_f32)(
+    x.size(), a, x.data(), b, y.data(), z.data(), nullptr)); }
 template <typename X, typename Y> void copy(const X &x, Y &y, device_memory)
-{ require_real<typename Y::value_type>(); cusp::detail::check(c_copy(x.size(), x.data(), y.data())); }
+{ require_real<typename Y::value_type>(); cusp::detail::check(by_type<typename Y::value_type>(cmi_blas_copy_f64, cmi_blas_copy_f32)(x.size(), x.data(), y.data(), nullptr)); }
 template <typename X, typename S> void fill(X &x, S v, device_memory)
-{ require_real<typename X::value_type>(); cusp::detail::check(c_fill(x.size(), v, x.data())); }
+{ require_real<typename X::value_type>(); cusp::detail::check(by_type<typename X::value_type>(cmi_blas_fill_f64, cmi_blas_fill_f32)(x.size(), v, x.data(), nullptr)); }
 template <typename X, typename Y> typename X::value_type dot(const X &x, const Y &y, device_memory)
 {
     typedef typename X::value_type V;
     require_real<V>();
     device_workspace &w = workspace();
-    cusp::detail::check(c_dot(x.size(), x.data(), y.data(), static_cast<V *>(w.result), w.ws));
+    cusp::detail::check(by_type<V>(cmi_blas_dot_f64, cmi_blas_dot_f32)(x.size(), x.data(), y.data(), static_cast<V *>(w.result), w.ws, nullptr));
     V r;
     cusp::detail::check(cmi_memcpy_d2h(&r, w.result, sizeof(V), nullptr));
     return r;
@@ -109,7 +86,7 @@ template <typename X> typename X::value_type nrm2(const X &x, device_memory)
     typedef typename X::value_type V;
     require_real<V>();
     device_workspace &w = workspace();
-    cusp::detail::check(c_nrm2(x.size(), x.data(), static_cast<V *>(w.result), w.ws));
+    cusp::detail::check(by_type<V>(cmi_blas_nrm2_f64, cmi_blas_nrm2_f32)(x.size(), x.data(), static_cast<V *>(w.result), w.ws, nullptr));
     V r;
     cusp::detail::check(cmi_memcpy_d2h(&r, w.result, sizeof(V), nullptr));
     return r;
@@ -123,14 +100,17 @@ template <typename X> typename X::value_type nrm2(const X &x, host_memory)
 
 // ---- the rest of the set: host loops and device kernels ----
 template <typename X, typename S> void scal(X &x, S a, host_memory) { for (size_t i = 0; i < x.size(); i++) x[i] = a * x[i]; }
-template <typename X, typename S> void scal(X &x, S a, device_memory) { require_real<typename X::value_type>(); cusp::detail::check(c_scal(x.size(), a, x.data())); }
+template <typename X, typename S> void scal(X &x, S a, device_memory) { require_real<typename X::value_type>(); cusp::detail::check(by_type<typename X::value_type>(cmi_blas_scal_f64, cmi_blas_scal_f32)(
+    x.size(), a, x.data(), nullptr)); }
 template <typename X, typename Y, typename Z> void xmy(const X &x, const Y &y, Z &z, host_memory) { for (size_t i = 0; i < x.size(); i++) z[i] = x[i] * y[i]; }
 template <typename X, typename Y, typename Z> void xmy(const X &x, const Y &y, Z &z, device_memory)
-{ require_real<typename Z::value_type>(); cusp::detail::check(c_xmy(x.size(), x.data(), y.data(), z.data())); }
+{ require_real<typename Z::value_type>(); cusp::detail::check(by_type<typename Z::value_type>(cmi_blas_xmy_f64, cmi_blas_xmy_f32)(
+    x.size(), x.data(), y.data(), z.data(), nullptr)); }
 template <typename X, typename Y, typename Z, typename O, typename S> void axpbypcz(const X &x, const Y &y, const Z &z, O &out, S a, S b, S c, host_memory)
 { for (size_t i = 0; i < x.size(); i++) out[i] = a * x[i] + b * y[i] + c * z[i]; }
 template <typename X, typename Y, typename Z, typename O, typename S> void axpbypcz(const X &x, const Y &y, const Z &z, O &out, S a, S b, S c, device_memory)
-{ require_real<typename O::value_type>(); cusp::detail::check(c_axpbypcz(x.size(), a, x.data(), b, y.data(), c, z.data(), out.data())); }
+{ require_real<typename O::value_type>(); cusp::detail::check(by_type<typename O::value_type>(cmi_blas_axpbypcz_f64, cmi_blas_axpbypcz_f32)(
+    x.size(), a, x.data(), b, y.data(), c, z.data(), out.data(), nullptr)); }
 template <typename X> typename X::value_type nrm1(const X &x, host_memory)
 {
     typename X::value_type s = 0;
@@ -142,7 +122,7 @@ template <typename X> typename X::value_type nrm1(const X &x, device_memory)
     typedef typename X::value_type V;
     require_real<V>();
     device_workspace &w = workspace();
-    cusp::detail::check(c_asum(x.size(), x.data(), static_cast<V *>(w.result), w.ws));
+    cusp::detail::check(by_type<V>(cmi_blas_asum_f64, cmi_blas_asum_f32)(x.size(), x.data(), static_cast<V *>(w.result), w.ws, nullptr));
     V r;
     cusp::detail::check(cmi_memcpy_d2h(&r, w.result, sizeof(V), nullptr));
     return r;
@@ -159,7 +139,7 @@ template <typename X> void max_abs(const X &x, typename X::value_type &value, si
     require_real<V>();
     device_workspace &w = workspace();
     int64_t *pos = reinterpret_cast<int64_t *>(static_cast<char *>(w.result) + sizeof(double));
-    cusp::detail::check(c_amax(x.size(), x.data(), static_cast<V *>(w.result), pos, w.ws));
+    cusp::detail::check(by_type<V>(cmi_blas_amax_f64, cmi_blas_amax_f32)(x.size(), x.data(), static_cast<V *>(w.result), pos, w.ws, nullptr));
     int64_t p = 0;
     cusp::detail::check(cmi_memcpy_d2h(&value, w.result, sizeof(V), nullptr));
     cusp::detail::check(cmi_memcpy_d2h(&p, pos, sizeof(int64_t), nullptr));
@@ -184,8 +164,6 @@ template <typename X, typename Y, typename Z, typename L> void xmy(const X &x, c
 { auto xl = x.local(); auto yl = y.local(); auto zl = z.local(); xmy(xl, yl, zl, L()); }
 template <typename X, typename Y, typename Z, typename O, typename S, typename L> void axpbypcz(const X &x, const Y &y, const Z &z, O &out, S a, S b, S c, distributed_memory<L>)
 { auto xl = x.local(); auto yl = y.local(); auto zl = z.local(); auto ol = out.local(); axpbypcz(xl, yl, zl, ol, a, b, c, L()); }
-inline int c_dotd(int64_t n, const double *x, const double *y, double *r, void *ws) { return cmi_blas_dot_f64(n, x, y, r, ws, nullptr); }
-inline int c_dotd(int64_t n, const float *x, const float *y, double *r, void *ws) { return cmi_blas_dotd_f32(n, x, y, r, ws, nullptr); }
 template <typename X, typename Y> double dot_all(const X &x, const Y &y, host_memory)
 {
     double s = 0;
@@ -198,7 +176,7 @@ template <typename X, typename Y> double dot_all(const X &x, const Y &y, device_
     require_real<typename X::value_type>();
     device_workspace &w = workspace();
     double *res = static_cast<double *>(w.result);
-    cusp::detail::check(c_dotd(x.size(), x.data(), y.data(), res, w.ws));
+    cusp::detail::check(by_type<typename X::value_type>(cmi_blas_dot_f64, cmi_blas_dotd_f32)(x.size(), x.data(), y.data(), res, w.ws, nullptr)); // (float: accumulated in double)
     x.comm().allreduce_sum(res, 1, device_memory());
     double r;
     cusp::detail::check(cmi_memcpy_d2h(&r, res, sizeof(double), nullptr));

@@ -352,13 +352,6 @@ template <typename Src, typename Dst> void copy_same(const Src &s, Dst &d, array
 }
 
 // ---- device fast paths: device CSR -> device ELL / COO through the C-ABI builders ----------------
-inline int csr_to_ell_device(int64_t rows, const int *Ap, const int *Aj, const double *Ax, int64_t w, int64_t pitch, int *eAj, double *eAx)
-{ return cmi_csr_to_ell_f64(rows, Ap, Aj, Ax, w, pitch, eAj, eAx, nullptr); }
-inline int csr_to_ell_device(int64_t rows, const int *Ap, const int *Aj, const float *Ax, int64_t w, int64_t pitch, int *eAj, float *eAx)
-{ return cmi_csr_to_ell_f32(rows, Ap, Aj, Ax, w, pitch, eAj, eAx, nullptr); }
-
-inline int count_zeros_device(int64_t n, const double *v, int64_t *c) { return cmi_count_zeros_f64(n, v, c, nullptr); }
-inline int count_zeros_device(int64_t n, const float *v, int64_t *c) { return cmi_count_zeros_f32(n, v, c, nullptr); }
 
 template <typename Src, typename Dst, typename SF, typename DF> struct device_fast_path {
     static bool run(const Src &, Dst &) { return false; }
@@ -371,10 +364,10 @@ struct device_fast_path<csr_matrix<int, V, device_memory>, ell_matrix<int, V, de
         const size_t width = compute_max_entries_per_row(s.row_offsets); // one D2H copy of the offsets
         check_fill("ell_matrix", width * s.num_rows, s.num_entries);
         int64_t zeros = 0; // reference csr_to_other.h:188: the ELL matrix reports num_entries without the explicit zeros
-        check(count_zeros_device(s.num_entries, s.values.data(), &zeros));
+        check(by_type<V>(cmi_count_zeros_f64, cmi_count_zeros_f32)(s.num_entries, s.values.data(), &zeros, nullptr));
         d.resize(s.num_rows, s.num_cols, s.num_entries - static_cast<size_t>(zeros), width);
-        check(csr_to_ell_device(s.num_rows, s.row_offsets.data(), s.column_indices.data(), s.values.data(), width,
-                                d.column_indices.pitch, d.column_indices.values.data(), d.values.values.data()));
+        check(by_type<V>(cmi_csr_to_ell_f64, cmi_csr_to_ell_f32)(s.num_rows, s.row_offsets.data(), s.column_indices.data(), s.values.data(), width,
+                                                                 d.column_indices.pitch, d.column_indices.values.data(), d.values.values.data(), nullptr));
         check(cmi_stream_synchronize(nullptr));
         return true;
     }
@@ -422,15 +415,6 @@ struct device_fast_path<coo_matrix<int, V, device_memory>, csr_matrix<int, V, de
     }
 };
 
-inline int ell_to_csr_device(int64_t rows, int64_t w, int64_t pitch, const int *eAj, const double *eAx, int *Ap, int *Aj, double *Ax, int64_t cap, int64_t *n)
-{ return cmi_ell_to_csr_f64(rows, w, pitch, eAj, eAx, Ap, Aj, Ax, cap, n, nullptr); }
-inline int ell_to_csr_device(int64_t rows, int64_t w, int64_t pitch, const int *eAj, const float *eAx, int *Ap, int *Aj, float *Ax, int64_t cap, int64_t *n)
-{ return cmi_ell_to_csr_f32(rows, w, pitch, eAj, eAx, Ap, Aj, Ax, cap, n, nullptr); }
-inline int dia_to_csr_device(int64_t rows, int64_t cols, int64_t nd, int64_t pitch, const int *off, const double *va, int *Ap, int *Aj, double *Ax, int64_t cap, int64_t *n)
-{ return cmi_dia_to_csr_f64(rows, cols, nd, pitch, off, va, Ap, Aj, Ax, cap, n, nullptr); }
-inline int dia_to_csr_device(int64_t rows, int64_t cols, int64_t nd, int64_t pitch, const int *off, const float *va, int *Ap, int *Aj, float *Ax, int64_t cap, int64_t *n)
-{ return cmi_dia_to_csr_f32(rows, cols, nd, pitch, off, va, Ap, Aj, Ax, cap, n, nullptr); }
-
 // device ELL / DIA -> device CSR: count per row, exclusive scan, scatter (two calls: sizes first, then the arrays)
 template <typename V>
 struct device_fast_path<ell_matrix<int, V, device_memory>, csr_matrix<int, V, device_memory>, ell_format, csr_format> {
@@ -439,12 +423,12 @@ struct device_fast_path<ell_matrix<int, V, device_memory>, csr_matrix<int, V, de
         array1d<int, device_memory> offsets(s.num_rows + 1);
         int64_t n = 0;
         const int64_t w = s.column_indices.num_cols, pitch = s.column_indices.pitch;
-        check(ell_to_csr_device(s.num_rows, w, pitch, s.column_indices.values.data(), s.values.values.data(), offsets.data(), nullptr,
-                                static_cast<V *>(nullptr), 0, &n));
+        check(by_type<V>(cmi_ell_to_csr_f64, cmi_ell_to_csr_f32)(s.num_rows, w, pitch, s.column_indices.values.data(), s.values.values.data(), offsets.data(), nullptr,
+                                                                 static_cast<V *>(nullptr), 0, &n, nullptr));
         d.resize(s.num_rows, s.num_cols, static_cast<size_t>(n));
         if (n > 0)
-            check(ell_to_csr_device(s.num_rows, w, pitch, s.column_indices.values.data(), s.values.values.data(), d.row_offsets.data(),
-                                    d.column_indices.data(), d.values.data(), n, &n));
+            check(by_type<V>(cmi_ell_to_csr_f64, cmi_ell_to_csr_f32)(s.num_rows, w, pitch, s.column_indices.values.data(), s.values.values.data(), d.row_offsets.data(),
+                                                                     d.column_indices.data(), d.values.data(), n, &n, nullptr));
         else
             d.row_offsets = offsets;
         return true;
@@ -457,22 +441,17 @@ struct device_fast_path<dia_matrix<int, V, device_memory>, csr_matrix<int, V, de
         array1d<int, device_memory> offsets(s.num_rows + 1);
         int64_t n = 0;
         const int64_t nd = s.values.num_cols, pitch = s.values.pitch;
-        check(dia_to_csr_device(s.num_rows, s.num_cols, nd, pitch, s.diagonal_offsets.data(), s.values.values.data(), offsets.data(), nullptr,
-                                static_cast<V *>(nullptr), 0, &n));
+        check(by_type<V>(cmi_dia_to_csr_f64, cmi_dia_to_csr_f32)(s.num_rows, s.num_cols, nd, pitch, s.diagonal_offsets.data(), s.values.values.data(), offsets.data(), nullptr,
+                                                                 static_cast<V *>(nullptr), 0, &n, nullptr));
         d.resize(s.num_rows, s.num_cols, static_cast<size_t>(n));
         if (n > 0)
-            check(dia_to_csr_device(s.num_rows, s.num_cols, nd, pitch, s.diagonal_offsets.data(), s.values.values.data(), d.row_offsets.data(),
-                                    d.column_indices.data(), d.values.data(), n, &n));
+            check(by_type<V>(cmi_dia_to_csr_f64, cmi_dia_to_csr_f32)(s.num_rows, s.num_cols, nd, pitch, s.diagonal_offsets.data(), s.values.values.data(), d.row_offsets.data(),
+                                                                     d.column_indices.data(), d.values.data(), n, &n, nullptr));
         else
             d.row_offsets = offsets;
         return true;
     }
 };
-
-inline int hyb_to_csr_device(int64_t rows, int64_t w, int64_t pitch, const int *eAj, const double *eAx, int64_t nc, const int *cAi, const int *cAj, const double *cAx, int *Ap, int *Aj, double *Ax, int64_t cap, int64_t *n)
-{ return cmi_hyb_to_csr_f64(rows, w, pitch, eAj, eAx, nc, cAi, cAj, cAx, Ap, Aj, Ax, cap, n, nullptr); }
-inline int hyb_to_csr_device(int64_t rows, int64_t w, int64_t pitch, const int *eAj, const float *eAx, int64_t nc, const int *cAi, const int *cAj, const float *cAx, int *Ap, int *Aj, float *Ax, int64_t cap, int64_t *n)
-{ return cmi_hyb_to_csr_f32(rows, w, pitch, eAj, eAx, nc, cAi, cAj, cAx, Ap, Aj, Ax, cap, n, nullptr); }
 
 // device HYB -> device CSR: a row's ELL entries, then its COO entries; a COO part that is not row-sorted takes the general path
 template <typename V>
@@ -482,26 +461,21 @@ struct device_fast_path<hyb_matrix<int, V, device_memory>, csr_matrix<int, V, de
         array1d<int, device_memory> offsets(s.num_rows + 1);
         int64_t n = 0;
         const int64_t w = s.ell.column_indices.num_cols, pitch = s.ell.column_indices.pitch;
-        int st = hyb_to_csr_device(s.num_rows, w, pitch, s.ell.column_indices.values.data(), s.ell.values.values.data(), s.coo.num_entries,
-                                   s.coo.row_indices.data(), s.coo.column_indices.data(), s.coo.values.data(), offsets.data(), nullptr,
-                                   static_cast<V *>(nullptr), 0, &n);
+        int st = by_type<V>(cmi_hyb_to_csr_f64, cmi_hyb_to_csr_f32)(s.num_rows, w, pitch, s.ell.column_indices.values.data(), s.ell.values.values.data(), s.coo.num_entries,
+                                                                    s.coo.row_indices.data(), s.coo.column_indices.data(), s.coo.values.data(), offsets.data(), nullptr,
+                                                                    static_cast<V *>(nullptr), 0, &n, nullptr);
         if (st == CMI_ERROR_NOT_SUPPORTED) return false;
         check(st);
         d.resize(s.num_rows, s.num_cols, static_cast<size_t>(n));
         if (n > 0)
-            check(hyb_to_csr_device(s.num_rows, w, pitch, s.ell.column_indices.values.data(), s.ell.values.values.data(), s.coo.num_entries,
-                                    s.coo.row_indices.data(), s.coo.column_indices.data(), s.coo.values.data(), d.row_offsets.data(),
-                                    d.column_indices.data(), d.values.data(), n, &n));
+            check(by_type<V>(cmi_hyb_to_csr_f64, cmi_hyb_to_csr_f32)(s.num_rows, w, pitch, s.ell.column_indices.values.data(), s.ell.values.values.data(), s.coo.num_entries,
+                                                                     s.coo.row_indices.data(), s.coo.column_indices.data(), s.coo.values.data(), d.row_offsets.data(),
+                                                                     d.column_indices.data(), d.values.data(), n, &n, nullptr));
         else
             d.row_offsets = offsets;
         return true;
     }
 };
-
-inline int csr_to_hyb_coo_device(int64_t rows, const int *Ap, const int *Aj, const double *Ax, int64_t w, const int *off, int *cAi, int *cAj, double *cAx)
-{ return cmi_csr_to_hyb_coo_f64(rows, Ap, Aj, Ax, w, off, cAi, cAj, cAx, nullptr); }
-inline int csr_to_hyb_coo_device(int64_t rows, const int *Ap, const int *Aj, const float *Ax, int64_t w, const int *off, int *cAi, int *cAj, float *cAx)
-{ return cmi_csr_to_hyb_coo_f32(rows, Ap, Aj, Ax, w, off, cAi, cAj, cAx, nullptr); }
 
 // device CSR -> device HYB: only the row offsets visit the host (width heuristic + overflow offsets)
 template <typename V>
@@ -525,23 +499,18 @@ struct device_fast_path<csr_matrix<int, V, device_memory>, hyb_matrix<int, V, de
         }
         d.resize(s.num_rows, s.num_cols, s.num_entries - n_coo, n_coo, width);
         if (width > 0)
-            check(csr_to_ell_device(s.num_rows, s.row_offsets.data(), s.column_indices.data(), s.values.data(), width,
-                                    d.ell.column_indices.pitch, d.ell.column_indices.values.data(), d.ell.values.values.data()));
+            check(by_type<V>(cmi_csr_to_ell_f64, cmi_csr_to_ell_f32)(s.num_rows, s.row_offsets.data(), s.column_indices.data(), s.values.data(), width,
+                                                                     d.ell.column_indices.pitch, d.ell.column_indices.values.data(), d.ell.values.values.data(), nullptr));
         if (n_coo) {
             array1d<int, device_memory> dev_off(coo_off);
-            check(csr_to_hyb_coo_device(s.num_rows, s.row_offsets.data(), s.column_indices.data(), s.values.data(), width, dev_off.data(),
-                                        d.coo.row_indices.data(), d.coo.column_indices.data(), d.coo.values.data()));
+            check(by_type<V>(cmi_csr_to_hyb_coo_f64, cmi_csr_to_hyb_coo_f32)(s.num_rows, s.row_offsets.data(), s.column_indices.data(), s.values.data(), width, dev_off.data(),
+                                                                             d.coo.row_indices.data(), d.coo.column_indices.data(), d.coo.values.data(), nullptr));
             check(cmi_stream_synchronize(nullptr));
         }
         check(cmi_stream_synchronize(nullptr));
         return true;
     }
 };
-
-inline int csr_to_dia_device(int64_t rows, int64_t cols, const int *Ap, const int *Aj, const double *Ax, int64_t nd, int64_t pitch, const int *off, int *map, double *va)
-{ return cmi_csr_to_dia_f64(rows, cols, Ap, Aj, Ax, nd, pitch, off, map, va, nullptr); }
-inline int csr_to_dia_device(int64_t rows, int64_t cols, const int *Ap, const int *Aj, const float *Ax, int64_t nd, int64_t pitch, const int *off, int *map, float *va)
-{ return cmi_csr_to_dia_f32(rows, cols, Ap, Aj, Ax, nd, pitch, off, map, va, nullptr); }
 
 // device CSR -> device DIA: only the (few) diagonal offsets visit the host, to be sorted ascending
 template <typename V>
@@ -563,8 +532,8 @@ struct device_fast_path<csr_matrix<int, V, device_memory>, dia_matrix<int, V, de
         std::sort(off.begin(), off.end());
         d.resize(s.num_rows, s.num_cols, s.num_entries, static_cast<size_t>(nd));
         d.diagonal_offsets = off;
-        check(csr_to_dia_device(s.num_rows, s.num_cols, s.row_offsets.data(), s.column_indices.data(), s.values.data(), nd, d.values.pitch,
-                                d.diagonal_offsets.data(), slot_map.data(), d.values.values.data()));
+        check(by_type<V>(cmi_csr_to_dia_f64, cmi_csr_to_dia_f32)(s.num_rows, s.num_cols, s.row_offsets.data(), s.column_indices.data(), s.values.data(), nd, d.values.pitch,
+                                                                 d.diagonal_offsets.data(), slot_map.data(), d.values.values.data(), nullptr));
         check(cmi_stream_synchronize(nullptr));
         return true;
     }

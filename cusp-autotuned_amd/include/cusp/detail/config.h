@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <new>
 #include <string>
+#include <type_traits>
 
 #include "../../../../include/cusp_mi355x.h"
 #include "../exception.h"
@@ -26,6 +27,16 @@ inline void check(int status)
     case CMI_ERROR_IO: throw cusp::io_exception(msg);
     default: throw cusp::runtime_exception(msg);
     }
+}
+
+// The C-ABI names its entry points by value type: by_type<T>(cmi_x_f64, cmi_x_f32) is the first for T = double and the second for T = float,
+// so a call reads check(by_type<T>(cmi_blas_axpy_f64, cmi_blas_axpy_f32)(n, a, x, y, nullptr)) with both symbols at the call site.
+template <typename T> struct is_real : std::integral_constant<bool, std::is_same<T, double>::value || std::is_same<T, float>::value> {};
+template <typename T, typename F64, typename F32> constexpr auto by_type([[maybe_unused]] F64 *f64, [[maybe_unused]] F32 *f32)
+{
+    static_assert(is_real<T>::value, "the device kernels are implemented for float and double");
+    if constexpr (std::is_same<T, double>::value) return f64;
+    else return f32;
 }
 
 // cusp::detail::round_up (reference cusp/detail/utils.h:24-28)

@@ -244,17 +244,15 @@ public:
 
 private:
     mutable detail::plan_slot plan_;
-    static int device_sort(int64_t r, int64_t c, int64_t n, int *ai, int *aj, double *ax, int ac) { return cmi_coo_sort_by_row_f64(r, c, n, ai, aj, ax, ac, nullptr); }
-    static int device_sort(int64_t r, int64_t c, int64_t n, int *ai, int *aj, float *ax, int ac) { return cmi_coo_sort_by_row_f32(r, c, n, ai, aj, ax, ac, nullptr); }
-    template <typename A, typename B, typename C> static int device_sort(int64_t, int64_t, int64_t, A *, B *, C *, int) { return -1; } // no device sort for these types
     static const bool on_device = std::is_same<MemorySpace, device_memory>::value && std::is_same<IndexType, int>::value &&
-                                  (std::is_same<ValueType, double>::value || std::is_same<ValueType, float>::value);
+                                  detail::is_real<ValueType>::value;
     void sort_impl(bool and_column)
     {
         plan_.reset();
-        if (on_device) {
-            detail::check(device_sort((int64_t)this->num_rows, (int64_t)this->num_cols, (int64_t)row_indices.size(), row_indices.data(),
-                                      column_indices.data(), values.data(), and_column ? 1 : 0));
+        if constexpr (on_device) {
+            detail::check(detail::by_type<ValueType>(cmi_coo_sort_by_row_f64, cmi_coo_sort_by_row_f32)(
+                (int64_t)this->num_rows, (int64_t)this->num_cols, (int64_t)row_indices.size(), row_indices.data(),
+                                                                                                       column_indices.data(), values.data(), and_column ? 1 : 0, nullptr));
             return;
         }
         array1d<IndexType, host_memory> ri(row_indices), ci(column_indices);

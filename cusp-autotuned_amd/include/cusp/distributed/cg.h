@@ -50,17 +50,6 @@ void cg_plain(const csr_matrix<I, V, L> &A, X &x, const B &b, Monitor &monitor)
     }
 }
 
-namespace detail {
-inline int local_dot_plan(const cmi_plan *pl, const int *Ap, const int *Aj, const double *Ax, const double *x, double *y, const double *w, double *yp, void *ws)
-{ return cmi_spmv_csr_dot_plan_f64(pl, Ap, Aj, Ax, x, y, w, yp, ws, nullptr); }
-inline int local_dot_plan(const cmi_plan *pl, const int *Ap, const int *Aj, const float *Ax, const float *x, float *y, const float *w, double *yp, void *ws)
-{ return cmi_spmv_csr_dot_plan_f32(pl, Ap, Aj, Ax, x, y, w, yp, ws, nullptr); }
-inline int local_dot(int64_t r, int64_t c, int64_t n, const int *Ap, const int *Aj, const double *Ax, const double *x, double *y, const double *w, double *yp, void *ws)
-{ return cmi_spmv_csr_dot_f64(r, c, n, Ap, Aj, Ax, x, y, w, yp, ws, nullptr, nullptr); }
-inline int local_dot(int64_t r, int64_t c, int64_t n, const int *Ap, const int *Aj, const float *Ax, const float *x, float *y, const float *w, double *yp, void *ws)
-{ return cmi_spmv_csr_dot_f32(r, c, n, Ap, Aj, Ax, x, y, w, yp, ws, nullptr, nullptr); }
-} // namespace detail
-
 // y_local <- A_local * (exchange buffer) and *yp <- <y_local, w_local> in one launch (w: this rank's slice of p)
 template <typename I, typename V>
 void multiply_dot_local(const csr_matrix<I, V, cusp::device_memory> &A, V *y_local, const V *w_local, double *yp, void *ws)
@@ -68,16 +57,13 @@ void multiply_dot_local(const csr_matrix<I, V, cusp::device_memory> &A, V *y_loc
     const auto &a = A.local;
     if (a.num_rows == 0) { cusp::detail::check(cmi_memset(yp, 0, sizeof(double), nullptr)); return; }
     if (const cmi_plan *pl = a.num_entries ? a.plan() : nullptr)
-        cusp::detail::check(detail::local_dot_plan(pl, a.row_offsets.data(), a.column_indices.data(), a.values.data(), A.x_full(), y_local, w_local, yp, ws));
+        cusp::detail::check(cusp::detail::by_type<V>(cmi_spmv_csr_dot_plan_f64, cmi_spmv_csr_dot_plan_f32)(
+            pl, a.row_offsets.data(), a.column_indices.data(), a.values.data(), A.x_full(), y_local, w_local, yp, ws, nullptr));
     else
-        cusp::detail::check(detail::local_dot((int64_t)a.num_rows, (int64_t)a.num_cols, (int64_t)a.num_entries, a.row_offsets.data(), a.column_indices.data(), a.values.data(),
-                                              A.x_full(), y_local, w_local, yp, ws));
+        cusp::detail::check(cusp::detail::by_type<V>(cmi_spmv_csr_dot_f64, cmi_spmv_csr_dot_f32)((int64_t)a.num_rows, (int64_t)a.num_cols, (int64_t)a.num_entries,
+                                                                                                 a.row_offsets.data(), a.column_indices.data(), a.values.data(),
+                                                                                                 A.x_full(), y_local, w_local, yp, ws, nullptr, nullptr));
 }
-
-namespace detail {
-inline int cg_direction_(size_t n, const double *rn, const double *ro, const double *r, double *p) { return cmi_cg_direction_f64((int64_t)n, rn, ro, r, p, nullptr); }
-inline int cg_direction_(size_t n, const double *rn, const double *ro, const float *r, float *p) { return cmi_cg_direction_f32((int64_t)n, rn, ro, r, p, nullptr); }
-} // namespace detail
 
 template <typename I, typename V, typename X, typename B, typename Monitor>
 void cg_fused_peer(const csr_matrix<I, V, cusp::device_memory> &A, X &x, const B &b, Monitor &monitor)
@@ -102,7 +88,7 @@ void cg_fused_peer(const csr_matrix<I, V, cusp::device_memory> &A, X &x, const B
     cusp::blas::axpby(b, y, r, V(1), V(-1));
     A.fence();                                                           // the peers have pulled x out of the buffer p reuses
     cusp::blas::copy(r, p);
-    cusp::detail::check(kd::dotd_(N, r.data(), r.data(), rr[0], w.ws));
+    cusp::detail::check(cusp::detail::by_type<V>(cmi_blas_dot_f64, cmi_blas_dotd_f32)(N, r.data(), r.data(), rr[0], w.ws, nullptr));
     comm.allreduce_sum(rr[0], 1, cusp::device_memory());
     A.pull();                                                            // p's halo, ordered behind every rank's copy by the all-reduce
     rr_host.fetch(rr[0]);
@@ -111,13 +97,15 @@ void cg_fused_peer(const csr_matrix<I, V, cusp::device_memory> &A, X &x, const B
         multiply_dot_local(A, y.data(), p.data(), yp, w.ws);             // halos of p are already in place: no exchange
         comm.allreduce_sum(yp, 1, cusp::device_memory());
         if (monitor.finished_norm(static_cast<typename Monitor::Real>(std::sqrt(rr_host.wait())))) break;
-        cusp::detail::check(kd::cg_update_(N, rr[cur], yp, y.data(), r.data(), rr[cur ^ 1], nullptr, w.ws));
+        cusp::detail::check(cusp::detail::by_type<V>(cmi_cg_update_f64, cmi_cg_update_f32)(N, rr[cur], yp, nullptr, y.data(), nullptr, r.data(), rr[cur ^ 1], nullptr,
+                                                                                           w.ws, nullptr));
         comm.allreduce_sum(rr[cur ^ 1], 1, cusp::device_memory());
         rr_host.fetch(rr[cur ^ 1]);
         r_ex.pull();                                                     // the peers' boundary r
         for (const auto &h : halo)                                       // halo: p <- r + beta p (the owner's arithmetic)
-            cusp::detail::check(detail::cg_direction_((size_t)h.second, rr[cur ^ 1], rr[cur], r_full + h.first, p_full + h.first));
-        cusp::detail::check(kd::cg_direction_x_(N, rr[cur ^ 1], rr[cur], yp, r.data(), p.data(), x.data()));
+            cusp::detail::check(cusp::detail::by_type<V>(cmi_cg_direction_f64, cmi_cg_direction_f32)(
+                (size_t)h.second, rr[cur ^ 1], rr[cur], r_full + h.first, p_full + h.first, nullptr));
+        cusp::detail::check(cusp::detail::by_type<V>(cmi_cg_direction_x_f64, cmi_cg_direction_x_f32)(N, rr[cur ^ 1], rr[cur], yp, r.data(), p.data(), x.data(), nullptr));
         cur ^= 1;
         ++monitor;
     }
@@ -143,7 +131,7 @@ void cg_fused(const csr_matrix<I, V, cusp::device_memory> &A, X &x, const B &b, 
     cusp::multiply(A, x, y);
     cusp::blas::axpby(b, y, r, V(1), V(-1));
     cusp::blas::copy(r, p);
-    cusp::detail::check(kd::dotd_(N, r.data(), r.data(), rr[0], w.ws));
+    cusp::detail::check(cusp::detail::by_type<V>(cmi_blas_dot_f64, cmi_blas_dotd_f32)(N, r.data(), r.data(), rr[0], w.ws, nullptr));
     comm.allreduce_sum(rr[0], 1, cusp::device_memory());
     rr_host.fetch(rr[0]);
     int cur = 0;
@@ -152,10 +140,11 @@ void cg_fused(const csr_matrix<I, V, cusp::device_memory> &A, X &x, const B &b, 
         multiply_dot_local(A, y.data(), p.data(), yp, w.ws);            // y <- A p, local <y, p>                  like the SpMV
         comm.allreduce_sum(yp, 1, cusp::device_memory());               //                                          of cg.h)
         if (monitor.finished_norm(static_cast<typename Monitor::Real>(std::sqrt(rr_host.wait())))) break; // the one host read
-        cusp::detail::check(kd::cg_update_(N, rr[cur], yp, y.data(), r.data(), rr[cur ^ 1], nullptr, w.ws)); // r, local <r,r>
+        cusp::detail::check(cusp::detail::by_type<V>(cmi_cg_update_f64, cmi_cg_update_f32)(N, rr[cur], yp, nullptr, y.data(), nullptr, r.data(), rr[cur ^ 1], nullptr,
+                                                                                           w.ws, nullptr)); // r, local <r,r>
         comm.allreduce_sum(rr[cur ^ 1], 1, cusp::device_memory());
         rr_host.fetch(rr[cur ^ 1]);
-        cusp::detail::check(kd::cg_direction_x_(N, rr[cur ^ 1], rr[cur], yp, r.data(), p.data(), x.data())); // x, p
+        cusp::detail::check(cusp::detail::by_type<V>(cmi_cg_direction_x_f64, cmi_cg_direction_x_f32)(N, rr[cur ^ 1], rr[cur], yp, r.data(), p.data(), x.data(), nullptr)); // x, p
         cur ^= 1;
         ++monitor;
     }

@@ -78,10 +78,11 @@ public:
     // ---- collectives by memory space ------------------------------------------------------------------------------------------
     // recv[r * count, +count) <- rank r's send (in place when send == recv + rank * count)
     template <typename T> void allgather(const T *send, T *recv, size_t count, host_memory) { star_->allgather(send, recv, count * sizeof(T)); }
-    void allgather(const double *send, double *recv, size_t count, device_memory, void *stream = nullptr)
-    { if (staged_) staged_allgather(send, recv, count, stream); else cusp::detail::check(cmi_allgather_f64(device(), send, recv, (int64_t)count, stream)); }
-    void allgather(const float *send, float *recv, size_t count, device_memory, void *stream = nullptr)
-    { if (staged_) staged_allgather(send, recv, count, stream); else cusp::detail::check(cmi_allgather_f32(device(), send, recv, (int64_t)count, stream)); }
+    template <typename T> void allgather(const T *send, T *recv, size_t count, device_memory, void *stream = nullptr)
+    {
+        if (staged_) staged_allgather(send, recv, count, stream);
+        else cusp::detail::check(cusp::detail::by_type<T>(cmi_allgather_f64, cmi_allgather_f32)(device(), send, recv, (int64_t)count, stream));
+    }
     // unequal pieces (element counts / displacements, `size()` entries each)
     template <typename T> void allgatherv(const T *send, T *recv, const int64_t *counts, const int64_t *displs, host_memory)
     {
@@ -89,10 +90,11 @@ public:
         for (int r = 0; r < world_; r++) { c[r] = (size_t)counts[r] * sizeof(T); d[r] = (size_t)displs[r] * sizeof(T); }
         star_->allgatherv(send, recv, c.data(), d.data());
     }
-    void allgatherv(const double *send, double *recv, const int64_t *counts, const int64_t *displs, device_memory, int algorithm = 1, void *stream = nullptr)
-    { if (staged_) staged_allgatherv(send, recv, counts, displs, stream); else cusp::detail::check(cmi_allgatherv_f64(device(), send, recv, counts, displs, algorithm, stream)); }
-    void allgatherv(const float *send, float *recv, const int64_t *counts, const int64_t *displs, device_memory, int algorithm = 1, void *stream = nullptr)
-    { if (staged_) staged_allgatherv(send, recv, counts, displs, stream); else cusp::detail::check(cmi_allgatherv_f32(device(), send, recv, counts, displs, algorithm, stream)); }
+    template <typename T> void allgatherv(const T *send, T *recv, const int64_t *counts, const int64_t *displs, device_memory, int algorithm = 1, void *stream = nullptr)
+    {
+        if (staged_) staged_allgatherv(send, recv, counts, displs, stream);
+        else cusp::detail::check(cusp::detail::by_type<T>(cmi_allgatherv_f64, cmi_allgatherv_f32)(device(), send, recv, counts, displs, algorithm, stream));
+    }
     // sum of `n` doubles over the ranks, in place
     void allreduce_sum(double *v, size_t n, host_memory) { star_->allreduce(v, n, 0); }
     void allreduce_sum(double *v, size_t n, device_memory, void *stream = nullptr)

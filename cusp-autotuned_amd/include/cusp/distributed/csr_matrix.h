@@ -53,10 +53,6 @@ template <typename I, typename V> void column_span(const cusp::csr_matrix<I, V, 
     lo = hi = (int)a.column_indices[0];
     for (size_t k = 1; k < a.num_entries; k++) { const int c = (int)a.column_indices[k]; lo = c < lo ? c : lo; hi = c > hi ? c : hi; }
 }
-inline int halo_call(cmi_comm *c, double *x, int n, const int *peers, const int64_t *sl, const int64_t *sc, const int64_t *rl, const int64_t *rc, void *s)
-{ return cmi_halo_exchange_f64(c, x, n, peers, sl, sc, rl, rc, s); }
-inline int halo_call(cmi_comm *c, float *x, int n, const int *peers, const int64_t *sl, const int64_t *sc, const int64_t *rl, const int64_t *rc, void *s)
-{ return cmi_halo_exchange_f32(c, x, n, peers, sl, sc, rl, rc, s); }
 } // namespace detail
 
 // A full-length vector buffer (indexed by global column) that peers can PULL from: the allocation (its own cmi_malloc, so that its
@@ -371,15 +367,12 @@ private:
         interior_b_ = b;
         overlap_ = true;
     }
-    static int rows_call(int64_t rows, int64_t cols, int64_t nnz, const int *Ap, const int *Aj, const double *Ax, const double *x, double *y, const cmi_config *c, void *s)
-    { return cmi_spmv_csr_f64(rows, cols, nnz, Ap, Aj, Ax, x, y, 0, c, s); }
-    static int rows_call(int64_t rows, int64_t cols, int64_t nnz, const int *Ap, const int *Aj, const float *Ax, const float *x, float *y, const cmi_config *c, void *s)
-    { return cmi_spmv_csr_f32(rows, cols, nnz, Ap, Aj, Ax, x, y, 0, c, s); }
     void rows(int64_t a, int64_t b, ValueType *y, void *stream) const // y[a:b] = A[a:b, :] * buffer
     {
         if (b <= a) return;
-        cusp::detail::check(rows_call(b - a, (int64_t)local.num_cols, (int64_t)local.num_entries, reinterpret_cast<const int *>(local.row_offsets.data()) + a,
-                                      reinterpret_cast<const int *>(local.column_indices.data()), local.values.data(), xbuf_.data.data(), y + a, &row_cfg_, stream));
+        cusp::detail::check(cusp::detail::by_type<ValueType>(cmi_spmv_csr_f64, cmi_spmv_csr_f32)(
+            b - a, (int64_t)local.num_cols, (int64_t)local.num_entries, reinterpret_cast<const int *>(local.row_offsets.data()) + a,
+            reinterpret_cast<const int *>(local.column_indices.data()), local.values.data(), xbuf_.data.data(), y + a, 0 /* y = A x */, &row_cfg_, stream));
     }
     void multiply_overlapped(ValueType *, void *, cusp::host_memory) const {}
     void multiply_overlapped(ValueType *y, void *stream, cusp::device_memory) const
@@ -413,7 +406,8 @@ private:
                 }
                 comm_->staged_exchange(buf, xbuf_.data.size(), sl.data(), sn.data(), rl.data(), rn.data(), stream);
             } else
-                cusp::detail::check(detail::halo_call(comm_->device(), buf, (int)peers_.size(), peers_.data(), send_lo_.data(), send_n_.data(), recv_lo_.data(), recv_n_.data(), stream));
+                cusp::detail::check(cusp::detail::by_type<ValueType>(cmi_halo_exchange_f64, cmi_halo_exchange_f32)(
+                    comm_->device(), buf, (int)peers_.size(), peers_.data(), send_lo_.data(), send_n_.data(), recv_lo_.data(), recv_n_.data(), stream));
         } else if (uniform_) {
             comm_->allgather(buf + row_begin(), buf, (size_t)count_, cusp::device_memory(), stream); // (a 1-rank world still goes through RCCL)
         } else {
@@ -449,13 +443,12 @@ private:
 // rows only -- on the device straight into HBM (cmi_poisson5pt_csr_*: 1e8-row matrices never exist in one piece anywhere), on the
 // host with the same stencil loop.
 namespace detail {
-inline int poisson_block(int64_t m, int64_t n, int64_t r0, int64_t r1, int *Ap, int *Aj, double *Ax) { return cmi_poisson5pt_csr_f64(m, n, r0, r1, Ap, Aj, Ax, nullptr); }
-inline int poisson_block(int64_t m, int64_t n, int64_t r0, int64_t r1, int *Ap, int *Aj, float *Ax) { return cmi_poisson5pt_csr_f32(m, n, r0, r1, Ap, Aj, Ax, nullptr); }
 template <typename V> void poisson_rows(cusp::csr_matrix<int, V, cusp::device_memory> &b, size_t m, size_t n, size_t r0, size_t r1)
 {
     const size_t nnz = (size_t)cmi_poisson5pt_shard_entries((int64_t)m, (int64_t)n, (int64_t)r0, (int64_t)r1);
     b.resize(r1 - r0, m * n, nnz);
-    cusp::detail::check(poisson_block((int64_t)m, (int64_t)n, (int64_t)r0, (int64_t)r1, b.row_offsets.data(), b.column_indices.data(), b.values.data()));
+    cusp::detail::check(cusp::detail::by_type<V>(cmi_poisson5pt_csr_f64, cmi_poisson5pt_csr_f32)((int64_t)m, (int64_t)n, (int64_t)r0, (int64_t)r1, b.row_offsets.data(),
+                                                                                                 b.column_indices.data(), b.values.data(), nullptr));
 }
 template <typename I, typename V> void poisson_rows(cusp::csr_matrix<I, V, cusp::host_memory> &b, size_t m, size_t n, size_t r0, size_t r1)
 {

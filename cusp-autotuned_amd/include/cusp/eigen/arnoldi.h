@@ -40,11 +40,6 @@ template <typename Matrix> struct fused_on_device {
     static const bool value = std::is_same<typename Matrix::memory_space, cusp::device_memory>::value && (std::is_same<V, double>::value || std::is_same<V, float>::value);
 };
 
-inline int axpy_dot(size_t n, const double *h, const double *v, double *w, const double *u, double *out, void *ws) { return cmi_blas_axpy_dot_f64(n, h, v, w, u, out, ws, nullptr); }
-inline int axpy_dot(size_t n, const double *h, const float *v, float *w, const float *u, double *out, void *ws) { return cmi_blas_axpy_dot_f32(n, h, v, w, u, out, ws, nullptr); }
-inline int scal_recip(size_t n, const void *s, int squared, double *x, double *s_out) { return cmi_blas_scal_recip_f64(n, s, squared, x, s_out, nullptr); }
-inline int scal_recip(size_t n, const void *s, int squared, float *x, double *s_out) { return cmi_blas_scal_recip_f32(n, s, squared, x, s_out, nullptr); }
-
 // `count` doubles of device memory for the coefficients of one step, kept per thread between calls (as gmres keeps its own)
 inline double *device_coefficients(size_t count)
 {
@@ -55,8 +50,9 @@ inline double *device_coefficients(size_t count)
 // x <- x / ||x||_2 with the norm in device memory (c[0] receives its square)
 template <typename Vec> void normalize_on_device(Vec &x, double *c, void *ws)
 {
-    cusp::detail::check(axpy_dot(x.size(), nullptr, x.data(), x.data(), x.data(), c, ws));
-    cusp::detail::check(scal_recip(x.size(), c, 1, x.data(), nullptr));
+    typedef typename Vec::value_type T;
+    cusp::detail::check(cusp::detail::by_type<T>(cmi_blas_axpy_dot_f64, cmi_blas_axpy_dot_f32)(x.size(), nullptr, x.data(), x.data(), x.data(), c, ws, nullptr));
+    cusp::detail::check(cusp::detail::by_type<T>(cmi_blas_scal_recip_f64, cmi_blas_scal_recip_f32)(x.size(), c, 1, x.data(), nullptr, nullptr));
 }
 
 // the leading `size` x `size` block of H_ (size = steps taken, breakdown step included: see the head of this file)
@@ -109,10 +105,14 @@ template <typename Matrix, typename Array2d> void arnoldi(const Matrix &A, Array
     for (j = 0; j < maxiter; j++) {
         ValueType *w = V[j + 1].data();
         cusp::multiply(A, V[j], V[j + 1]);
-        cusp::detail::check(axpy_dot(N, nullptr, w, w, V[0].data(), c, ws.ws));                                              // <V[0], w>
-        for (size_t i = 0; i < j; i++) cusp::detail::check(axpy_dot(N, c + i, V[i].data(), w, V[i + 1].data(), c + i + 1, ws.ws)); // w -= h_i V[i]; <V[i+1], w>
-        cusp::detail::check(axpy_dot(N, c + j, V[j].data(), w, w, c + j + 1, ws.ws));                                        // w -= h_j V[j]; <w, w>
-        cusp::detail::check(scal_recip(N, c + j + 1, 1, w, nullptr));                                                        // w <- w / beta: behind the read's back
+        cusp::detail::check(cusp::detail::by_type<ValueType>(cmi_blas_axpy_dot_f64, cmi_blas_axpy_dot_f32)(
+            N, nullptr, w, w, V[0].data(), c, ws.ws, nullptr)); // <V[0], w>
+        for (size_t i = 0; i < j; i++) cusp::detail::check(cusp::detail::by_type<ValueType>(cmi_blas_axpy_dot_f64, cmi_blas_axpy_dot_f32)(
+            N, c + i, V[i].data(), w, V[i + 1].data(), c + i + 1, ws.ws, nullptr)); // w -= h_i V[i]; <V[i+1], w>
+        cusp::detail::check(cusp::detail::by_type<ValueType>(cmi_blas_axpy_dot_f64, cmi_blas_axpy_dot_f32)(
+            N, c + j, V[j].data(), w, w, c + j + 1, ws.ws, nullptr)); // w -= h_j V[j]; <w, w>
+        cusp::detail::check(cusp::detail::by_type<ValueType>(cmi_blas_scal_recip_f64, cmi_blas_scal_recip_f32)(
+            N, c + j + 1, 1, w, nullptr, nullptr)); // w <- w / beta: behind the read's back
         cusp::detail::check(cmi_memcpy_d2h(host.data(), c, (j + 2) * sizeof(double), nullptr));                              // the step's one host read
         for (size_t i = 0; i <= j; i++) H_(i, j) = static_cast<ValueType>(host[i]);
         const ValueType beta = static_cast<ValueType>(std::sqrt(host[j + 1]));
@@ -167,9 +167,12 @@ template <typename Matrix, typename Array2d> void lanczos_estimate(const Matrix 
     size_t j;
     for (j = 0; j < maxiter; j++) {
         cusp::multiply(A, v1, w);
-        cusp::detail::check(axpy_dot(N, j >= 1 ? c + 2 : nullptr, v0.data(), w.data(), v1.data(), c, ws.ws)); // w -= beta v0 (j >= 1); alpha = <w, v1>
-        cusp::detail::check(axpy_dot(N, c, v1.data(), w.data(), w.data(), c + 1, ws.ws));                     // w -= alpha v1; <w, w>
-        cusp::detail::check(scal_recip(N, c + 1, 1, w.data(), c + 2));                                        // w <- w / beta; beta stays on the device
+        cusp::detail::check(cusp::detail::by_type<ValueType>(cmi_blas_axpy_dot_f64, cmi_blas_axpy_dot_f32)(
+            N, j >= 1 ? c + 2 : nullptr, v0.data(), w.data(), v1.data(), c, ws.ws, nullptr)); // w -= beta v0 (j >= 1); alpha = <w, v1>
+        cusp::detail::check(cusp::detail::by_type<ValueType>(cmi_blas_axpy_dot_f64, cmi_blas_axpy_dot_f32)(
+            N, c, v1.data(), w.data(), w.data(), c + 1, ws.ws, nullptr)); // w -= alpha v1; <w, w>
+        cusp::detail::check(cusp::detail::by_type<ValueType>(cmi_blas_scal_recip_f64, cmi_blas_scal_recip_f32)(
+            N, c + 1, 1, w.data(), c + 2, nullptr)); // w <- w / beta; beta stays on the device
         cusp::detail::check(cmi_memcpy_d2h(host, c, 2 * sizeof(double), nullptr));                            // the step's one host read
         const ValueType beta = static_cast<ValueType>(std::sqrt(host[1]));
         H_(j, j) = static_cast<ValueType>(host[0]);

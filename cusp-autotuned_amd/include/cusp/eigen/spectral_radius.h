@@ -88,16 +88,11 @@ template <typename M> struct native_row_sums {
     static const bool value = std::is_same<typename M::memory_space, cusp::device_memory>::value && std::is_same<typename M::index_type, int>::value &&
                               (std::is_same<V, double>::value || std::is_same<V, float>::value);
 };
-inline int csr_sums(size_t n, const int *Ap, const double *Ax, double *s, int acc) { return cmi_csr_abs_row_sums_f64(n, Ap, Ax, s, acc, nullptr); }
-inline int csr_sums(size_t n, const int *Ap, const float *Ax, float *s, int acc) { return cmi_csr_abs_row_sums_f32(n, Ap, Ax, s, acc, nullptr); }
-inline int ell_sums(size_t r, size_t c, size_t w, size_t p, const double *Ax, const int *rl, double *s, int acc) { return cmi_ell_abs_row_sums_f64(r, c, w, p, nullptr, Ax, rl, s, acc, nullptr); }
-inline int ell_sums(size_t r, size_t c, size_t w, size_t p, const float *Ax, const int *rl, float *s, int acc) { return cmi_ell_abs_row_sums_f32(r, c, w, p, nullptr, Ax, rl, s, acc, nullptr); }
-inline int dia_sums(size_t r, size_t c, size_t d, size_t p, const int *off, const double *v, double *s, int acc) { return cmi_dia_abs_row_sums_f64(r, c, d, p, off, v, s, acc, nullptr); }
-inline int dia_sums(size_t r, size_t c, size_t d, size_t p, const int *off, const float *v, float *s, int acc) { return cmi_dia_abs_row_sums_f32(r, c, d, p, off, v, s, acc, nullptr); }
 
 template <typename M, typename S> void device_row_sums(const M &A, S &sums, int acc, cusp::csr_format)
 {
-    cusp::detail::check(csr_sums(A.num_rows, A.row_offsets.data(), A.values.data(), sums.data(), acc));
+    cusp::detail::check(cusp::detail::by_type<typename M::value_type>(cmi_csr_abs_row_sums_f64, cmi_csr_abs_row_sums_f32)(
+        A.num_rows, A.row_offsets.data(), A.values.data(), sums.data(), acc, nullptr));
 }
 template <typename M, typename S> void device_row_sums(const M &A, S &sums, int acc, cusp::coo_format)
 {
@@ -110,7 +105,8 @@ template <typename M, typename S> void device_row_sums(const M &A, S &sums, int 
     int sorted = 0;
     cusp::detail::check(cmi_coo_row_offsets((int64_t)A.num_rows, (int64_t)A.num_entries, A.row_indices.data(), offsets.data(), &sorted, nullptr));
     if (sorted) {
-        cusp::detail::check(csr_sums(A.num_rows, offsets.data(), A.values.data(), sums.data(), acc));
+        cusp::detail::check(cusp::detail::by_type<typename M::value_type>(cmi_csr_abs_row_sums_f64, cmi_csr_abs_row_sums_f32)(
+            A.num_rows, offsets.data(), A.values.data(), sums.data(), acc, nullptr));
         cusp::detail::check(cmi_stream_synchronize(nullptr)); // `offsets` is released on return
         return;
     }
@@ -120,11 +116,13 @@ template <typename M, typename S> void device_row_sums(const M &A, S &sums, int 
 }
 template <typename M, typename S> void device_row_sums(const M &A, S &sums, int acc, cusp::ell_format)
 {
-    cusp::detail::check(ell_sums(A.num_rows, A.num_cols, A.values.num_cols, A.values.pitch, cusp::detail::data_of(A.values), cusp::detail::row_lengths_of(A, 0), sums.data(), acc));
+    cusp::detail::check(cusp::detail::by_type<typename M::value_type>(cmi_ell_abs_row_sums_f64, cmi_ell_abs_row_sums_f32)(
+        A.num_rows, A.num_cols, A.values.num_cols, A.values.pitch, nullptr, cusp::detail::data_of(A.values), cusp::detail::row_lengths_of(A, 0), sums.data(), acc, nullptr)); // (the column indices play no part)
 }
 template <typename M, typename S> void device_row_sums(const M &A, S &sums, int acc, cusp::dia_format)
 {
-    cusp::detail::check(dia_sums(A.num_rows, A.num_cols, A.values.num_cols, A.values.pitch, A.diagonal_offsets.data(), cusp::detail::data_of(A.values), sums.data(), acc));
+    cusp::detail::check(cusp::detail::by_type<typename M::value_type>(cmi_dia_abs_row_sums_f64, cmi_dia_abs_row_sums_f32)(
+        A.num_rows, A.num_cols, A.values.num_cols, A.values.pitch, A.diagonal_offsets.data(), cusp::detail::data_of(A.values), sums.data(), acc, nullptr));
 }
 template <typename M, typename S> void device_row_sums(const M &A, S &sums, int acc, cusp::hyb_format)
 {
@@ -139,7 +137,7 @@ template <typename M> double disks_spectral_radius(const M &A, std::true_type) /
     cusp::array1d<V, cusp::device_memory> sums(A.num_rows);
     device_row_sums(A, sums, 0, typename M::format());
     cusp::blas::detail::device_workspace &w = cusp::blas::detail::workspace();
-    cusp::detail::check(cusp::blas::detail::c_amax(sums.size(), sums.data(), static_cast<V *>(w.result), nullptr, w.ws));
+    cusp::detail::check(cusp::detail::by_type<V>(cmi_blas_amax_f64, cmi_blas_amax_f32)(sums.size(), sums.data(), static_cast<V *>(w.result), nullptr, w.ws, nullptr));
     V r;
     cusp::detail::check(cmi_memcpy_d2h(&r, w.result, sizeof(V), nullptr));
     return static_cast<double>(r);
@@ -171,8 +169,8 @@ template <typename M> double power_iteration(const M &A, size_t k, std::true_typ
     cusp::copy(cusp::random_array<V>(N), x);
     cusp::blas::detail::device_workspace &w = cusp::blas::detail::workspace();
     for (size_t i = 0; i < k; i++) {
-        cusp::detail::check(cusp::blas::detail::c_amax(N, x.data(), static_cast<V *>(w.result), nullptr, w.ws));
-        cusp::detail::check(scal_recip(N, w.result, 0, x.data(), nullptr));
+        cusp::detail::check(cusp::detail::by_type<V>(cmi_blas_amax_f64, cmi_blas_amax_f32)(N, x.data(), static_cast<V *>(w.result), nullptr, w.ws, nullptr));
+        cusp::detail::check(cusp::detail::by_type<V>(cmi_blas_scal_recip_f64, cmi_blas_scal_recip_f32)(N, w.result, 0, x.data(), nullptr, nullptr));
         cusp::multiply(A, x, y);
         x.swap(y);
     }

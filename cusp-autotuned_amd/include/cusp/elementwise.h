@@ -83,13 +83,6 @@ template <typename A, typename B, typename C> void host_elementwise(const A &a, 
     cusp::convert(cc, c);
 }
 
-inline int c_elementwise(int64_t m, int64_t n, int64_t na, const int *Ap, const int *Aj, const double *Ax, int64_t nb, const int *Bp, const int *Bj,
-                         const double *Bx, int op, int *Cp, int *Cj, double *Cx, int64_t cap, int *sorted)
-{ return cmi_csr_elementwise_f64(m, n, na, Ap, Aj, Ax, nb, Bp, Bj, Bx, op, Cp, Cj, Cx, cap, sorted, nullptr); }
-inline int c_elementwise(int64_t m, int64_t n, int64_t na, const int *Ap, const int *Aj, const float *Ax, int64_t nb, const int *Bp, const int *Bj,
-                         const float *Bx, int op, int *Cp, int *Cj, float *Cx, int64_t cap, int *sorted)
-{ return cmi_csr_elementwise_f32(m, n, na, Ap, Aj, Ax, nb, Bp, Bj, Bx, op, Cp, Cj, Cx, cap, sorted, nullptr); }
-
 template <typename A, typename B, typename C> void device_elementwise(const A &a, const B &b, C &c, int op, csr_format)
 {
     typedef typename C::value_type V;
@@ -100,9 +93,10 @@ template <typename A, typename B, typename C> void device_elementwise(const A &a
     const size_t cap = a.num_entries + b.num_entries;
     csr_matrix<int, V, device_memory> t(a.num_rows, a.num_cols, cap);
     int sorted = 0;
-    check(c_elementwise((int64_t)a.num_rows, (int64_t)a.num_cols, (int64_t)a.num_entries, a.row_offsets.data(), a.column_indices.data(), a.values.data(),
+    check(by_type<V>(cmi_csr_elementwise_f64, cmi_csr_elementwise_f32)((int64_t)a.num_rows, (int64_t)a.num_cols, (int64_t)a.num_entries, a.row_offsets.data(),
+                                                                       a.column_indices.data(), a.values.data(),
                         (int64_t)b.num_entries, b.row_offsets.data(), b.column_indices.data(), b.values.data(), op, t.row_offsets.data(), t.column_indices.data(),
-                        t.values.data(), (int64_t)cap, &sorted));
+                                                                       t.values.data(), (int64_t)cap, &sorted, nullptr));
     if (!sorted) { // an operand's rows are not sorted by column: the host path on host copies
         csr_matrix<int, V, host_memory> ha(a), hb(b), hc;
         host_elementwise(ha, hb, hc, op, csr_format());

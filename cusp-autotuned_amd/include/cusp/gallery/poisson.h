@@ -35,16 +35,12 @@ template <typename I, typename V> void poisson5pt_host_dia(dia_matrix<I, V, host
     dia.num_entries = nnz;
 }
 
-inline int build_csr(int64_t m, int64_t n, int *Ap, int *Aj, double *Ax) { return cmi_poisson5pt_csr_f64(m, n, 0, m * n, Ap, Aj, Ax, nullptr); }
-inline int build_csr(int64_t m, int64_t n, int *Ap, int *Aj, float *Ax) { return cmi_poisson5pt_csr_f32(m, n, 0, m * n, Ap, Aj, Ax, nullptr); }
-inline int build_dia(int64_t m, int64_t n, int64_t pitch, int *off, double *v) { return cmi_poisson5pt_dia_f64(m, n, pitch, off, v, nullptr); }
-inline int build_dia(int64_t m, int64_t n, int64_t pitch, int *off, float *v) { return cmi_poisson5pt_dia_f32(m, n, pitch, off, v, nullptr); }
-
 template <typename V> void poisson5pt_device_csr(csr_matrix<int, V, device_memory> &A, size_t m, size_t n)
 {
     const size_t N = m * n, nnz = static_cast<size_t>(cmi_poisson5pt_num_entries(m, n));
     A.resize(N, N, nnz);
-    cusp::detail::check(build_csr(m, n, A.row_offsets.data(), A.column_indices.data(), A.values.data()));
+    cusp::detail::check(cusp::detail::by_type<V>(cmi_poisson5pt_csr_f64, cmi_poisson5pt_csr_f32)(m, n, 0, N, A.row_offsets.data(), A.column_indices.data(),
+                                                                                                 A.values.data(), nullptr)); // rows [0, N): all of them
     cusp::detail::check(cmi_stream_synchronize(nullptr));
 }
 
@@ -60,7 +56,7 @@ template <typename V> void poisson5pt_impl(dia_matrix<int, V, device_memory> &A,
 {
     const size_t N = m * n;
     A.resize(N, N, static_cast<size_t>(cmi_poisson5pt_num_entries(m, n)), 5, 1);
-    cusp::detail::check(build_dia(m, n, A.values.pitch, A.diagonal_offsets.data(), A.values.values.data()));
+    cusp::detail::check(cusp::detail::by_type<V>(cmi_poisson5pt_dia_f64, cmi_poisson5pt_dia_f32)(m, n, A.values.pitch, A.diagonal_offsets.data(), A.values.values.data(), nullptr));
     cusp::detail::check(cmi_stream_synchronize(nullptr));
 }
 template <typename Matrix> void poisson5pt_impl(Matrix &A, size_t m, size_t n, device_memory)

@@ -71,39 +71,28 @@ template <typename T> struct bicgstab_shifts<T, cusp::host_memory> {
     }
 };
 
-inline int bicg_m_s_(size_t n, double a, double c, const double *r1, const double *As, double *s0) { return cmi_bicgstab_m_s_f64(n, a, c, r1, As, s0, nullptr); }
-inline int bicg_m_s_(size_t n, float a, float c, const float *r1, const float *As, float *s0) { return cmi_bicgstab_m_s_f32(n, a, c, r1, As, s0, nullptr); }
-inline int bicg_m_coefficients_(size_t ns, double bm1, double b0, double ao, double an, double c, const double *sg, const double *zm1, const double *z0, const double *rho0,
-                                double *z1, double *bs, double *cs, double *rho1, double *as)
-{ return cmi_bicgstab_m_coefficients_f64(ns, bm1, b0, ao, an, c, sg, zm1, z0, rho0, z1, bs, cs, rho1, as, nullptr); }
-inline int bicg_m_coefficients_(size_t ns, float bm1, float b0, float ao, float an, float c, const float *sg, const float *zm1, const float *z0, const float *rho0,
-                                float *z1, float *bs, float *cs, float *rho1, float *as)
-{ return cmi_bicgstab_m_coefficients_f32(ns, bm1, b0, ao, an, c, sg, zm1, z0, rho0, z1, bs, cs, rho1, as, nullptr); }
-inline int bicg_m_update_xs_(size_t n, size_t ns, const double *bs, const double *cs, double *rho0, double *zm1, double *z0, const double *as, const double *rho1,
-                             const double *z1, const double *r0, const double *r1, const double *w1, double *x, double *ss)
-{ return cmi_bicgstab_m_update_xs_f64(n, ns, n, bs, cs, rho0, zm1, z0, as, rho1, z1, r0, r1, w1, x, ss, nullptr); }
-inline int bicg_m_update_xs_(size_t n, size_t ns, const float *bs, const float *cs, float *rho0, float *zm1, float *z0, const float *as, const float *rho1,
-                             const float *z1, const float *r0, const float *r1, const float *w1, float *x, float *ss)
-{ return cmi_bicgstab_m_update_xs_f32(n, ns, n, bs, cs, rho0, zm1, z0, as, rho1, z1, r0, r1, w1, x, ss, nullptr); }
-
 template <typename T> struct bicgstab_shifts<T, cusp::device_memory> {
-    static_assert(std::is_same<T, double>::value || std::is_same<T, float>::value, "device_memory bicgstab_m is implemented for float and double");
+    static_assert(cusp::detail::is_real<T>::value, "device_memory bicgstab_m is implemented for float and double");
     typedef cusp::array1d<T, cusp::device_memory> Vec;
     Vec sig, z_m1, z_0, z_1, alpha_s, beta_s, rho_0, rho_1, chi_s;
     template <typename S> explicit bicgstab_shifts(const S &sigma)
         : sig(sigma), z_m1(sigma.size(), T(1)), z_0(sigma.size(), T(1)), z_1(sigma.size()), alpha_s(sigma.size(), T(0)), beta_s(sigma.size()),
           rho_0(sigma.size(), T(1)), rho_1(sigma.size()), chi_s(sigma.size())
     {}
-    static void s(size_t N, T alpha_1, T chi_0, const T *r_1, const T *As, T *s_0) { cusp::detail::check(bicg_m_s_(N, alpha_1, chi_0, r_1, As, s_0)); }
+    static void s(size_t N, T alpha_1, T chi_0, const T *r_1, const T *As, T *s_0) { cusp::detail::check(by_type<T>(cmi_bicgstab_m_s_f64, cmi_bicgstab_m_s_f32)(
+        N, alpha_1, chi_0, r_1, As, s_0, nullptr)); }
     void coefficients(T beta_m1, T beta_0, T alpha_old, T alpha_new, T chi_0)
     {
-        cusp::detail::check(bicg_m_coefficients_(sig.size(), beta_m1, beta_0, alpha_old, alpha_new, chi_0, sig.data(), z_m1.data(), z_0.data(), rho_0.data(), z_1.data(),
-                                                 beta_s.data(), chi_s.data(), rho_1.data(), alpha_s.data()));
+        cusp::detail::check(by_type<T>(cmi_bicgstab_m_coefficients_f64, cmi_bicgstab_m_coefficients_f32)(
+            sig.size(), beta_m1, beta_0, alpha_old, alpha_new, chi_0, sig.data(), z_m1.data(), z_0.data(), rho_0.data(), z_1.data(),
+                                                                                                         beta_s.data(), chi_s.data(), rho_1.data(), alpha_s.data(), nullptr));
     }
     void update_xs(size_t N, const T *r_0, const T *r_1, const T *w_1, T *x, T *ss)
     {
-        cusp::detail::check(bicg_m_update_xs_(N, sig.size(), beta_s.data(), chi_s.data(), rho_0.data(), z_m1.data(), z_0.data(), alpha_s.data(), rho_1.data(),
-                                              z_1.data(), r_0, r_1, w_1, x, ss)); // (the rotation rides behind it)
+        cusp::detail::check(by_type<T>(cmi_bicgstab_m_update_xs_f64, cmi_bicgstab_m_update_xs_f32)(N, sig.size(), N, beta_s.data(), chi_s.data(), rho_0.data(),
+                                                                                                   z_m1.data(), z_0.data(),
+                                                                                                   alpha_s.data(), rho_1.data(), z_1.data(), r_0, r_1, w_1, x, ss,
+                                                                                                   nullptr)); // (the shifts lie N apart; the rotation rides behind it)
     }
 };
 

@@ -48,17 +48,8 @@ template <typename T> void replicate(const T *b, T *dest, size_t N, size_t N_s, 
 }
 template <typename T> void replicate(const T *b, T *dest, size_t N, size_t N_s, cusp::device_memory)
 {
-    for (size_t s = 0; s < N_s; s++) cusp::detail::check(cusp::blas::detail::c_copy(static_cast<int64_t>(N), b, dest + s * N));
+    for (size_t s = 0; s < N_s; s++) cusp::detail::check(by_type<T>(cmi_blas_copy_f64, cmi_blas_copy_f32)(N, b, dest + s * N, nullptr));
 }
-
-inline int update_xp_(size_t n, size_t ns, const double *state, const double *bs, const double *as, const double *z, const double *r, double *p0, double *x, double *ps)
-{ return cmi_cg_m_update_xp_f64(n, ns, n, state, bs, as, z, r, p0, x, ps, nullptr); }
-inline int update_xp_(size_t n, size_t ns, const float *state, const float *bs, const float *as, const float *z, const float *r, float *p0, float *x, float *ps)
-{ return cmi_cg_m_update_xp_f32(n, ns, n, state, bs, as, z, r, p0, x, ps, nullptr); }
-inline int coefficients_(size_t ns, const double *ro, const double *pAp, const double *rn, double *state, const double *sg, double *zm1, double *z0, double *bs, double *as)
-{ return cmi_cg_m_coefficients_f64(ns, ro, pAp, rn, state, sg, zm1, z0, bs, as, nullptr); }
-inline int coefficients_(size_t ns, const double *ro, const double *pAp, const double *rn, float *state, const float *sg, float *zm1, float *z0, float *bs, float *as)
-{ return cmi_cg_m_coefficients_f32(ns, ro, pAp, rn, state, sg, zm1, z0, bs, as, nullptr); }
 
 // KERNEL_XP: x_s <- x_s - beta_s p_s (the old p_s), p_s <- zeta_s r + alpha_s p_s
 template <typename T>
@@ -74,10 +65,11 @@ void xp(const std::vector<T> &alpha_s, const std::vector<T> &z_1, const std::vec
 template <typename T>
 void xp(const std::vector<T> &alpha_s, const std::vector<T> &z_1, const std::vector<T> &beta_s, const T *r, T *x, T *ps, size_t N, cusp::device_memory)
 {
-    static_assert(std::is_same<T, double>::value || std::is_same<T, float>::value, "device_memory cg_m is implemented for float and double");
+    static_assert(cusp::detail::is_real<T>::value, "device_memory cg_m is implemented for float and double");
     if (alpha_s.empty()) return;
     const cusp::array1d<T, cusp::device_memory> a(alpha_s), z(z_1), b(beta_s); // N_s values each
-    cusp::detail::check(update_xp_(N, alpha_s.size(), static_cast<const T *>(nullptr), b.data(), a.data(), z.data(), r, static_cast<T *>(nullptr), x, ps));
+    cusp::detail::check(by_type<T>(cmi_cg_m_update_xp_f64, cmi_cg_m_update_xp_f32)(N, alpha_s.size(), N, nullptr, b.data(), a.data(), z.data(), r, nullptr, x, ps,
+                                                                                   nullptr)); // (no state, no p_0: the shifted part only)
 }
 
 template <typename A, typename X, typename B, typename S> void check_sizes(const A &a, const X &x, const B &b, const S &sigma, const char *who)
@@ -148,39 +140,24 @@ void cg_m_fused_device(const LinearOperator &A, VectorType1 &x, const VectorType
     cusp::blas::copy(b, p0);
     multishift::replicate(b.data(), ps.data(), N, N_s, cusp::device_memory());
     cusp::blas::fill(x, T(0));
-    cusp::detail::check(dotd_(N, r.data(), r.data(), rr[0], w.ws));
+    cusp::detail::check(by_type<T>(cmi_blas_dot_f64, cmi_blas_dotd_f32)(N, r.data(), r.data(), rr[0], w.ws, nullptr));
     rr_host.fetch(rr[0]);
     int cur = 0;
     for (;;) {
-        multiply_dot_any(A, p0, y, yp, w.ws, std::is_same<T, double>()); // the multiply, speculative: y <- A p0, *yp <- <y, p0>
+        multiply_dot(A, p0, y, p0, yp, w.ws); // the multiply, speculative: y <- A p0, *yp <- <y, p0>
         if (monitor.finished_norm(static_cast<typename Monitor::Real>(std::sqrt(rr_host.wait())))) break; // the one host read
-        cusp::detail::check(cg_update_(N, rr[cur], yp, y.data(), r.data(), rr[cur ^ 1], rr_host.host, w.ws)); // r <- r + beta_0 y, <r,r>
+        cusp::detail::check(by_type<T>(cmi_cg_update_f64, cmi_cg_update_f32)(N, rr[cur], yp, nullptr, y.data(), nullptr, r.data(), rr[cur ^ 1], rr_host.host, w.ws,
+                                                                             nullptr)); // r <- r + beta_0 y, <r,r>
         rr_host.record();
-        cusp::detail::check(multishift::coefficients_(N_s, rr[cur], yp, rr[cur ^ 1], state.data(), sig.data(), zm1.data(), z0.data(), beta_s.data(), alpha_s.data()));
-        cusp::detail::check(multishift::update_xp_(N, N_s, state.data(), beta_s.data(), alpha_s.data(), z0.data(), r.data(), p0.data(), x.data(), ps.data()));
+        cusp::detail::check(by_type<T>(cmi_cg_m_coefficients_f64, cmi_cg_m_coefficients_f32)(N_s, rr[cur], yp, rr[cur ^ 1], state.data(), sig.data(), zm1.data(),
+                                                                                             z0.data(), beta_s.data(), alpha_s.data(), nullptr));
+        cusp::detail::check(by_type<T>(cmi_cg_m_update_xp_f64, cmi_cg_m_update_xp_f32)(N, N_s, N, state.data(), beta_s.data(), alpha_s.data(), z0.data(), r.data(),
+                                                                                       p0.data(), x.data(), ps.data(),
+                                                                                       nullptr)); // (the shifts lie N apart)
         cur ^= 1;
         ++monitor;
     }
     cusp::detail::check(cmi_device_synchronize()); // the discarded multiply must not outlive y
-}
-
-template <typename A, typename X, typename B, typename Mon> struct use_fused_cg_m {
-    typedef typename A::value_type T;
-    static const bool value = std::is_same<typename A::memory_space, cusp::device_memory>::value &&
-                              (std::is_same<T, double>::value || std::is_same<T, float>::value) && std::is_same<typename X::value_type, T>::value &&
-                              std::is_same<typename B::value_type, T>::value && decltype(has_finished_norm(static_cast<Mon *>(nullptr)))::value;
-};
-template <typename LinearOperator, typename VectorType1, typename VectorType2, typename VectorType3, typename Monitor>
-void cg_m_select(const LinearOperator &A, VectorType1 &x, const VectorType2 &b, const VectorType3 &sigma, Monitor &monitor, std::true_type)
-{
-    const char *e = std::getenv("CMI_CG_M_FUSED");
-    if (e && e[0] == '0') { cg_m_plain(A, x, b, sigma, monitor); return; } // (measurements: the operation-by-operation path)
-    cg_m_fused_device(A, x, b, sigma, monitor);
-}
-template <typename LinearOperator, typename VectorType1, typename VectorType2, typename VectorType3, typename Monitor>
-void cg_m_select(const LinearOperator &A, VectorType1 &x, const VectorType2 &b, const VectorType3 &sigma, Monitor &monitor, std::false_type)
-{
-    cg_m_plain(A, x, b, sigma, monitor);
 }
 
 } // namespace detail
@@ -190,8 +167,14 @@ template <typename LinearOperator, typename VectorType1, typename VectorType2, t
 void cg_m(const LinearOperator &A, VectorType1 &x, const VectorType2 &b, const VectorType3 &sigma, Monitor &monitor)
 {
     detail::multishift::check_sizes(A, x, b, sigma, "cg_m");
-    detail::cg_m_select(A, x, b, sigma, monitor,
-                        std::integral_constant<bool, detail::use_fused_cg_m<LinearOperator, VectorType1, VectorType2, Monitor>::value>());
+    if constexpr (detail::fused_eligible<LinearOperator, VectorType1, Monitor>::value &&
+                  std::is_same<typename VectorType2::value_type, typename LinearOperator::value_type>::value) {
+        const char *e = std::getenv("CMI_CG_M_FUSED");
+        if (e && e[0] == '0') detail::cg_m_plain(A, x, b, sigma, monitor); // (measurements: the operation-by-operation path)
+        else detail::cg_m_fused_device(A, x, b, sigma, monitor);
+    } else {
+        detail::cg_m_plain(A, x, b, sigma, monitor);
+    }
 }
 
 template <typename LinearOperator, typename VectorType1, typename VectorType2, typename VectorType3, typename = detail::not_policy<LinearOperator>>

@@ -45,8 +45,6 @@ template <typename Vec, typename ValueType, typename Space> void orthogonalize(c
     }
     hcol[i + 1] = cusp::blas::nrm2(w);
 }
-inline int axpy_dot_(size_t n, const double *h, const double *v, double *w, const double *u, double *out, void *ws) { return cmi_blas_axpy_dot_f64(n, h, v, w, u, out, ws, nullptr); }
-inline int axpy_dot_(size_t n, const double *h, const float *v, float *w, const float *u, double *out, void *ws) { return cmi_blas_axpy_dot_f32(n, h, v, w, u, out, ws, nullptr); }
 template <typename ValueType> struct mgs_on_device : std::integral_constant<bool, std::is_same<ValueType, double>::value || std::is_same<ValueType, float>::value> {};
 template <typename Vec, typename ValueType>
 typename std::enable_if<mgs_on_device<ValueType>::value>::type orthogonalize(const std::vector<Vec> &V, int i, Vec &w, ValueType *hcol, cusp::device_memory)
@@ -56,9 +54,12 @@ typename std::enable_if<mgs_on_device<ValueType>::value>::type orthogonalize(con
     cusp::blas::detail::device_workspace &ws = cusp::blas::detail::workspace();
     const size_t n = w.size();
     double *c = coeff.data();
-    cusp::detail::check(axpy_dot_(n, nullptr, w.data(), w.data(), V[0].data(), c, ws.ws));                                   // <V[0], w>
-    for (int k = 0; k < i; k++) cusp::detail::check(axpy_dot_(n, c + k, V[k].data(), w.data(), V[k + 1].data(), c + k + 1, ws.ws)); // w -= h_k V[k]; <V[k+1], w>
-    cusp::detail::check(axpy_dot_(n, c + i, V[i].data(), w.data(), w.data(), c + i + 1, ws.ws));                             // w -= h_i V[i]; <w, w>
+    cusp::detail::check(by_type<ValueType>(cmi_blas_axpy_dot_f64, cmi_blas_axpy_dot_f32)(n, nullptr, w.data(), w.data(), V[0].data(), c, ws.ws,
+                                                                                         nullptr)); // <V[0], w>
+    for (int k = 0; k < i; k++) cusp::detail::check(by_type<ValueType>(cmi_blas_axpy_dot_f64, cmi_blas_axpy_dot_f32)(
+        n, c + k, V[k].data(), w.data(), V[k + 1].data(), c + k + 1, ws.ws, nullptr)); // w -= h_k V[k]; <V[k+1], w>
+    cusp::detail::check(by_type<ValueType>(cmi_blas_axpy_dot_f64, cmi_blas_axpy_dot_f32)(n, c + i, V[i].data(), w.data(), w.data(), c + i + 1, ws.ws,
+                                                                                         nullptr)); // w -= h_i V[i]; <w, w>
     std::vector<double> host(static_cast<size_t>(i + 2));
     cusp::detail::check(cmi_memcpy_d2h(host.data(), c, host.size() * sizeof(double), nullptr));
     for (int k = 0; k <= i; k++) hcol[k] = static_cast<ValueType>(host[k]);

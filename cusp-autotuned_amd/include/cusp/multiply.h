@@ -154,43 +154,6 @@ template <typename V> struct device_functors<V, identity_function<V>, multiplies
 // explicit launch configuration for cusp::ktt::tune (thread-local; nullptr = tuning table)
 inline const cmi_config *&forced_config() { static thread_local const cmi_config *c = nullptr; return c; }
 
-inline int spmv_csr(int64_t r, int64_t c, int64_t n, const int *Ap, const int *Aj, const double *Ax, const double *x, double *y, int acc, void *s)
-{ return cmi_spmv_csr_f64(r, c, n, Ap, Aj, Ax, x, y, acc, forced_config(), s); }
-inline int spmv_csr(int64_t r, int64_t c, int64_t n, const int *Ap, const int *Aj, const float *Ax, const float *x, float *y, int acc, void *s)
-{ return cmi_spmv_csr_f32(r, c, n, Ap, Aj, Ax, x, y, acc, forced_config(), s); }
-inline int spmv_coo(int64_t r, int64_t c, int64_t n, const int *Ai, const int *Aj, const double *Ax, const double *x, double *y, int acc, void *s)
-{ return cmi_spmv_coo_f64(r, c, n, Ai, Aj, Ax, x, y, acc, forced_config(), s); }
-inline int spmv_coo(int64_t r, int64_t c, int64_t n, const int *Ai, const int *Aj, const float *Ax, const float *x, float *y, int acc, void *s)
-{ return cmi_spmv_coo_f32(r, c, n, Ai, Aj, Ax, x, y, acc, forced_config(), s); }
-inline int spmv_ell(int64_t r, int64_t c, int64_t w, int64_t p, const int *Aj, const double *Ax, const int *rl, const double *x, double *y, int acc, void *s)
-{ return cmi_spmv_ell_f64(r, c, w, p, Aj, Ax, rl, x, y, acc, forced_config(), s); }
-inline int spmv_ell(int64_t r, int64_t c, int64_t w, int64_t p, const int *Aj, const float *Ax, const int *rl, const float *x, float *y, int acc, void *s)
-{ return cmi_spmv_ell_f32(r, c, w, p, Aj, Ax, rl, x, y, acc, forced_config(), s); }
-inline int spmv_dia(int64_t r, int64_t c, int64_t d, int64_t p, const int *off, const double *v, const double *x, double *y, int acc, void *s)
-{ return cmi_spmv_dia_f64(r, c, d, p, off, v, x, y, acc, forced_config(), s); }
-inline int spmv_dia(int64_t r, int64_t c, int64_t d, int64_t p, const int *off, const float *v, const float *x, float *y, int acc, void *s)
-{ return cmi_spmv_dia_f32(r, c, d, p, off, v, x, y, acc, forced_config(), s); }
-inline int spmv_hyb(int64_t r, int64_t c, int64_t w, int64_t p, const int *eAj, const double *eAx, int64_t n, const int *cAi, const int *cAj,
-                    const double *cAx, const double *x, double *y, int acc, void *s)
-{ return cmi_spmv_hyb_f64(r, c, w, p, eAj, eAx, n, cAi, cAj, cAx, x, y, acc, nullptr, nullptr, s); }
-inline int spmv_hyb(int64_t r, int64_t c, int64_t w, int64_t p, const int *eAj, const float *eAx, int64_t n, const int *cAi, const int *cAj,
-                    const float *cAx, const float *x, float *y, int acc, void *s)
-{ return cmi_spmv_hyb_f32(r, c, w, p, eAj, eAx, n, cAi, cAj, cAx, x, y, acc, nullptr, nullptr, s); }
-
-inline int spmv_csr_plan(const cmi_plan *p, const int *Ap, const int *Aj, const double *Ax, const double *x, double *y, int acc, void *s)
-{ return cmi_spmv_csr_plan_f64(p, Ap, Aj, Ax, x, y, acc, s); }
-inline int spmv_csr_plan(const cmi_plan *p, const int *Ap, const int *Aj, const float *Ax, const float *x, float *y, int acc, void *s)
-{ return cmi_spmv_csr_plan_f32(p, Ap, Aj, Ax, x, y, acc, s); }
-inline int spmv_coo_plan(const cmi_plan *p, const int *Ai, const int *Aj, const double *Ax, const double *x, double *y, int acc, void *s)
-{ return cmi_spmv_coo_plan_f64(p, Ai, Aj, Ax, x, y, acc, s); }
-inline int spmv_coo_plan(const cmi_plan *p, const int *Ai, const int *Aj, const float *Ax, const float *x, float *y, int acc, void *s)
-{ return cmi_spmv_coo_plan_f32(p, Ai, Aj, Ax, x, y, acc, s); }
-
-inline int spmv_hyb_plan(const cmi_plan *p, size_t pitch, const int *eAj, const double *eAx, const int *Ai, const int *Aj, const double *Ax, const double *x, double *y, int acc, void *s)
-{ return cmi_spmv_hyb_plan_f64(p, (int64_t)pitch, eAj, eAx, Ai, Aj, Ax, x, y, acc, s); }
-inline int spmv_hyb_plan(const cmi_plan *p, size_t pitch, const int *eAj, const float *eAx, const int *Ai, const int *Aj, const float *Ax, const float *x, float *y, int acc, void *s)
-{ return cmi_spmv_hyb_plan_f32(p, (int64_t)pitch, eAj, eAx, Ai, Aj, Ax, x, y, acc, s); }
-
 // the container's plan (views, and anything while cusp::ktt::tune forces a configuration: none)
 template <typename A> auto plan_of(const A &a, void *stream, int) -> decltype(a.plan(stream))
 {
@@ -210,45 +173,54 @@ template <typename A> const int *row_lengths_of(const A &, long) { return nullpt
 template <typename A, typename X, typename Y> void device_multiply(const A &a, const X &x, Y &y, int acc, void *stream, csr_format)
 {
     require_int_index<A>();
+    typedef typename A::value_type V;
     if (const cmi_plan *p = plan_of(a, stream, 0)) {
-        check(spmv_csr_plan(p, a.row_offsets.data(), a.column_indices.data(), a.values.data(), x.data(), y.data(), acc, stream));
+        check(by_type<V>(cmi_spmv_csr_plan_f64, cmi_spmv_csr_plan_f32)(p, a.row_offsets.data(), a.column_indices.data(), a.values.data(), x.data(), y.data(), acc, stream));
         return;
     }
-    check(spmv_csr(a.num_rows, a.num_cols, a.num_entries, a.row_offsets.data(), a.column_indices.data(), a.values.data(), x.data(), y.data(), acc, stream));
+    check(by_type<V>(cmi_spmv_csr_f64, cmi_spmv_csr_f32)(a.num_rows, a.num_cols, a.num_entries, a.row_offsets.data(), a.column_indices.data(), a.values.data(), x.data(),
+                                                         y.data(), acc, forced_config(), stream));
 }
 template <typename A, typename X, typename Y> void device_multiply(const A &a, const X &x, Y &y, int acc, void *stream, coo_format)
 {
     require_int_index<A>();
+    typedef typename A::value_type V;
     if (const cmi_plan *p = plan_of(a, stream, 0)) {
-        check(spmv_coo_plan(p, a.row_indices.data(), a.column_indices.data(), a.values.data(), x.data(), y.data(), acc, stream));
+        check(by_type<V>(cmi_spmv_coo_plan_f64, cmi_spmv_coo_plan_f32)(p, a.row_indices.data(), a.column_indices.data(), a.values.data(), x.data(), y.data(), acc, stream));
         return;
     }
-    check(spmv_coo(a.num_rows, a.num_cols, a.num_entries, a.row_indices.data(), a.column_indices.data(), a.values.data(), x.data(), y.data(), acc, stream));
+    check(by_type<V>(cmi_spmv_coo_f64, cmi_spmv_coo_f32)(a.num_rows, a.num_cols, a.num_entries, a.row_indices.data(), a.column_indices.data(), a.values.data(), x.data(),
+                                                         y.data(), acc, forced_config(), stream));
 }
 template <typename A, typename X, typename Y> void device_multiply(const A &a, const X &x, Y &y, int acc, void *stream, ell_format)
 {
     require_int_index<A>();
     // reference ell_spmv.h:138 asserts equal pitches; here it is an error the caller sees
     if (a.column_indices.pitch != a.values.pitch) throw cusp::invalid_input_exception("ell_matrix: column_indices.pitch != values.pitch");
-    check(spmv_ell(a.num_rows, a.num_cols, a.column_indices.num_cols, a.column_indices.pitch, data_of(a.column_indices), data_of(a.values),
-                   row_lengths_of(a, 0), x.data(), y.data(), acc, stream));
+    check(by_type<typename A::value_type>(cmi_spmv_ell_f64, cmi_spmv_ell_f32)(a.num_rows, a.num_cols, a.column_indices.num_cols, a.column_indices.pitch, data_of(a.column_indices),
+                                                                              data_of(a.values), row_lengths_of(a, 0), x.data(), y.data(), acc, forced_config(), stream));
 }
 template <typename A, typename X, typename Y> void device_multiply(const A &a, const X &x, Y &y, int acc, void *stream, dia_format)
 {
     require_int_index<A>();
-    check(spmv_dia(a.num_rows, a.num_cols, a.values.num_cols, a.values.pitch, a.diagonal_offsets.data(), data_of(a.values), x.data(), y.data(), acc, stream));
+    check(by_type<typename A::value_type>(cmi_spmv_dia_f64, cmi_spmv_dia_f32)(a.num_rows, a.num_cols, a.values.num_cols, a.values.pitch, a.diagonal_offsets.data(),
+                                                                              data_of(a.values),
+                                                                              x.data(), y.data(), acc, forced_config(), stream));
 }
 template <typename A, typename X, typename Y> void device_multiply(const A &a, const X &x, Y &y, int acc, void *stream, hyb_format)
 {
     require_int_index<A>();
+    typedef typename A::value_type V;
     if (a.ell.column_indices.pitch != a.ell.values.pitch) throw cusp::invalid_input_exception("hyb_matrix: ell.column_indices.pitch != ell.values.pitch");
     if (const cmi_plan *p = plan_of(a, stream, 0)) { // COO part sorted by row (every conversion's output): one launch, y written once
-        check(spmv_hyb_plan(p, a.ell.column_indices.pitch, data_of(a.ell.column_indices), data_of(a.ell.values), a.coo.row_indices.data(),
-                            a.coo.column_indices.data(), a.coo.values.data(), x.data(), y.data(), acc, stream));
+        check(by_type<V>(cmi_spmv_hyb_plan_f64, cmi_spmv_hyb_plan_f32)(p, a.ell.column_indices.pitch, data_of(a.ell.column_indices), data_of(a.ell.values),
+                                                                       a.coo.row_indices.data(),
+                                                                       a.coo.column_indices.data(), a.coo.values.data(), x.data(), y.data(), acc, stream));
         return;
     }
-    check(spmv_hyb(a.num_rows, a.num_cols, a.ell.column_indices.num_cols, a.ell.column_indices.pitch, data_of(a.ell.column_indices), data_of(a.ell.values),
-                   a.coo.num_entries, a.coo.row_indices.data(), a.coo.column_indices.data(), a.coo.values.data(), x.data(), y.data(), acc, stream));
+    check(by_type<V>(cmi_spmv_hyb_f64, cmi_spmv_hyb_f32)(a.num_rows, a.num_cols, a.ell.column_indices.num_cols, a.ell.column_indices.pitch, data_of(a.ell.column_indices),
+                                                         data_of(a.ell.values), a.coo.num_entries, a.coo.row_indices.data(), a.coo.column_indices.data(), a.coo.values.data(),
+                                                         x.data(), y.data(), acc, nullptr, nullptr, stream)); // (no configuration for either part: the tuning table's)
 }
 
 // host adaptor: containers expose operator[] / data; give ELL/DIA a data_ptr() view for the loops
@@ -352,13 +324,6 @@ void host_block_multiply(const A &a, const X &x, Y &y, Init initialize, Comb com
     (void)parallel;
 }
 
-inline int spmm_csr(int64_t r, int64_t c, int64_t n, const int *Ap, const int *Aj, const double *Ax, int64_t k, const double *X, int64_t xrs, int64_t xcs,
-                    double *Y, int64_t yrs, int64_t ycs, int acc, void *s)
-{ return cmi_spmm_csr_f64(r, c, n, Ap, Aj, Ax, k, X, xrs, xcs, Y, yrs, ycs, acc, forced_config(), s); }
-inline int spmm_csr(int64_t r, int64_t c, int64_t n, const int *Ap, const int *Aj, const float *Ax, int64_t k, const float *X, int64_t xrs, int64_t xcs,
-                    float *Y, int64_t yrs, int64_t ycs, int acc, void *s)
-{ return cmi_spmm_csr_f32(r, c, n, Ap, Aj, Ax, k, X, xrs, xcs, Y, yrs, ycs, acc, forced_config(), s); }
-
 // a contiguous device column as the vector device_multiply takes
 template <typename T> struct column_ref {
     T *p;
@@ -378,8 +343,8 @@ template <typename A, typename X, typename Y> void device_block_multiply(const A
         device_multiply(a, xc, yc, acc, stream, csr_format());
         return;
     }
-    check(spmm_csr(a.num_rows, a.num_cols, a.num_entries, a.row_offsets.data(), a.column_indices.data(), a.values.data(), (int64_t)x.num_cols,
-                   data_of(x), xrs, xcs, const_cast<V *>(data_of(y)), yrs, ycs, acc, stream));
+    check(by_type<V>(cmi_spmm_csr_f64, cmi_spmm_csr_f32)(a.num_rows, a.num_cols, a.num_entries, a.row_offsets.data(), a.column_indices.data(), a.values.data(), (int64_t)x.num_cols,
+                                                         data_of(x), xrs, xcs, const_cast<V *>(data_of(y)), yrs, ycs, acc, forced_config(), stream));
 }
 
 // ---- sparse x sparse: C = A B with three sparse matrices (SpGEMM) ---------------------------------------------
@@ -455,15 +420,6 @@ void host_spgemm(const A &a, const B &b, C &c, Comb combine, Red reduce, coo_for
     cusp::convert(cc, c);
 }
 
-inline int spgemm_csr(int64_t m, int64_t k, int64_t n, int64_t na, const int *Ap, const int *Aj, const double *Ax, int64_t nb, const int *Bp, const int *Bj,
-                      const double *Bx, cmi_spgemm **r, void *s)
-{ return cmi_spgemm_csr_f64(m, k, n, na, Ap, Aj, Ax, nb, Bp, Bj, Bx, r, s); }
-inline int spgemm_csr(int64_t m, int64_t k, int64_t n, int64_t na, const int *Ap, const int *Aj, const float *Ax, int64_t nb, const int *Bp, const int *Bj,
-                      const float *Bx, cmi_spgemm **r, void *s)
-{ return cmi_spgemm_csr_f32(m, k, n, na, Ap, Aj, Ax, nb, Bp, Bj, Bx, r, s); }
-inline int spgemm_take(cmi_spgemm *r, int *Cp, int *Cj, double *Cx, int64_t cap, void *s) { return cmi_spgemm_take_f64(r, Cp, Cj, Cx, cap, s); }
-inline int spgemm_take(cmi_spgemm *r, int *Cp, int *Cj, float *Cx, int64_t cap, void *s) { return cmi_spgemm_take_f32(r, Cp, Cj, Cx, cap, s); }
-
 template <typename A, typename B, typename C> void device_spgemm(const A &a, const B &b, C &c, void *stream, csr_format)
 {
     require_int_index<A>();
@@ -475,12 +431,14 @@ template <typename A, typename B, typename C> void device_spgemm(const A &a, con
         cmi_spgemm *p = nullptr;
         ~handle() { cmi_spgemm_destroy(p); }
     } h;
-    check(spgemm_csr((int64_t)a.num_rows, (int64_t)a.num_cols, (int64_t)b.num_cols, (int64_t)a.num_entries, a.row_offsets.data(), a.column_indices.data(),
-                     a.values.data(), (int64_t)b.num_entries, b.row_offsets.data(), b.column_indices.data(), b.values.data(), &h.p, stream));
+    typedef typename A::value_type V;
+    check(by_type<V>(cmi_spgemm_csr_f64, cmi_spgemm_csr_f32)((int64_t)a.num_rows, (int64_t)a.num_cols, (int64_t)b.num_cols, (int64_t)a.num_entries, a.row_offsets.data(),
+                                                             a.column_indices.data(),
+                                                             a.values.data(), (int64_t)b.num_entries, b.row_offsets.data(), b.column_indices.data(), b.values.data(), &h.p, stream));
     int64_t entries = 0;
     check(cmi_spgemm_num_entries(h.p, &entries));
     c.resize(a.num_rows, b.num_cols, (size_t)entries); // (A and B have been read: C may be one of them)
-    check(spgemm_take(h.p, c.row_offsets.data(), c.column_indices.data(), c.values.data(), entries, stream));
+    check(by_type<V>(cmi_spgemm_take_f64, cmi_spgemm_take_f32)(h.p, c.row_offsets.data(), c.column_indices.data(), c.values.data(), entries, stream));
     check(cmi_stream_synchronize(stream)); // the copies read the handle's arrays
 }
 // COO on the device: the existing device conversions around the CSR product (stable sort by row + row offsets in, row indices out)

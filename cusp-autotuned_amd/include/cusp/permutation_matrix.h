@@ -26,13 +26,6 @@ struct permutation_format : known_format {};
 
 namespace detail {
 
-inline int map_gather(int64_t n, int64_t m, const int *map, const int *in, int *out) { return cmi_gather_i32(n, m, map, in, out, nullptr); }
-inline int map_gather(int64_t n, int64_t m, const int *map, const float *in, float *out) { return cmi_gather_f32(n, m, map, in, out, nullptr); }
-inline int map_gather(int64_t n, int64_t m, const int *map, const double *in, double *out) { return cmi_gather_f64(n, m, map, in, out, nullptr); }
-inline int map_scatter(int64_t n, int64_t m, const int *map, const int *in, int *out) { return cmi_scatter_i32(n, m, map, in, out, nullptr); }
-inline int map_scatter(int64_t n, int64_t m, const int *map, const float *in, float *out) { return cmi_scatter_f32(n, m, map, in, out, nullptr); }
-inline int map_scatter(int64_t n, int64_t m, const int *map, const double *in, double *out) { return cmi_scatter_f64(n, m, map, in, out, nullptr); }
-
 // out[i] = in[map[i]] (scatter: out[map[i]] = in[i]); `out` is sized by the caller and must not be `in`
 template <typename Map, typename In, typename Out> void map_copy(bool scatter, const Map &map, const In &in, Out &out, cusp::host_memory)
 {
@@ -49,7 +42,12 @@ template <typename Map, typename In, typename Out> void map_copy(bool scatter, c
     static_assert(sizeof(typename Map::value_type) == 4, "the device path takes 32-bit indices");
     static_assert(std::is_same<typename std::remove_const<typename In::value_type>::type, typename Out::value_type>::value, "the device path moves values of one type");
     const int64_t n = (int64_t)map.size(), m = (int64_t)(scatter ? out.size() : in.size());
-    cusp::detail::check(scatter ? map_scatter(n, m, map.data(), in.data(), out.data()) : map_gather(n, m, map.data(), in.data(), out.data()));
+    typedef typename Out::value_type T; // int (index arrays), float or double
+    using cusp::detail::by_type;
+    if constexpr (std::is_same<T, int>::value)
+        cusp::detail::check((scatter ? cmi_scatter_i32 : cmi_gather_i32)(n, m, map.data(), in.data(), out.data(), nullptr));
+    else
+        cusp::detail::check((scatter ? by_type<T>(cmi_scatter_f64, cmi_scatter_f32) : by_type<T>(cmi_gather_f64, cmi_gather_f32))(n, m, map.data(), in.data(), out.data(), nullptr));
 }
 
 } // namespace detail

@@ -26,11 +26,11 @@ template <typename M, typename D, typename V> void scale_rows(M &m, const D &d, 
             m.values[q] = quotient * lambda;
         }
 }
-inline int c_scale_rows(int64_t n, int64_t nnz, const int *Ap, const double *d, double l, double *x) { return cmi_csr_scale_rows_f64(n, nnz, Ap, x, d, l, x, nullptr); }
-inline int c_scale_rows(int64_t n, int64_t nnz, const int *Ap, const float *d, float l, float *x) { return cmi_csr_scale_rows_f32(n, nnz, Ap, x, d, l, x, nullptr); }
 template <typename M, typename D, typename V> void scale_rows(M &m, const D &d, V lambda, cusp::device_memory)
 {
-    cusp::detail::check(c_scale_rows((int64_t)m.num_rows, (int64_t)m.num_entries, m.row_offsets.data(), d.data(), lambda, m.values.data()));
+    cusp::detail::check(cusp::detail::by_type<typename M::value_type>(cmi_csr_scale_rows_f64, cmi_csr_scale_rows_f32)(
+        (int64_t)m.num_rows, (int64_t)m.num_entries, m.row_offsets.data(), m.values.data(), d.data(), lambda,
+                                                                                                                      m.values.data(), nullptr)); // in place: the values are input and output
 }
 
 } // namespace detail

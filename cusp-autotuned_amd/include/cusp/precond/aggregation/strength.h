@@ -47,17 +47,14 @@ template <typename A, typename S> void strength(const A &a, S &s, double theta, 
     }
 }
 
-inline int c_strength(int64_t n, int64_t nnz, const int *Ap, const int *Aj, const double *Ax, double theta, int *Sp, int *Sj, double *Sx)
-{ return cmi_csr_strength_symmetric_f64(n, n, nnz, Ap, Aj, Ax, theta, Sp, Sj, Sx, nnz, nullptr); }
-inline int c_strength(int64_t n, int64_t nnz, const int *Ap, const int *Aj, const float *Ax, double theta, int *Sp, int *Sj, float *Sx)
-{ return cmi_csr_strength_symmetric_f32(n, n, nnz, Ap, Aj, Ax, theta, Sp, Sj, Sx, nnz, nullptr); }
-
 template <typename A, typename S> void strength(const A &a, S &s, double theta, cusp::device_memory)
 {
     typedef typename S::value_type V;
     cusp::csr_matrix<int, V, cusp::device_memory> t(a.num_rows, a.num_cols, a.num_entries);
-    cusp::detail::check(c_strength((int64_t)a.num_rows, (int64_t)a.num_entries, a.row_offsets.data(), a.column_indices.data(), a.values.data(), theta,
-                                   t.row_offsets.data(), t.column_indices.data(), t.values.data()));
+    const int64_t n = (int64_t)a.num_rows, nnz = (int64_t)a.num_entries; // square: n rows and n columns; t holds up to nnz entries
+    cusp::detail::check(cusp::detail::by_type<V>(cmi_csr_strength_symmetric_f64, cmi_csr_strength_symmetric_f32)(
+        n, n, nnz, a.row_offsets.data(), a.column_indices.data(), a.values.data(), theta,
+                                                                                                                 t.row_offsets.data(), t.column_indices.data(), t.values.data(), nnz, nullptr));
     cusp::detail::take_compacted(t, s);
 }
 

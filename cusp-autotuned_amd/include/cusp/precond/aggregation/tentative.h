@@ -47,16 +47,15 @@ template <typename Agg, typename BA, typename Q, typename RA> void fit(const Agg
     q.row_offsets[n] = static_cast<I>(at);
 }
 
-inline int c_fit(int64_t n, int64_t na, const int *agg, const double *B, int *Tp, int *Tj, double *Tx, double *R) { return cmi_aggregates_fit_f64(n, na, agg, B, Tp, Tj, Tx, n, R, nullptr); }
-inline int c_fit(int64_t n, int64_t na, const int *agg, const float *B, int *Tp, int *Tj, float *Tx, float *R) { return cmi_aggregates_fit_f32(n, na, agg, B, Tp, Tj, Tx, n, R, nullptr); }
-
 template <typename Agg, typename BA, typename Q, typename RA> void fit(const Agg &agg, const BA &B, Q &q, RA &R, size_t na, cusp::device_memory)
 {
     typedef typename Q::value_type V;
     const size_t n = agg.size();
     cusp::csr_matrix<int, V, cusp::device_memory> t(n, na, n);
     R.resize(na);
-    cusp::detail::check(c_fit((int64_t)n, (int64_t)na, agg.data(), B.data(), t.row_offsets.data(), t.column_indices.data(), t.values.data(), R.data()));
+    cusp::detail::check(cusp::detail::by_type<V>(cmi_aggregates_fit_f64, cmi_aggregates_fit_f32)((int64_t)n, (int64_t)na, agg.data(), B.data(), t.row_offsets.data(),
+                                                                                                 t.column_indices.data(), t.values.data(),
+                                                                                                 (int64_t)n, R.data(), nullptr)); // (capacity of t: one entry per row)
     cusp::detail::take_compacted(t, q);
 }
 

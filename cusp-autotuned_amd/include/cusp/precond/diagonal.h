@@ -30,12 +30,11 @@ private:
                                   (std::is_same<ValueType, double>::value || std::is_same<ValueType, float>::value) &&
                                   !std::is_same<typename MatrixType::format, cusp::array2d_format>::value;
     };
-    static int diag_call(int64_t n, const int *Ap, const int *Aj, const double *Ax, double *d) { return cmi_csr_diagonal_f64(n, Ap, Aj, Ax, d, 1, nullptr); }
-    static int diag_call(int64_t n, const int *Ap, const int *Aj, const float *Ax, float *d) { return cmi_csr_diagonal_f32(n, Ap, Aj, Ax, d, 1, nullptr); }
-    template <typename T> static int diag_call(int64_t, const int *, const int *, const T *, T *) { return -1; }
     template <typename Csr> void from_device_csr(const Csr &C)
     {
-        cusp::detail::check(diag_call((int64_t)C.num_rows, C.row_offsets.data(), C.column_indices.data(), C.values.data(), diagonal_reciprocals.data()));
+        cusp::detail::check(cusp::detail::by_type<ValueType>(cmi_csr_diagonal_f64, cmi_csr_diagonal_f32)(
+            (int64_t)C.num_rows, C.row_offsets.data(), C.column_indices.data(), C.values.data(),
+                                                                                                         diagonal_reciprocals.data(), 1 /* reciprocals */, nullptr));
         cusp::detail::check(cmi_stream_synchronize(nullptr));
     }
     template <typename MatrixType> void build_device(const MatrixType &A, cusp::csr_format) { from_device_csr(A); }

@@ -11,11 +11,6 @@
 namespace cusp {
 namespace precond {
 
-namespace detail {
-inline int c_presmooth(int64_t n, const double *d, const double *b, double w, double *x) { return cmi_relax_jacobi_presmooth_f64(n, d, b, w, x, nullptr); }
-inline int c_presmooth(int64_t n, const float *d, const float *b, float w, float *x) { return cmi_relax_jacobi_presmooth_f32(n, d, b, w, x, nullptr); }
-} // namespace detail
-
 template <typename ValueType, typename MemorySpace> class jacobi_smoother {
 public:
     cusp::relaxation::jacobi<ValueType, MemorySpace> M;
@@ -48,7 +43,8 @@ private:
     }
     template <typename VectorType1, typename VectorType2> void presmooth_in(const VectorType1 &b, VectorType2 &x, cusp::device_memory)
     {
-        cusp::detail::check(detail::c_presmooth((int64_t)x.size(), M.diagonal.data(), b.data(), M.default_omega, x.data()));
+        cusp::detail::check(cusp::detail::by_type<ValueType>(cmi_relax_jacobi_presmooth_f64, cmi_relax_jacobi_presmooth_f32)(
+            (int64_t)x.size(), M.diagonal.data(), b.data(), M.default_omega, x.data(), nullptr));
     }
 };
 

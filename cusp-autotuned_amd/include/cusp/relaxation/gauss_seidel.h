@@ -31,15 +31,6 @@ namespace relaxation {
 
 typedef enum { FORWARD, BACKWARD, SYMMETRIC } sweep;
 
-namespace detail {
-inline int c_gs_colour(int64_t rows, int64_t nnz, const int *Ap, const int *Aj, const double *Ax, const double *b, double *x, const int *ord,
-                       int64_t s0, int64_t s1, double *scratch)
-{ return cmi_csr_gauss_seidel_colour_f64(rows, nnz, Ap, Aj, Ax, b, x, ord, s0, s1, scratch, nullptr); }
-inline int c_gs_colour(int64_t rows, int64_t nnz, const int *Ap, const int *Aj, const float *Ax, const float *b, float *x, const int *ord,
-                       int64_t s0, int64_t s1, float *scratch)
-{ return cmi_csr_gauss_seidel_colour_f32(rows, nnz, Ap, Aj, Ax, b, x, ord, s0, s1, scratch, nullptr); }
-} // namespace detail
-
 template <typename ValueType, typename MemorySpace> class gauss_seidel : public cusp::linear_operator<ValueType, MemorySpace> {
     typedef cusp::linear_operator<ValueType, MemorySpace> Parent;
 
@@ -148,8 +139,9 @@ private:
             if (scratch.size() < len) scratch.resize(len);
             park = scratch.data();
         }
-        cusp::detail::check(detail::c_gs_colour((int64_t)A.num_rows, (int64_t)A.num_entries, A.row_offsets.data(), A.column_indices.data(),
-                                                A.values.data(), b.data(), x.data(), ordering.data(), color_offsets[c], color_offsets[c + 1], park));
+        cusp::detail::check(cusp::detail::by_type<ValueType>(cmi_csr_gauss_seidel_colour_f64, cmi_csr_gauss_seidel_colour_f32)(
+            (int64_t)A.num_rows, (int64_t)A.num_entries, A.row_offsets.data(), A.column_indices.data(),
+                                                A.values.data(), b.data(), x.data(), ordering.data(), color_offsets[c], color_offsets[c + 1], park, nullptr));
     }
 };
 

@@ -20,14 +20,6 @@
 namespace cusp {
 namespace relaxation {
 
-namespace detail {
-inline int c_jacobi_update(int64_t n, const double *d, const double *b, const double *y, double w, double *x)
-{ return cmi_relax_jacobi_update_f64(n, d, b, y, w, x, nullptr); }
-inline int c_jacobi_update(int64_t n, const float *d, const float *b, const float *y, float w, float *x)
-{ return cmi_relax_jacobi_update_f32(n, d, b, y, w, x, nullptr); }
-
-} // namespace detail
-
 template <typename ValueType, typename MemorySpace> class jacobi : public cusp::linear_operator<ValueType, MemorySpace> {
     typedef cusp::linear_operator<ValueType, MemorySpace> Parent;
 
@@ -80,7 +72,8 @@ private:
                       "device_memory cusp::relaxation::jacobi is implemented for float and double");
         if (A.num_rows == 0) return;
         cusp::multiply(A, x, temp);
-        cusp::detail::check(detail::c_jacobi_update((int64_t)x.size(), diagonal.data(), b.data(), temp.data(), omega, x.data()));
+        cusp::detail::check(cusp::detail::by_type<ValueType>(cmi_relax_jacobi_update_f64, cmi_relax_jacobi_update_f32)(
+            (int64_t)x.size(), diagonal.data(), b.data(), temp.data(), omega, x.data(), nullptr));
     }
 };
 

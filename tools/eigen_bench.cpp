@@ -71,8 +71,9 @@ template <typename V> struct bench {
         cusp::detail::check(cmi_event_create(&e0));
         cusp::detail::check(cmi_event_create(&e1));
         auto once = [&] {
-            cusp::detail::check(cusp::eigen::detail::csr_sums(A.num_rows, A.row_offsets.data(), A.values.data(), sums.data(), 0));
-            cusp::detail::check(cusp::blas::detail::c_amax(sums.size(), sums.data(), static_cast<V *>(w.result), nullptr, w.ws));
+            cusp::detail::check(cusp::detail::by_type<V>(cmi_csr_abs_row_sums_f64, cmi_csr_abs_row_sums_f32)(
+                A.num_rows, A.row_offsets.data(), A.values.data(), sums.data(), 0, nullptr));
+            cusp::detail::check(cusp::detail::by_type<V>(cmi_blas_amax_f64, cmi_blas_amax_f32)(sums.size(), sums.data(), static_cast<V *>(w.result), nullptr, w.ws, nullptr));
         };
         once();
         cusp::detail::check(cmi_event_record(e0, nullptr));

@@ -63,8 +63,8 @@ template <typename V> struct bench {
         cusp::detail::check(cmi_event_create(&e0));
         cusp::detail::check(cmi_event_create(&e1));
         auto once = [&] {
-            cusp::detail::check(cusp::krylov::detail::multishift::update_xp_(A.num_rows, ns, state.data(), coef.data(), coef.data() + ns, coef.data() + 2 * ns, r.data(),
-                                                                             p0.data(), x.data(), ps.data()));
+            cusp::detail::check(cusp::detail::by_type<V>(cmi_cg_m_update_xp_f64, cmi_cg_m_update_xp_f32)(
+                A.num_rows, ns, A.num_rows, state.data(), coef.data(), coef.data() + ns, coef.data() + 2 * ns, r.data(), p0.data(), x.data(), ps.data(), nullptr));
         };
         once();
         cusp::detail::check(cmi_event_record(e0, nullptr));
