@@ -178,6 +178,9 @@ def _declare(L):
         getattr(L, f"cmi_bicgstab_m_s_{suf}").argtypes = [i64, sc, sc, vp, vp, vp, vp]
         getattr(L, f"cmi_bicgstab_m_coefficients_{suf}").argtypes = [i64, sc, sc, sc, sc, sc, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         getattr(L, f"cmi_bicgstab_m_update_xs_{suf}").argtypes = [i64, i64, i64] + [vp] * 14
+        getattr(L, f"cmi_lobpcg_residual_{suf}").argtypes = [i64] + [vp] * 8     # cusp::eigen::lobpcg's vector tail (csrc/lobpcg.hip)
+        getattr(L, f"cmi_lobpcg_gram_{suf}").argtypes = [i64] + [vp] * 9
+        getattr(L, f"cmi_lobpcg_update_{suf}").argtypes = [i64, sc, sc, sc, c_int, sc] + [vp] * 11
     L.cmi_count_zeros_f64.argtypes = [i64, vp, POINTER(c_int64), vp]
     L.cmi_count_zeros_f32.argtypes = [i64, vp, POINTER(c_int64), vp]
     L.cmi_tuning_hyb_rule.argtypes = [c_int, POINTER(c_int), POINTER(c_double), POINTER(c_int64)]
@@ -1377,6 +1380,48 @@ def cg_m_update_xp(n, ld, state, beta_s, alpha_s, zeta_0, r, p0, x, p_s, stream=
     _need_all("cg_m_update_xp", r.dtype, state=state, beta_s=beta_s, alpha_s=alpha_s, zeta_0=zeta_0, r=r, p0=p0, x=x, p_s=p_s)
     check(getattr(lib(), "cmi_cg_m_update_xp_" + _suffix(r))(int(n), beta_s.numel(), int(ld), _ptr(state), _ptr(beta_s), _ptr(alpha_s), _ptr(zeta_0), _ptr(r),
                                                               _ptr(p0), _ptr(x), _ptr(p_s), _stream(stream)))
+
+
+def _ptr_given(t, stand_in):
+    """_ptr for an operand whose PRESENCE selects a form of the call: an empty tensor has no address, so it hands over `stand_in`'s (never
+    dereferenced: the call has n == 0)."""
+    return None if t is None else c_void_p(t.data_ptr() or stand_in.data_ptr())
+
+
+def lobpcg_residual(lambda_dev, x, ax, r, rr_out, workspace, stream=None, mirror=None):
+    """r <- T(-lambda) x + ax (lambda: a 1-element float64 device tensor); rr_out <- <r, r>, also to the HostScalar `mirror`."""
+    import torch
+    _need_all("lobpcg_residual", torch.float64, lambda_dev=lambda_dev, rr_out=rr_out, workspace=workspace)
+    _need_all("lobpcg_residual", r.dtype, x=x, ax=ax, r=r)
+    check(getattr(lib(), "cmi_lobpcg_residual_" + _suffix(r))(r.numel(), _ptr(lambda_dev), _ptr(x), _ptr(ax), _ptr(r), _ptr(rr_out),
+                                                               mirror.ptr if mirror is not None else None, _ptr(workspace), _stream(stream)))
+    if mirror is not None:
+        mirror.record(stream)
+
+
+def lobpcg_gram(pp, x, w, aw, p, ap, gram_out, workspace, stream=None):
+    """p, ap <- s p, s ap with s = T(1) / T(sqrt(pp)) (pp: 1 float64 on the device), and from the scaled values gram_out[0..7] = <x,aw>, <w,aw>,
+    <x,w>, <x,ap>, <w,ap>, <p,ap>, <x,p>, <w,p> (float64).  p and ap None (the first iteration): only gram_out[0..2]; pp may be None."""
+    import torch
+    _need_all("lobpcg_gram", torch.float64, pp=pp, gram_out=gram_out, workspace=workspace)
+    _need_all("lobpcg_gram", x.dtype, x=x, w=w, aw=aw, p=p, ap=ap)
+    check(getattr(lib(), "cmi_lobpcg_gram_" + _suffix(x))(x.numel(), _ptr(pp), _ptr(x), _ptr(w), _ptr(aw), _ptr_given(p, gram_out), _ptr_given(ap, gram_out), _ptr(gram_out),
+                                                           _ptr(workspace),
+                                                           _stream(stream)))
+
+
+def lobpcg_update(cx, cr, cp, first, lambda_new, w, aw, p, ap, x, ax, r, scalars_out, workspace, stream=None, mirror=None):
+    """p, ap <- cr (w, aw) + cp (p, ap) (first: cr (w, aw) + (p, ap)); x, ax <- cx (x, ax) + (p, ap); r <- T(-lambda_new) x + ax (r None: skipped);
+    scalars_out[0] <- <r, r> (also to `mirror`), scalars_out[1] <- <p, p>.  The scalars by value."""
+    import torch
+    _need_all("lobpcg_update", torch.float64, scalars_out=scalars_out, workspace=workspace)
+    _need_all("lobpcg_update", x.dtype, w=w, aw=aw, p=p, ap=ap, x=x, ax=ax, r=r)
+    use_mirror = mirror is not None and r is not None
+    check(getattr(lib(), "cmi_lobpcg_update_" + _suffix(x))(x.numel(), float(cx), float(cr), float(cp), int(bool(first)), float(lambda_new), _ptr(w), _ptr(aw),
+                                                             _ptr(p), _ptr(ap), _ptr(x), _ptr(ax), _ptr_given(r, scalars_out), _ptr(scalars_out),
+                                                             mirror.ptr if use_mirror else None, _ptr(workspace), _stream(stream)))
+    if use_mirror:
+        mirror.record(stream)
 
 
 def bicgstab_m_s(alpha_1, chi_0, r_1, As, s_0, stream=None):

@@ -12,9 +12,7 @@
 // loads of x_s and p_s are in flight before the first store -- with the per-shift coefficients as wave-uniform reads.  Shift s lives at
 // offset s * ld (64-bit: (num_shifts - 1) ld + n may pass 2^31); whether shift s can use 16-byte accesses is decided per shift, since an
 // ld that is no multiple of the piece breaks the alignment from one shift to the next.
-#include "blas1_shared.h"
-
-#include <initializer_list>
+#include "blas1_shared.h" // + ld_piece / st_piece, any_overlap
 
 namespace cmi {
 namespace {
@@ -22,32 +20,6 @@ namespace {
 constexpr int kShiftUnroll = 4;    // shifts whose loads are in flight together: 8 x 16 bytes per lane
 constexpr bool kShiftNtStores = true; // x_s and p_s (s_s) are not read again before the next iteration's multiply has streamed its matrix: nt, as CG's x
 constexpr bool kShiftNtLoads = true;  // ... and each is read once per iteration
-
-// a lane's piece of one vector: cnt <= W elements from `base`; wide (uniform but for the last piece): one 16-byte access; nt: a stream read once
-template <typename T> __device__ __forceinline__ typename vec16<T>::type ld_piece(const T *base, int cnt, bool wide, bool nt = false)
-{
-    typedef typename vec16<T>::type V;
-    constexpr int W = vec16<T>::n;
-    V v = {};
-    if (wide) v = nt ? __builtin_nontemporal_load(reinterpret_cast<const V *>(base)) : *reinterpret_cast<const V *>(base);
-    else {
-#pragma unroll
-        for (int k = 0; k < W; k++)
-            if (k < cnt) v[k] = base[k];
-    }
-    return v;
-}
-template <typename T> __device__ __forceinline__ void st_piece(T *base, typename vec16<T>::type v, int cnt, bool wide, bool nt)
-{
-    typedef typename vec16<T>::type V;
-    constexpr int W = vec16<T>::n;
-    if (wide) st_policy(reinterpret_cast<V *>(base), v, nt);
-    else {
-#pragma unroll
-        for (int k = 0; k < W; k++)
-            if (k < cnt) base[k] = v[k];
-    }
-}
 
 // ---- CG-M ------------------------------------------------------------------------------------------------------------------------------
 // KERNEL_ZB (+ the clamp), KERNEL_A and the rotation of zeta for every shift; one workgroup, strided over the shifts, so that the store of
@@ -258,22 +230,6 @@ bicgstab_m_rotate_kernel(int64_t num_shifts, T *__restrict__ zeta_m1, T *__restr
 }
 
 // ---- refusals, all made before any device call -------------------------------------------------------------------------------------------
-struct span { const void *p; size_t bytes; };
-bool overlap(const span &a, const span &b)
-{
-    if (!a.p || !b.p || a.bytes == 0 || b.bytes == 0) return false;
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a.p), b0 = reinterpret_cast<uintptr_t>(b.p);
-    return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
-}
-// every output against every other output and against every input
-bool any_overlap(std::initializer_list<span> outs, std::initializer_list<span> ins)
-{
-    for (const span *a = outs.begin(); a != outs.end(); ++a) {
-        for (const span *b = a + 1; b != outs.end(); ++b) if (overlap(*a, *b)) return true;
-        for (const span &b : ins) if (overlap(*a, b)) return true;
-    }
-    return false;
-}
 template <typename T> size_t shifted_bytes(int64_t n, int64_t num_shifts, int64_t ld)
 {
     return num_shifts > 0 && n > 0 ? ((size_t)(num_shifts - 1) * (size_t)ld + (size_t)n) * sizeof(T) : 0;

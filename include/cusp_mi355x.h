@@ -1203,6 +1203,36 @@ int cmi_cg_m_update_xp_f64(int64_t n, int64_t num_shifts, int64_t ld, const doub
                            const double *r, double *p0, double *x, double *p_s, void *stream);
 int cmi_cg_m_update_xp_f32(int64_t n, int64_t num_shifts, int64_t ld, const float *state, const float *beta_s, const float *alpha_s, const float *zeta_0,
                            const float *r, float *p0, float *x, float *p_s, void *stream);
+/* cusp::eigen::lobpcg for one eigenpair (csrc/lobpcg.hip): the vector tail of an iteration in three kernels, the reference's expressions
+ * (cusp/eigen/detail/lobpcg.inl:67-180) term for term and unfused.  Reductions: products and sums in double, deterministic two-stage (fixed
+ * grid and tree, no atomics), results in DEVICE doubles; `workspace`: cmi_blas_workspace_bytes().  No call allocates or synchronises.  n == 0
+ * stores zeros to the reduction results and touches no vector.  Refused with CMI_ERROR_INVALID_VALUE before any device call: a negative n, a
+ * null required array, an output range (vectors and result scalars) that overlaps another output or an input.  16-byte accesses when every
+ * vector operand is 16-byte aligned, element accesses otherwise.
+ * cmi_lobpcg_residual_*: r <- T(-*lambda_dev) x + ax (one multiply, one add);  *rr_dev <- <r, r>, also written to rr_host_mirror when that is
+ *   not NULL (page-locked memory the device can write, as cmi_cg_update_*).
+ * cmi_lobpcg_gram_*: with p != NULL: s = T(1) / T(sqrt(*pp_dev)) (the root in double, rounded to T once); p <- s p, ap <- s ap in place; and
+ *   from the SCALED values gram_dev[0..7] = <x,aw>, <w,aw>, <x,w>, <x,ap>, <w,ap>, <p,ap>, <x,p>, <w,p>.  With p == NULL (and ap == NULL; the
+ *   first iteration) only gram_dev[0..2]; pp_dev may then be NULL.  x, w, aw are only read: 5 vector reads and 2 writes.
+ * cmi_lobpcg_update_*: the scalars by value in T (the host has just formed them from the 3 x 3 problem).
+ *     p <- cr w + cp p,  ap <- cr aw + cp ap            (first != 0: p <- cr w + p, ap <- cr aw + ap -- the reference's axpy; cp is not used)
+ *     x <- cx x + T(1) p,  ax <- cx ax + T(1) ap        (the NEW p, ap)
+ *     r <- T(-lambda_new) x + ax                        (the new x, ax; r == NULL: skipped with its sum)
+ *     scalars_dev[0] <- <r, r> (+ rr_host_mirror);  scalars_dev[1] <- <p, p>, the next cmi_lobpcg_gram_*'s pp_dev
+ *   With identity M, w is r normalised in place by cmi_blas_scal_recip_* from <r, r>: an iteration is scal_recip, the multiply, gram, one
+ *   host read of eight doubles, update -- and the mirror's read for the monitor.                                                      */
+int cmi_lobpcg_residual_f64(int64_t n, const double *lambda_dev, const double *x, const double *ax, double *r, double *rr_dev, double *rr_host_mirror,
+                            void *workspace, void *stream);
+int cmi_lobpcg_residual_f32(int64_t n, const double *lambda_dev, const float *x, const float *ax, float *r, double *rr_dev, double *rr_host_mirror,
+                            void *workspace, void *stream);
+int cmi_lobpcg_gram_f64(int64_t n, const double *pp_dev, const double *x, const double *w, const double *aw, double *p, double *ap, double *gram_dev,
+                        void *workspace, void *stream);
+int cmi_lobpcg_gram_f32(int64_t n, const double *pp_dev, const float *x, const float *w, const float *aw, float *p, float *ap, double *gram_dev,
+                        void *workspace, void *stream);
+int cmi_lobpcg_update_f64(int64_t n, double cx, double cr, double cp, int first, double lambda_new, const double *w, const double *aw, double *p, double *ap,
+                          double *x, double *ax, double *r, double *scalars_dev, double *rr_host_mirror, void *workspace, void *stream);
+int cmi_lobpcg_update_f32(int64_t n, float cx, float cr, float cp, int first, float lambda_new, const float *w, const float *aw, float *p, float *ap, float *x,
+                          float *ax, float *r, double *scalars_dev, double *rr_host_mirror, void *workspace, void *stream);
 /* BiCGstab-M; the scalars of the unshifted system are passed by value in T (the header layer forms them on the host, as the reference does).
  * cmi_bicgstab_m_s_*: s_0 <- r_1 + alpha_1 (s_0 - chi_0 As)                                                                     (KERNEL_S)
  * cmi_bicgstab_m_coefficients_*: per shift, from the current zeta_m1, zeta_0, rho_0 (all three only read):
