@@ -132,9 +132,18 @@ typedef enum cmi_kernel {
     CMI_CSR_SCALAR = 1, /* one lane per row          (ref: csr_scalar.h:51-73)                   */
     CMI_CSR_VECTOR = 2, /* threads_per_row lanes/row (ref: csr_vector_spmv.h:71-161, THREADS_PER_ROW) */
     CMI_CSR_STREAM = 3, /* LDS-staged nnz tile, sequential per-row sum (bit-exact vs host order); threads_per_row
-                           0: rows of 512+ entries are streamed by their whole workgroup instead (re-associated,
-                           <= 1e-6; ~1-2 ns instead of ~12 ns per entry), 1: storage order for every row,
-                           2..64: that many lanes per row (lane-strided partial sums)                    */
+                           0: rows of 512+ entries are streamed by their whole workgroup instead (re-associated:
+                           the rounding-error contract below; ~1-2 ns instead of ~12 ns per entry), 1: storage order
+                           for every row, 2..64: that many lanes per row (lane-strided partial sums)
+                           THE ROUNDING-ERROR CONTRACT of every kernel that re-associates a row sum (this one with
+                           threads_per_row 0 or 2+, CMI_CSR_VECTOR, CMI_CSR_BALANCED, CMI_ELL_ROW with several lanes,
+                           CMI_COO_SEGMENTED / _LANE4): y_i is SOME summation order of the row's rounded products
+                           fl(a_ij x_j) (and of y_i's old value when accumulating), every product and every addition
+                           done in the value type T.  So for a row of n terms
+                               |y_i - exact_i| <= gamma_n * sum_j |a_ij x_j| (+ |y_i old|),  gamma_n = n u / (1 - n u),
+                           u = 2^-53 (f64) or 2^-24 (f32): about 1e-15 for 8 entries, 1e-11 for 100 000 in f64.  A row
+                           without entries is +0.0 (or y_i unchanged), a row of one entry is its rounded product.
+                           tests/test_rounding_gpu.py holds every such path to it against exact row sums.  */
     CMI_CSR_STREAM_PIPE = 4, /* persistent, software-pipelined csr_stream (next tile's streams in flight) */
     CMI_CSR_BALANCED = 5,   /* merge-path split of row ends + entries: equal work per tile whatever the row
                                lengths (a few huge rows, power-law tails, runs of empty rows); replaces KTT's
@@ -204,7 +213,8 @@ typedef enum cmi_kernel {
     /* ELL */
     CMI_ELL_ROW = 10, /* one lane per row            (ref: ell_spmv.h:55-93); threads_per_row 2,4,8,16: that many
                          lanes per row, each summing every 2nd / 4th / ... slot (ref: THREADS_PER_ROW of ktt
-                         kernels/ell_kernel.h:102-109,165-173) -- re-associated sums, <= 1e-6; threads_per_row 0
+                         kernels/ell_kernel.h:102-109,165-173) -- re-associated sums: any order of the row's rounded
+                         products, error <= gamma_n * sum|a x| (the contract at CMI_CSR_STREAM); threads_per_row 0
                          picks width/16 lanes (<= 16) for matrices >= 32 slots wide with < 131072 rows (>= 64 wide:
                          < 524288 rows): 6x on 2000 x 512, 1.2x on 200000 x 64; threads_per_row 1 never          */
     /* DIA */
@@ -416,7 +426,8 @@ int cmi_plan_validate(const cmi_plan *plan, const int32_t *index_array, const in
 int cmi_plan_config(const cmi_plan *plan, cmi_config *out);
 /* What was measured: longest row and entries sitting in rows of 512+ (CSR; -1 otherwise), row-sortedness   */
 /* (COO: 1/0; -1 otherwise), and whether every result is the storage-order sum (bit-identical to the host   */
-/* loop: 1) or some rows are re-associated (within 1e-6: 0).                                                  */
+/* loop: 1) or some rows are re-associated (0: some other order of the same rounded products, so within      */
+/* gamma_n * sum|a x| of the exact row sum, gamma_n = n u / (1 - n u) -- the contract at CMI_CSR_STREAM).     */
 int cmi_plan_info(const cmi_plan *plan, int64_t *max_row_length, int64_t *entries_in_long_rows, int *coo_sorted,
                   int *storage_order_sums);
 
