@@ -398,7 +398,7 @@ template <typename T> __device__ __forceinline__ T sum_in_order(T s, const T *p,
 }
 
 // run `f(std::integral_constant<int, V>())` for the runtime value v among the instances Vs...; false when v is none of them
-template <int... Vs, typename F> inline bool with_int(int v, F &&f)
+template <int... Vs, typename F> __host__ __device__ inline bool with_int(int v, F &&f)
 {
     return ((v == Vs ? (f(std::integral_constant<int, Vs>()), true) : false) || ...);
 }

@@ -768,24 +768,72 @@ csr_wavep_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, const in
 // neighbouring tiles, encoded against THEIR bases, whose products are parked and never read but whose gather address must stay inside
 // x.  One v_min per entry covers both ends (selecting the foreign positions costs a compare and a select per candidate position: more).
 // The !fits path (the arrays' last vector, an empty tile) reads the caller's 32-bit Aj, as before.
-// SH (round 13; only with C16): the plan also holds the shift-invariant tiles' table (wavev_cols16_scan_kernel above).  Its first word is
-// fetched with a scalar load beside the partition entry and the base (address from wt alone); a MARKED tile -- always an equal-length one,
-// so uniform_len is its row length L -- then takes a wave-uniform branch in front of the stream requests and asks for NO column at all:
-// lane l picks up shift[wt][l & 7] with one vector load (32 bytes per wave, issued first), the value requests go out as ever, and behind
-// the barrier position p = e + i - nz0 of the lane's vectors gives r = p / L = (p div_mul) >> 16 (24-bit multiplies: full rate; exact for
-// p < 4096, a tile has fewer than 1024), k = p - r L and column = min(rs + r + shift[k], last column) with shift[k] read from lane k by a
-// ds_bpermute -- one LDS-crossbar instruction per entry, no LDS memory, where a compare / select chain over eight SGPRs costs 2 (L - 1)
-// VALU instructions per entry.  Positions before nz0 (p wraps) and past nz1 form some column that the same unsigned minimum keeps inside
-// x; their products are parked and never read.  Everything else -- row bounds, parking, sums, epilogues -- is shared with the other tiles;
-// an unmarked tile runs the C16 path above.
-// Four wave tiles per workgroup.
+// SH (round 13, row lanes since round 21; only with C16): the plan also holds the shift-invariant tiles' table (wavev_cols16_scan_kernel
+// above).  Its eight words are fetched with ONE scalar load beside the partition entry and the base (address from wt alone, 32-byte
+// aligned); a MARKED tile that fits its slots runs wavev_rowlane_tile below and nothing else, an unmarked tile the C16 path above.
+// Four wave tiles per workgroup (the kernel follows its marked-tile body).
+//
+// wavev_rowlane_tile: one marked tile of rows of L entries (L = uniform_len, 1..8, a template argument: the kernel branches once on the
+// wave-uniform value, so a slot k >= L issues no request and every wait counts exact loads).  Such a tile asks for NO column.  What it needs
+// of x are L contiguous windows x[rs + shift[k] .. + nr): the lane that sums row r needs exactly x[rs + r + shift[k]], k < L -- addresses
+// made of wave-uniform data and the lane number, so they go out as L coalesced loads IN THE BATCH of the value requests, in front of the
+// barrier (DIA's request shape: lane per row, x at fixed offsets, no dependent hop).  The row is clamped to the tile's last, so every
+// address is a true column of the tile: no last-column minimum, no foreign positions, no gather.  The lanes park their VALUES where the
+// other tiles park products -- same positions, same clamping to `last`, same nt policy, same 16-byte stores -- and the row lane forms
+// sum + v[k] x[k] in storage order: the host loop's products in the host loop's order.  A tile of more than 64 rows (L <= 3 at V = 1) has
+// its first turn's x in flight with the streams and loads the x of turn t >= 1 at the top of that turn (the values are in LDS by then).
+// y, the dot and the lanes' rows (lane, lane + 64, ...) are the other tiles'.
+template <typename T, int V, int POL, bool DOT, int L, typename S>
+__device__ __forceinline__ void wavev_rowlane_tile(T *mine, int lane, int rs, int nr, int nz0, int nz1, S sh, const T *__restrict__ Ax,
+                                                   const T *__restrict__ x, T *__restrict__ y, int accumulate, const T *__restrict__ w, double &d)
+{
+    constexpr int E = sizeof(T) == 8 ? 2 : 4, NL = (V * 4) / E;
+    typedef T __attribute__((ext_vector_type(E))) val_t;
+    constexpr bool NT = (POL & kPolLoadNT) != 0, NTS = (POL & kPolStoreNT) != 0;
+    const int fbase = nz0 & ~(E - 1), last = (nz1 - 1) & ~(E - 1);
+    val_t v[NL];
+    T xk[L];
+#pragma unroll
+    for (int k = 0; k < NL; k++) {
+        int e = fbase + (k * kWave + lane) * E;
+        e = e < last ? e : last;
+        v[k] = ld<NT>(reinterpret_cast<const val_t *>(Ax + e));
+    }
+    // The turns of the row loop are the WAVE's (a uniform count, at least one: a marked tile has rows): a lane without a row in a turn
+    // walks the tile's last row and stores nothing, so the first turn's x is asked for and used by straight-line code.
+    unsigned row = (unsigned)(lane < nr ? lane : nr - 1);
+#pragma unroll
+    for (int k = 0; k < L; k++) xk[k] = (x + ((int64_t)rs + sh[k]))[row]; // a uniform base per slot, the row per lane; x is reused: a plain load
+    __builtin_amdgcn_sched_barrier(0); // every request of the tile is out before anything waits
+#pragma unroll
+    for (int k = 0; k < NL; k++) *reinterpret_cast<val_t *>(mine + (k * kWave + lane) * E) = v[k]; // 16 bytes per lane, lanes contiguous: no bank conflict
+    __builtin_amdgcn_wave_barrier(); // (compiler only: the hardware runs a wave's LDS instructions in order)
+    int r0 = 0;
+    do {
+        const int r = r0 + lane; // this lane's rows are lane, lane + 64, ... as in every other tile
+        if (r0 > 0) {
+            row = (unsigned)(r < nr ? r : nr - 1);
+#pragma unroll
+            for (int k = 0; k < L; k++) xk[k] = (x + ((int64_t)rs + sh[k]))[row];
+        }
+        const T *val = mine + (nz0 - fbase) + row * L;
+        T sum = accumulate ? y[rs + row] : T(0);
+#pragma unroll
+        for (int k = 0; k < L; k++) sum = sum + val[k] * xk[k];
+        if (r < nr) {
+            st<NTS>(y + rs + r, sum);
+            if constexpr (DOT) d += (double)sum * (double)w[rs + r];
+        }
+    } while ((r0 += kWave) < nr);
+}
+
 template <typename T, int V, int POL, bool DOT, bool C16, bool SH = false>
 __global__ void __launch_bounds__(256)
 csr_wavev_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t num_entries, const int *Ap /* not restrict: see csr_wave */,
                  const int *__restrict__ Aj, const T *__restrict__ Ax, const T *__restrict__ x, T *__restrict__ y, int64_t num_tiles,
                  int64_t tiles_per_xcd, int swizzle, int accumulate, const T *__restrict__ w, double *__restrict__ dot_partial,
                  int uniform_len, const uint16_t *__restrict__ cols16, const int32_t *__restrict__ tile_base, int last_col,
-                 const int32_t *__restrict__ shift, unsigned div_mul)
+                 const int32_t *__restrict__ shift)
 {
     static_assert(C16 || !SH, "the shift-invariant tiles' table belongs to the 16-bit column copy");
     // Request shape: every load instruction of the wave covers ONE contiguous span and every 128-byte line of the streams is requested
@@ -798,6 +846,7 @@ csr_wavev_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t 
     typedef T __attribute__((ext_vector_type(E))) val_t;
     typedef unsigned __attribute__((ext_vector_type(2))) uint2v;
     typedef std::conditional_t<E == 2, unsigned, uint2v> idx16_t; // E 16-bit offsets
+    typedef int __attribute__((ext_vector_type(kShiftMaxLen))) shift_t;
     __shared__ __attribute__((aligned(16))) T prod[4][SLOTS];
     __shared__ double dot_slots[DOT ? 4 : 1];
     constexpr bool NT = (POL & kPolLoadNT) != 0, NTS = (POL & kPolStoreNT) != 0;
@@ -811,14 +860,18 @@ csr_wavev_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t 
         const int rs = lo.x, nz0 = lo.y, re = hi.x, nz1 = hi.y; // {first row, first entry} of this tile and of the next: one scalar hop
         unsigned cbase = 0;
         if constexpr (C16) cbase = (unsigned)tile_base[wt]; // (scalar, beside the partition entry)
-        bool marked = false;
-        if constexpr (SH) { // (scalar, beside them: this tile's columns are its first row's plus the row)
-            int first_shift = shift[8 * wt];
-            asm volatile("" : "+s"(first_shift)); // requested HERE, with the partition entry, not where the branch on it stands
-            marked = first_shift != INT32_MIN;
-        }
         const int nr = re - rs;
-        if (nr > 0) { // (uniform per wave)
+        bool rowlane = false; // (uniform) a marked tile took the row-lane path
+        if constexpr (SH) { // (scalar, beside them: this tile's columns are its first row's plus the row)
+            shift_t sh = *reinterpret_cast<const shift_t *>(shift + kShiftMaxLen * wt);
+            asm volatile("" : "+s"(sh), "+s"(cbase)); // requested HERE, with the partition entry, not where the branch on them stands
+            // marked (nr >= 1 rows of uniform_len entries each; 1..8 by the launcher) and inside the arrays and the slots (`fits` below)
+            if (sh[0] != INT32_MIN && (int64_t)((nz1 + E - 1) & ~(E - 1)) <= num_entries && nz1 - (nz0 & ~(E - 1)) <= SLOTS)
+                rowlane = with_int<1, 2, 3, 4, 5, 6, 7, 8>(uniform_len, [&](auto LL) {
+                    wavev_rowlane_tile<T, V, POL, DOT, decltype(LL)::value>(prod[wave], lane, rs, nr, nz0, nz1, sh, Ax, x, y, accumulate, w, d);
+                });
+        }
+        if (nr > 0 && !rowlane) { // (uniform per wave)
             const int fbase = nz0 & ~(E - 1);
             // Every row of the tile has the longest row's length (64-bit product: a stretch of empty rows makes nr large): row r is
             // [nz0 + r uniform_len, nz0 + (r + 1) uniform_len) and nothing is read from Ap.  (uniform per wave: a scalar branch)
@@ -838,17 +891,12 @@ csr_wavev_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t 
                 idx_t c[NL];
                 idx16_t c16[NL];
                 val_t v[NL];
-                int shl = 0;
-                if (SH && marked) { // (uniform per wave) no column request: lane l holds shift[wt][l & 7]
-                    shl = shift[8 * wt + (lane & 7)];
-                } else {
 #pragma unroll
-                    for (int k = 0; k < NL; k++) {
-                        int e = fbase + (k * kWave + lane) * E;
-                        e = e < last ? e : last;
-                        if constexpr (C16) c16[k] = ld<NT>(reinterpret_cast<const idx16_t *>(cols16 + e));
-                        else c[k] = ld<NT>(reinterpret_cast<const idx_t *>(Aj + e));
-                    }
+                for (int k = 0; k < NL; k++) {
+                    int e = fbase + (k * kWave + lane) * E;
+                    e = e < last ? e : last;
+                    if constexpr (C16) c16[k] = ld<NT>(reinterpret_cast<const idx16_t *>(cols16 + e));
+                    else c[k] = ld<NT>(reinterpret_cast<const idx_t *>(Aj + e));
                 }
 #pragma unroll
                 for (int k = 0; k < NL; k++) {
@@ -857,19 +905,7 @@ csr_wavev_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t 
                     v[k] = ld<NT>(reinterpret_cast<const val_t *>(Ax + e));
                 }
                 __builtin_amdgcn_sched_barrier(0); // every stream request is out before the first gather address is formed
-                if (SH && marked) {
-#pragma unroll
-                    for (int k = 0; k < NL; k++) {
-                        int e = fbase + (k * kWave + lane) * E;
-                        e = e < last ? e : last;
-#pragma unroll
-                        for (int i = 0; i < E; i++) {
-                            const unsigned p = (unsigned)(e + i - nz0), r = __umul24(p, div_mul) >> 16, kk = p - __umul24(r, (unsigned)uniform_len);
-                            const unsigned col = (unsigned)(rs + (int)r + __builtin_amdgcn_ds_bpermute((int)(kk << 2), shl));
-                            c[k][i] = (int)(col < (unsigned)last_col ? col : (unsigned)last_col);
-                        }
-                    }
-                } else if constexpr (C16) {
+                if constexpr (C16) {
 #pragma unroll
                     for (int k = 0; k < NL; k++)
 #pragma unroll
@@ -1673,7 +1709,7 @@ static int launch_wavev(const cmi_config &c, const cmi_plan *plan, int pol, hipS
                     hipLaunchKernelGGL((csr_wavev_kernel<T, decltype(VV)::value, decltype(P)::value, decltype(DOT)::value, cf >= 1, cf == 2>),
                                        dim3(g.grid), dim3(256), 0, s, plan->wave_row_start.get(), plan->wave_tiles, A.nnz, A.Ap, A.Aj, A.Ax, A.x, A.y, g.tiles,
                                        g.tiles_per_xcd, g.swizzle, A.accumulate, d.w, d.partial, uniform_len, plan->wavev_cols16.get(), plan->wavev_base.get(),
-                                       (int)(cols - 1), plan->wavev_shift.get(), shift_div_mul(uniform_len > 0 ? uniform_len : 1));
+                                       (int)(cols - 1), plan->wavev_shift.get());
                 });
             });
         });
