@@ -27,7 +27,7 @@ from .binding import (  # noqa: F401
     cg_update, cg_direction, cg_direction_x, HostScalar,
     blas_scal, blas_xmy, blas_axpbypcz, blas_asum, blas_amax, blas_axpy_dot, blas_axpy_ratio, csr_diagonal,
     pcg_update_jacobi, pcg_direction_x_jacobi, bicgstab_s, bicgstab_xr, bicgstab_p, cr_xr, cr_py,
-    cg_m_coefficients, cg_m_update_xp, bicgstab_m_s, bicgstab_m_coefficients, bicgstab_m_update_xs, lobpcg_residual, lobpcg_gram, lobpcg_update,
+    cg_m_coefficients, cg_m_update_xp, bicgstab_m_s, bicgstab_m_coefficients, bicgstab_m_update_xs, lobpcg_residual, lobpcg_gram, lobpcg_update, dense_gemm,
     csr_abs_row_sums, ell_abs_row_sums, dia_abs_row_sums, random_fill, blas_scal_recip,
     csr_strength_symmetric, csr_scale_rows, aggregates_fit, csr_elementwise, relax_jacobi_presmooth,
     csr_ring_max, maximal_independent_set, mis_aggregate,

@@ -181,6 +181,7 @@ def _declare(L):
         getattr(L, f"cmi_lobpcg_residual_{suf}").argtypes = [i64] + [vp] * 8     # cusp::eigen::lobpcg's vector tail (csrc/lobpcg.hip)
         getattr(L, f"cmi_lobpcg_gram_{suf}").argtypes = [i64] + [vp] * 9
         getattr(L, f"cmi_lobpcg_update_{suf}").argtypes = [i64, sc, sc, sc, c_int, sc] + [vp] * 11
+        getattr(L, f"cmi_dense_gemm_{suf}").argtypes = [i64, i64, i64, vp, i64, vp, i64, vp, i64, vp]   # cusp::blas::gemm (csrc/dense.hip)
     L.cmi_count_zeros_f64.argtypes = [i64, vp, POINTER(c_int64), vp]
     L.cmi_count_zeros_f32.argtypes = [i64, vp, POINTER(c_int64), vp]
     L.cmi_tuning_hyb_rule.argtypes = [c_int, POINTER(c_int), POINTER(c_double), POINTER(c_int64)]
@@ -1422,6 +1423,13 @@ def lobpcg_update(cx, cr, cp, first, lambda_new, w, aw, p, ap, x, ax, r, scalars
                                                              mirror.ptr if use_mirror else None, _ptr(workspace), _stream(stream)))
     if use_mirror:
         mirror.record(stream)
+
+
+def dense_gemm(m, n, k, A, lda, B, ldb, C, ldc, stream=None):
+    """C (m x n) <- A (m x k) B (k x n), column-major with leading dimensions lda, ldb, ldc: A, B and C are 1-D device tensors of one dtype that
+    hold the operands from their first element (views at any element offset); the chain of each element starts at +0 and adds j ascending."""
+    _need_all("dense_gemm", C.dtype, A=A, B=B, C=C)
+    check(getattr(lib(), "cmi_dense_gemm_" + _suffix(C))(int(m), int(n), int(k), _ptr(A), int(lda), _ptr(B), int(ldb), _ptr(C), int(ldc), _stream(stream)))
 
 
 def bicgstab_m_s(alpha_1, chi_0, r_1, As, s_0, stream=None):

@@ -21,6 +21,22 @@ template <> struct index_of_impl<column_major> {
 };
 } // namespace detail
 
+// non-owning view of a column_major block with a pitch (what cusp::blas::gemm takes beside an array2d): element (i, j) at data()[j * pitch + i]
+template <typename T, typename MemorySpace> class array2d_column_view {
+public:
+    typedef typename std::remove_const<T>::type value_type;
+    typedef MemorySpace memory_space;
+    typedef array2d_format format;
+    typedef column_major orientation;
+    size_t num_rows, num_cols, pitch;
+    array2d_column_view() : num_rows(0), num_cols(0), pitch(0), ptr_(nullptr) {}
+    array2d_column_view(size_t rows, size_t cols, size_t pitch_, T *first) : num_rows(rows), num_cols(cols), pitch(pitch_), ptr_(first) {}
+    T *column_pointer(size_t j) const { return ptr_ + j * pitch; }
+    array1d_view<T, MemorySpace> column(size_t j) const { return array1d_view<T, MemorySpace>(column_pointer(j), num_rows); }
+private:
+    T *ptr_;
+};
+
 template <typename T, typename MemorySpace, typename Orientation = row_major> class array2d {
 public:
     typedef T value_type;
@@ -88,6 +104,14 @@ public:
     }
 
     size_t index_of(size_t i, size_t j) const { return detail::index_of_impl<Orientation>::at(i, j, pitch); }
+
+    // column_major only: column j as a pointer / an array1d_view of num_rows values, and `count` columns from `first` as a view with this pitch
+    T *column_pointer(size_t j) { static_assert(std::is_same<Orientation, column_major>::value, "columns are contiguous in column_major only"); return values.data() + j * pitch; }
+    const T *column_pointer(size_t j) const { static_assert(std::is_same<Orientation, column_major>::value, "columns are contiguous in column_major only"); return values.data() + j * pitch; }
+    array1d_view<T, MemorySpace> column(size_t j) { return array1d_view<T, MemorySpace>(column_pointer(j), num_rows); }
+    array1d_view<const T, MemorySpace> column(size_t j) const { return array1d_view<const T, MemorySpace>(column_pointer(j), num_rows); }
+    array2d_column_view<T, MemorySpace> columns(size_t first, size_t count) { return array2d_column_view<T, MemorySpace>(num_rows, count, pitch, column_pointer(first)); }
+    array2d_column_view<const T, MemorySpace> columns(size_t first, size_t count) const { return array2d_column_view<const T, MemorySpace>(num_rows, count, pitch, column_pointer(first)); }
 
 private:
     template <typename Other> void assign_transposed(const Other &o)

@@ -5,12 +5,15 @@
 //   copy(x, y)   fill(x, v)   dot(x, y)   dotc(x, y)   nrm2(x)
 // and the rest of the reference's BLAS-1 set for the multiply's other callers (preconditioned cg, bicgstab, cr):
 //   scal(x, alpha)   xmy(x, y, z)   axpbypcz(x, y, z, out, alpha, beta, gamma)   nrm1(x)   nrmmax(x)   amax(x)
+// and the one BLAS-3 routine the reference's solvers call (cusp::eigen::lanczos):
+//   gemm(A, B, C)                C <- A B for column_major array2d's or array2d_column_view's; each element is the chain s = 0; s = s + A(i,j) B(j,c), j ascending
 // host_memory: plain loops.  device_memory: cmi_blas_*_{f64,f32} kernels; reductions are deterministic two-stage trees whose scalar is copied back (one 8-byte D2H
 // per call -- the reference's Thrust reductions synchronise the same way).
 #pragma once
 #include <cmath>
 
 #include "../array1d.h"
+#include "../array2d.h"
 #include "../execution_policy.h"
 
 namespace cusp {
@@ -146,6 +149,30 @@ template <typename X> void max_abs(const X &x, typename X::value_type &value, si
     index = static_cast<size_t>(p);
 }
 
+// ---- gemm: column-major operands given by pointer and pitch ----
+template <typename V> void gemm_loop(size_t m, size_t n, size_t k, const V *A, size_t lda, const V *B, size_t ldb, V *C, size_t ldc)
+{
+    for (size_t c = 0; c < n; c++)
+        for (size_t i = 0; i < m; i++) {
+            V s = V(0);
+            for (size_t j = 0; j < k; j++) s = s + A[j * lda + i] * B[c * ldb + j];
+            C[c * ldc + i] = s;
+        }
+}
+template <typename V> void gemm(size_t m, size_t n, size_t k, const V *A, size_t lda, const V *B, size_t ldb, V *C, size_t ldc, host_memory)
+{ gemm_loop(m, n, k, A, lda, B, ldb, C, ldc); }
+template <typename V> void gemm(size_t m, size_t n, size_t k, const V *A, size_t lda, const V *B, size_t ldb, V *C, size_t ldc, device_memory)
+{
+    if constexpr (cusp::detail::is_real<V>::value) { // the tall-skinny kernel of csrc/dense.hip: the loop's bits
+        cusp::detail::check(by_type<V>(cmi_dense_gemm_f64, cmi_dense_gemm_f32)(m, n, k, A, lda, B, ldb, C, ldc, nullptr));
+    } else { // any other value type: the loop on host copies (set-up convenience)
+        array1d<V, host_memory> a(array1d_view<const V, device_memory>(A, m && k ? (k - 1) * lda + m : 0)), b(array1d_view<const V, device_memory>(B, k && n ? (n - 1) * ldb + k : 0));
+        array1d<V, host_memory> c(array1d_view<const V, device_memory>(C, m && n ? (n - 1) * ldc + m : 0));
+        gemm_loop(m, n, k, a.data(), lda, b.data(), ldb, c.data(), ldc);
+        cusp::detail::raw_copy<V, device_memory, host_memory>::run(C, c.data(), c.size());
+    }
+}
+
 // ---- sharded vectors (cusp/distributed/vector.h): element-wise work on this rank's slice, reductions all-reduced --------------
 // The slice is an array1d_view in the local space, so the loops / kernels above do the work.  Reductions: the local partial as a
 // DOUBLE (device: left in device memory by the library's deterministic two-stage reduction, all-reduced there by RCCL, then the one
@@ -226,6 +253,20 @@ template <typename X> int amax(const X &x) // position of the first entry of lar
     return static_cast<int>(i);
 }
 
+// C <- A B (reference cusp/blas/blas.h gemm).  A, B, C: column_major array2d's or array2d_column_view's in one memory space
+template <typename A2, typename B2, typename C2> void gemm(const A2 &A, const B2 &B, C2 &&C)
+{
+    typedef typename std::remove_reference<C2>::type CT;
+    typedef typename CT::value_type V;
+    static_assert(std::is_same<typename A2::orientation, column_major>::value && std::is_same<typename B2::orientation, column_major>::value &&
+                  std::is_same<typename CT::orientation, column_major>::value, "cusp::blas::gemm takes column_major operands");
+    static_assert(std::is_same<typename A2::memory_space, typename CT::memory_space>::value && std::is_same<typename B2::memory_space, typename CT::memory_space>::value,
+                  "cusp::blas::gemm: the operands live in one memory space");
+    if (A.num_cols != B.num_rows || C.num_rows != A.num_rows || C.num_cols != B.num_cols) throw cusp::invalid_input_exception("cusp::blas::gemm: shapes do not match");
+    const V *a = A.column_pointer(0), *b = B.column_pointer(0);
+    detail::gemm<V>(A.num_rows, B.num_cols, A.num_cols, a, A.pitch, b, B.pitch, C.column_pointer(0), C.pitch, typename CT::memory_space());
+}
+
 // ---- execution-policy overloads (reference cusp/blas/blas.h: every routine also takes a policy first) ----
 // A policy derived from cusp::execution_policy<Derived> reaches a user overload `axpy(my_policy&, ...)` by
 // ADL (testing/blas.cu:752-1208); a policy without one gets the memory-space dispatch above.
@@ -247,6 +288,7 @@ void axpbypcz(D &, const X &x, const Y &y, const Z &z, O &o, S1 a, S2 b, S3 c) {
 template <typename D, typename X, typename = if_policy<D>> typename X::value_type nrm1(D &, const X &x) { return cusp::blas::nrm1(x); }
 template <typename D, typename X, typename = if_policy<D>> typename X::value_type nrmmax(D &, const X &x) { return cusp::blas::nrmmax(x); }
 template <typename D, typename X, typename = if_policy<D>> int amax(D &, const X &x) { return cusp::blas::amax(x); }
+template <typename D, typename A2, typename B2, typename C2, typename = if_policy<D>> void gemm(D &, const A2 &A, const B2 &B, C2 &&C) { cusp::blas::gemm(A, B, C); }
 } // namespace policy_default
 } // namespace detail
 
@@ -278,6 +320,8 @@ template <typename D, typename X> typename X::value_type nrmmax(const cusp::exec
 { using detail::policy_default::nrmmax; return nrmmax(const_cast<D &>(exec.derived()), x); }
 template <typename D, typename X> int amax(const cusp::execution_policy<D> &exec, const X &x)
 { using detail::policy_default::amax; return amax(const_cast<D &>(exec.derived()), x); }
+template <typename D, typename A2, typename B2, typename C2> void gemm(const cusp::execution_policy<D> &exec, const A2 &A, const B2 &B, C2 &&C)
+{ using detail::policy_default::gemm; gemm(const_cast<D &>(exec.derived()), A, B, C); }
 
 } // namespace blas
 } // namespace cusp

@@ -1244,6 +1244,15 @@ int cmi_lobpcg_update_f64(int64_t n, double cx, double cr, double cp, int first,
                           double *x, double *ax, double *r, double *scalars_dev, double *rr_host_mirror, void *workspace, void *stream);
 int cmi_lobpcg_update_f32(int64_t n, float cx, float cr, float cp, int first, float lambda_new, const float *w, const float *aw, float *p, float *ap, float *x,
                           float *ax, float *r, double *scalars_dev, double *rr_host_mirror, void *workspace, void *stream);
+/* The dense product behind cusp::blas::gemm (csrc/dense.hip): C (m x n) <- A (m x k) B (k x n), all three column-major in DEVICE memory with
+ * leading dimensions lda >= m, ldb >= k, ldc >= m; written for m >> k, n (the Ritz vectors E = V S of cusp::eigen::lanczos).
+ * C(i, c) is the chain s = +0; for j = 0 .. k - 1: s = s + A(i, j) B(j, c): one multiply and one add per term, unfused, j ascending -- the
+ * bits of the host triple loop.  k == 0 stores +0; m == 0 or n == 0 is a no-op.  A is read once per group of <= 8 columns of C (one launch
+ * per group); 16-byte loads where every column of A is 16-byte aligned, element loads otherwise; every element of C has one owner (no atomics).
+ * All offsets are 64-bit.  No allocation, no synchronisation.  Refused with CMI_ERROR_INVALID_VALUE before any device call: a negative size;
+ * lda < m, ldb < k or ldc < m for a non-empty operand; a NULL non-empty operand; C overlapping A or B.                                 */
+int cmi_dense_gemm_f64(int64_t m, int64_t n, int64_t k, const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, void *stream);
+int cmi_dense_gemm_f32(int64_t m, int64_t n, int64_t k, const float *A, int64_t lda, const float *B, int64_t ldb, float *C, int64_t ldc, void *stream);
 /* BiCGstab-M; the scalars of the unshifted system are passed by value in T (the header layer forms them on the host, as the reference does).
  * cmi_bicgstab_m_s_*: s_0 <- r_1 + alpha_1 (s_0 - chi_0 As)                                                                     (KERNEL_S)
  * cmi_bicgstab_m_coefficients_*: per shift, from the current zeta_m1, zeta_0, rho_0 (all three only read):
