@@ -31,11 +31,13 @@ from .binding import (  # noqa: F401
     csr_abs_row_sums, ell_abs_row_sums, dia_abs_row_sums, random_fill, blas_scal_recip,
     csr_strength_symmetric, csr_scale_rows, aggregates_fit, csr_elementwise, relax_jacobi_presmooth,
     csr_ring_max, maximal_independent_set, mis_aggregate,
+    spmv_csr_semiring, spmv_coo_semiring, spmv_ell_semiring, spmv_dia_semiring, semiring_op, SEMIRING_OPS,
+    OP_PLUS, OP_MULTIPLIES, OP_MINIMUM, OP_MAXIMUM, OP_PROJECT1ST, OP_PROJECT2ND,
     bfs_levels_per_read, breadth_first_search, pseudo_peripheral_vertex, symmetric_rcm, gather, scatter,
     Comm, OP_SUM, OP_MAX, OP_MIN, csr_column_span,
 )
 from .matrices import (  # noqa: F401
-    CsrMatrix, CooMatrix, EllMatrix, DiaMatrix, HybMatrix, multiply, spgemm, poisson5pt, convert, abs_row_sums, disks_spectral_radius,
+    CsrMatrix, CooMatrix, EllMatrix, DiaMatrix, HybMatrix, multiply, spmv_semiring, spgemm, poisson5pt, convert, abs_row_sums, disks_spectral_radius,
     csr_bytes, ell_bytes, dia_bytes, coo_bytes, fill_x,
 )
 from . import binding, distributed, krylov  # noqa: F401,E402

@@ -275,6 +275,12 @@ def _declare(L):
         getattr(L, f"cmi_relax_jacobi_presmooth_{suf}").argtypes = [i64, vp, vp, real, vp, vp]
     # the maximal independent set and its aggregation (csrc/mis.hip)
     L.cmi_csr_ring_max_u64.argtypes = [i64, i64, vp, vp, vp, vp, vp]
+    # the semiring multiply (csrc/spmv_semiring.hip): ..., x, y0, init_value, combine, reduce, y, stream
+    for suf, sc in (("f64", ctypes.c_double), ("f32", ctypes.c_float)):
+        getattr(L, f"cmi_spmv_csr_semiring_{suf}").argtypes = [i64, i64, i64, vp, vp, vp, vp, vp, sc, i32, i32, vp, vp]
+        getattr(L, f"cmi_spmv_coo_semiring_{suf}").argtypes = [i64, i64, i64, vp, vp, vp, vp, vp, sc, i32, i32, vp, vp]
+        getattr(L, f"cmi_spmv_ell_semiring_{suf}").argtypes = [i64, i64, i64, i64, vp, vp, vp, vp, sc, i32, i32, vp, vp]
+        getattr(L, f"cmi_spmv_dia_semiring_{suf}").argtypes = [i64, i64, i64, i64, vp, vp, vp, vp, sc, i32, i32, vp, vp]
     L.cmi_csr_maximal_independent_set.argtypes = [i64, i64, vp, vp, c_int, ctypes.c_uint64, vp, POINTER(c_int64), POINTER(c_int), vp]
     L.cmi_csr_mis_aggregate.argtypes = [i64, i64, vp, vp, ctypes.c_uint64, vp, vp, POINTER(c_int64), vp]
     # breadth-first search, pseudo-peripheral vertex, level ordering, gather / scatter (csrc/bfs.hip)
@@ -927,6 +933,74 @@ def spmv_coo(num_rows, num_cols, Ai, Aj, Ax, x, y, accumulate=False, cfg=None, s
     fn = getattr(lib(), "cmi_spmv_coo_" + _suffix(y))
     check(fn(num_rows, num_cols, Ax.numel(), _ptr(Ai), _ptr(Aj), _ptr(Ax), _ptr(x), _ptr(y), int(bool(accumulate)),
              _cfg(cfg), _stream(stream)))
+
+
+# ---- the semiring multiply (cmi_spmv_*_semiring_*): y[i] = the chain of row i under (combine, reduce), started from y0[i] or init ----
+OP_PLUS, OP_MULTIPLIES, OP_MINIMUM, OP_MAXIMUM, OP_PROJECT1ST, OP_PROJECT2ND = range(6)
+SEMIRING_OPS = {"plus": OP_PLUS, "multiplies": OP_MULTIPLIES, "minimum": OP_MINIMUM, "maximum": OP_MAXIMUM, "project1st": OP_PROJECT1ST,
+                "project2nd": OP_PROJECT2ND}
+
+
+def semiring_op(op):
+    """cmi_op of a name ("plus", ..., "project2nd") or of an integer (handed on as it is: the library refuses what it does not know)."""
+    if isinstance(op, str):
+        if op not in SEMIRING_OPS:
+            raise ValueError(f"unknown operation {op!r}: one of {sorted(SEMIRING_OPS)}")
+        return SEMIRING_OPS[op]
+    return int(op)
+
+
+def _semiring_operands(who, y, index, values, x, y0, num_cols):
+    """Checks shared by the four wrappers: tensors that may be None (streams the operations do not read), dtypes, the vectors' lengths."""
+    import torch
+    for t, n in index:
+        _need(t, n, torch.int32)
+    for t, n in (*values, (x, "x"), (y0, "y0"), (y, "y")):
+        _need(t, n, y.dtype)
+    if (x is not None and x.numel() != num_cols) or (y0 is not None and y0.numel() != y.numel()):
+        raise ValueError(f"{who}: vector lengths do not match the matrix shape")
+
+
+def spmv_csr_semiring(num_rows, num_cols, Ap, Aj, Ax, x, y, combine, reduce, y0=None, init=0.0, num_entries=None, stream=None):
+    """cmi_spmv_csr_semiring_*.  Ax may be None with project2nd, Aj and x with project1st; y0=None starts every row from `init`."""
+    _semiring_operands("spmv_csr_semiring", y, ((Ap, "Ap"), (Aj, "Aj")), ((Ax, "Ax"),), x, y0, num_cols)
+    if Ap.numel() != num_rows + 1 or y.numel() != num_rows or (Aj is not None and Ax is not None and Aj.numel() != Ax.numel()):
+        raise ValueError("spmv_csr_semiring: array lengths do not match the matrix shape")
+    if num_entries is None:
+        num_entries = (Aj if Aj is not None else Ax).numel()
+    fn = getattr(lib(), "cmi_spmv_csr_semiring_" + _suffix(y))
+    check(fn(num_rows, num_cols, num_entries, _ptr(Ap), _ptr(Aj), _ptr(Ax), _ptr(x), _ptr(y0), float(init), semiring_op(combine), semiring_op(reduce),
+             _ptr(y), _stream(stream)))
+
+
+def spmv_coo_semiring(num_rows, num_cols, Ai, Aj, Ax, x, y, combine, reduce, y0=None, init=0.0, stream=None):
+    """cmi_spmv_coo_semiring_*: entries sorted by row.  Ax may be None with project2nd, Aj and x with project1st."""
+    _semiring_operands("spmv_coo_semiring", y, ((Ai, "Ai"), (Aj, "Aj")), ((Ax, "Ax"),), x, y0, num_cols)
+    if y.numel() != num_rows or any(t is not None and t.numel() != Ai.numel() for t in (Aj, Ax)):
+        raise ValueError("spmv_coo_semiring: array lengths do not match the matrix shape")
+    fn = getattr(lib(), "cmi_spmv_coo_semiring_" + _suffix(y))
+    check(fn(num_rows, num_cols, Ai.numel(), _ptr(Ai), _ptr(Aj), _ptr(Ax), _ptr(x), _ptr(y0), float(init), semiring_op(combine), semiring_op(reduce),
+             _ptr(y), _stream(stream)))
+
+
+def spmv_ell_semiring(num_rows, num_cols, width, pitch, Aj, Ax, x, y, combine, reduce, y0=None, init=0.0, stream=None):
+    """cmi_spmv_ell_semiring_*: slots ascending, column -1 skipped.  Ax may be None with project2nd, x with project1st."""
+    _semiring_operands("spmv_ell_semiring", y, ((Aj, "Aj"),), ((Ax, "Ax"),), x, y0, num_cols)
+    if y.numel() != num_rows or any(t is not None and t.numel() < width * pitch for t in (Aj, Ax)):
+        raise ValueError("spmv_ell_semiring: array lengths do not match the matrix shape")
+    fn = getattr(lib(), "cmi_spmv_ell_semiring_" + _suffix(y))
+    check(fn(num_rows, num_cols, width, pitch, _ptr(Aj), _ptr(Ax), _ptr(x), _ptr(y0), float(init), semiring_op(combine), semiring_op(reduce), _ptr(y),
+             _stream(stream)))
+
+
+def spmv_dia_semiring(num_rows, num_cols, num_diagonals, pitch, offsets, values, x, y, combine, reduce, y0=None, init=0.0, stream=None):
+    """cmi_spmv_dia_semiring_*: every in-range slot takes part, stored zeros included.  values may be None with project2nd, x with project1st."""
+    _semiring_operands("spmv_dia_semiring", y, ((offsets, "offsets"),), ((values, "values"),), x, y0, num_cols)
+    if y.numel() != num_rows or offsets.numel() != num_diagonals or (values is not None and values.numel() < num_diagonals * pitch):
+        raise ValueError("spmv_dia_semiring: array lengths do not match the matrix shape")
+    fn = getattr(lib(), "cmi_spmv_dia_semiring_" + _suffix(y))
+    check(fn(num_rows, num_cols, num_diagonals, pitch, _ptr(offsets), _ptr(values), _ptr(x), _ptr(y0), float(init), semiring_op(combine),
+             semiring_op(reduce), _ptr(y), _stream(stream)))
 
 
 def spmv_ell(num_rows, num_cols, width, pitch, Aj, Ax, x, y, row_lengths=None, accumulate=False, cfg=None,

@@ -8,9 +8,16 @@
 //   device_memory : forwards to the MI355X C-ABI (cmi_spmv_{csr,coo,ell,dia,hyb}_{f64,f32}): hand-written
 //                   gfx950 kernels, launch shape from the persisted tuning table.  NEVER falls back to the
 //                   host: a functor combination the kernels do not implement throws
-//                   cusp::not_implemented_exception.  Supported on the device: combine = multiplies,
-//                   reduce = plus, initialize = constant_functor(0) (y = A x) or identity_function
-//                   (y = y + A x) -- exactly the combinations the reference's own multiply / hyb path use.
+//                   cusp::not_implemented_exception.  combine = multiplies, reduce = plus with
+//                   initialize = constant_functor(0) (y = A x) or identity_function (y = y + A x) -- the
+//                   combinations the reference's own multiply / hyb path use -- run the plans and tuned kernels.
+//                   Every other combination of the NAMED functors of cusp/functional.h (combine: plus,
+//                   multiplies, minimum, maximum, project1st, project2nd; reduce: the first four; initialize:
+//                   identity_function or constant_functor of any value) runs the semiring kernels
+//                   (cmi_spmv_*_semiring_*): one chain per row in the format's own order, the host loops' bits;
+//                   HYB in two launches; a coo_matrix (and HYB's COO part) must be sorted by row --
+//                   cusp::not_implemented_exception naming sort_by_row() otherwise.  A functor type the library
+//                   does not know (a user's struct) throws.
 //
 // x and y may be any contiguous vector type of the matrix's memory space with data()/size():
 // cusp::array1d, cusp::array1d_view, or a solver's temporary (the reference's CG passes
@@ -223,6 +230,85 @@ template <typename A, typename X, typename Y> void device_multiply(const A &a, c
                                                          x.data(), y.data(), acc, nullptr, nullptr, stream)); // (no configuration for either part: the tuning table's)
 }
 
+// ---- device dispatch of the NAMED functors (the semiring multiply, cmi_spmv_*_semiring_*) ---------------------------
+// functor type -> cmi_op; -1: a type the library does not know (a user's struct), which the device route refuses
+template <typename V, typename F> struct semiring_op : std::integral_constant<int, -1> {};
+template <typename V> struct semiring_op<V, plus<V>> : std::integral_constant<int, CMI_OP_PLUS> {};
+template <typename V> struct semiring_op<V, multiplies<V>> : std::integral_constant<int, CMI_OP_MULTIPLIES> {};
+template <typename V> struct semiring_op<V, minimum<V>> : std::integral_constant<int, CMI_OP_MINIMUM> {};
+template <typename V> struct semiring_op<V, maximum<V>> : std::integral_constant<int, CMI_OP_MAXIMUM> {};
+template <typename V> struct semiring_op<V, project1st<V>> : std::integral_constant<int, CMI_OP_PROJECT1ST> {};
+template <typename V> struct semiring_op<V, project2nd<V>> : std::integral_constant<int, CMI_OP_PROJECT2ND> {};
+// initialize -> (does the chain start from y[i]?, the constant it starts from otherwise)
+template <typename V, typename I> struct semiring_init : std::false_type {};
+template <typename V> struct semiring_init<V, identity_function<V>> : std::true_type {
+    static bool from_y(const identity_function<V> &) { return true; }
+    static V constant(const identity_function<V> &) { return V(0); }
+};
+template <typename V> struct semiring_init<V, constant_functor<V>> : std::true_type {
+    static bool from_y(const constant_functor<V> &) { return false; }
+    static V constant(const constant_functor<V> &f) { return f.value; }
+};
+// a (combine, reduce) pair the semiring kernels run: any named combine, a named reduce that is no projection
+template <typename V, typename C, typename R> struct semiring_pair
+    : std::integral_constant<bool, (semiring_op<V, C>::value >= 0) && (semiring_op<V, R>::value >= 0) && (semiring_op<V, R>::value <= CMI_OP_MAXIMUM)> {};
+// ... and the one pair that has tuned kernels and plans of its own
+template <typename V, typename C, typename R> struct arithmetic_pair
+    : std::integral_constant<bool, std::is_same<C, multiplies<V>>::value && std::is_same<R, plus<V>>::value> {};
+
+template <typename A> void require_row_sorted(const A &coo, void *stream)
+{
+    if (coo.num_entries == 0) return;
+    int sorted = 0;
+    check(cmi_coo_is_sorted((int64_t)coo.num_rows, (int64_t)coo.num_entries, coo.row_indices.data(), nullptr, 0, &sorted, stream));
+    if (!sorted)
+        throw cusp::not_implemented_exception("cusp::multiply on device_memory with these functors needs a coo_matrix whose entries are sorted by row: call sort_by_row() first");
+}
+
+// y[i] = the chain of row i started from y0[i] (y0 != nullptr) or from `init`; the operands of cmi_spmv_*_semiring_*
+template <typename A, typename X, typename V, typename Y> void device_semiring(const A &a, const X &x, const V *y0, V init, int comb, int red, Y &y, void *stream, csr_format)
+{
+    check(by_type<V>(cmi_spmv_csr_semiring_f64, cmi_spmv_csr_semiring_f32)(a.num_rows, a.num_cols, a.num_entries, a.row_offsets.data(), a.column_indices.data(), a.values.data(),
+                                                                           x.data(), y0, init, comb, red, y.data(), stream));
+}
+template <typename A, typename X, typename V, typename Y> void device_semiring_sorted_coo(const A &a, const X &x, const V *y0, V init, int comb, int red, Y &y, void *stream)
+{
+    check(by_type<V>(cmi_spmv_coo_semiring_f64, cmi_spmv_coo_semiring_f32)(a.num_rows, a.num_cols, a.num_entries, a.row_indices.data(), a.column_indices.data(), a.values.data(),
+                                                                           x.data(), y0, init, comb, red, y.data(), stream));
+}
+template <typename A, typename X, typename V, typename Y> void device_semiring(const A &a, const X &x, const V *y0, V init, int comb, int red, Y &y, void *stream, coo_format)
+{
+    require_row_sorted(a, stream);
+    device_semiring_sorted_coo(a, x, y0, init, comb, red, y, stream);
+}
+template <typename A, typename X, typename V, typename Y> void device_semiring(const A &a, const X &x, const V *y0, V init, int comb, int red, Y &y, void *stream, ell_format)
+{
+    if (a.column_indices.pitch != a.values.pitch) throw cusp::invalid_input_exception("ell_matrix: column_indices.pitch != values.pitch");
+    check(by_type<V>(cmi_spmv_ell_semiring_f64, cmi_spmv_ell_semiring_f32)(a.num_rows, a.num_cols, a.column_indices.num_cols, a.column_indices.pitch, data_of(a.column_indices),
+                                                                           data_of(a.values), x.data(), y0, init, comb, red, y.data(), stream));
+}
+template <typename A, typename X, typename V, typename Y> void device_semiring(const A &a, const X &x, const V *y0, V init, int comb, int red, Y &y, void *stream, dia_format)
+{
+    check(by_type<V>(cmi_spmv_dia_semiring_f64, cmi_spmv_dia_semiring_f32)(a.num_rows, a.num_cols, a.values.num_cols, a.values.pitch, a.diagonal_offsets.data(), data_of(a.values),
+                                                                           x.data(), y0, init, comb, red, y.data(), stream));
+}
+// HYB: the ELL part with the caller's start, then the COO part on top of what the first call left (hyb_spmv.h:55-56): two launches
+template <typename A, typename X, typename V, typename Y> void device_semiring(const A &a, const X &x, const V *y0, V init, int comb, int red, Y &y, void *stream, hyb_format)
+{
+    require_row_sorted(a.coo, stream);
+    device_semiring(a.ell, x, y0, init, comb, red, y, stream, ell_format());
+    device_semiring_sorted_coo(a.coo, x, static_cast<const V *>(y.data()), V(0), comb, red, y, stream);
+}
+template <typename A, typename X, typename Y, typename I, typename C, typename R>
+void device_semiring_multiply(const A &a, const X &x, Y &y, const I &init, void *stream)
+{
+    require_int_index<A>();
+    typedef typename Y::value_type V;
+    static_assert(std::is_same<typename A::value_type, V>::value, "cusp::multiply on device_memory: the matrix and y must have the same value type");
+    const V *y0 = semiring_init<V, I>::from_y(init) ? static_cast<const V *>(y.data()) : nullptr;
+    device_semiring(a, x, y0, semiring_init<V, I>::constant(init), semiring_op<V, C>::value, semiring_op<V, R>::value, y, stream, typename A::format());
+}
+
 // host adaptor: containers expose operator[] / data; give ELL/DIA a data_ptr() view for the loops
 template <typename M> struct host_ell_adaptor {
     const M &m;
@@ -275,6 +361,15 @@ template <typename A, typename X, typename Y, typename I, typename C, typename R
 void multiply_in_space(const A &a, const X &x, Y &y, I init, C comb, R red, void *stream, device_memory)
 {
     typedef typename Y::value_type V;
+    if constexpr (semiring_pair<V, C, R>::value && semiring_init<V, I>::value) {
+        // (constant 0 | identity, multiplies, plus): the plans and tuned kernels, as ever.  Every other named combination -- a constant other
+        // than zero among them -- runs the semiring kernels: one chain per row, in the format's own order.
+        const bool tuned = arithmetic_pair<V, C, R>::value && (semiring_init<V, I>::from_y(init) || semiring_init<V, I>::constant(init) == V(0));
+        if (!tuned) {
+            device_semiring_multiply<A, X, Y, I, C, R>(a, x, y, init, stream);
+            return;
+        }
+    }
     const int acc = device_functors<V, I, C, R>::accumulate(init);
     device_multiply(a, x, y, acc, stream, typename A::format());
 }
@@ -619,12 +714,34 @@ void multiply(const cusp::omp::execution_policy &exec, const LinearOperator &A, 
 }
 
 // z = y + A*x (reference cusp/multiply.h:301,377 generalized_spmv with combine = *, reduce = +)
+// device_memory vectors with a named pair other than (multiplies, plus): row i's chain starts from y[i] and is stored to z[i] by the semiring
+// kernels, without a copy of y.  (multiplies, plus) keeps the copy and the tuned kernels.
+namespace detail {
+template <typename A, typename X, typename Z, typename C, typename R, typename = void> struct semiring_generalized : std::false_type {};
+template <typename A, typename X, typename Z, typename C, typename R>
+struct semiring_generalized<A, X, Z, C, R, typename std::enable_if<has_format<A>::value && std::is_same<typename Z::memory_space, device_memory>::value>::type>
+    : std::integral_constant<bool, semiring_pair<typename Z::value_type, C, R>::value && !arithmetic_pair<typename Z::value_type, C, R>::value && !is_block<X>::value &&
+                                       !is_sparse<X>::value && !is_block<Z>::value && !is_sparse<Z>::value> {};
+} // namespace detail
 template <typename LinearOperator, typename Vector1, typename Vector2, typename Vector3, typename BinaryFunction1, typename BinaryFunction2>
 void generalized_spmv(const LinearOperator &A, const Vector1 &x, const Vector2 &y, Vector3 &z, BinaryFunction1 combine, BinaryFunction2 reduce)
 {
     typedef typename Vector3::value_type V;
-    if (static_cast<const void *>(y.data()) != static_cast<const void *>(z.data())) cusp::copy_array(y, z);
-    cusp::multiply(A, x, z, identity_function<V>(), combine, reduce);
+    if constexpr (detail::semiring_generalized<LinearOperator, Vector1, Vector3, BinaryFunction1, BinaryFunction2>::value) {
+        static_assert(std::is_same<typename LinearOperator::memory_space, device_memory>::value && std::is_same<typename Vector1::memory_space, device_memory>::value &&
+                          std::is_same<typename Vector2::memory_space, device_memory>::value && std::is_same<typename Vector2::value_type, V>::value &&
+                          std::is_same<typename LinearOperator::value_type, V>::value,
+                      "cusp::generalized_spmv: A, x, y and z must live in the same memory space and have the same value type");
+        detail::require_int_index<LinearOperator>();
+        detail::check_shapes(A, x, z);
+        if (y.size() != z.size()) throw cusp::invalid_input_exception("cusp::generalized_spmv: y and z differ in length");
+        if (A.num_rows == 0) return;
+        detail::device_semiring(A, x, static_cast<const V *>(y.data()), V(0), detail::semiring_op<V, BinaryFunction1>::value, detail::semiring_op<V, BinaryFunction2>::value, z,
+                                nullptr, typename LinearOperator::format());
+    } else {
+        if (static_cast<const void *>(y.data()) != static_cast<const void *>(z.data())) cusp::copy_array(y, z);
+        cusp::multiply(A, x, z, identity_function<V>(), combine, reduce);
+    }
 }
 
 } // namespace cusp

@@ -221,6 +221,37 @@ def multiply(A, x, y, accumulate=False, cfg=None, stream=None):
     return y
 
 
+def spmv_semiring(A, x, y, combine="multiplies", reduce="plus", init=None, stream=None):
+    """The functor overload of cusp::multiply for the named operations: y[i] = the chain of row i,
+        s = y[i] (init=None) or init;  for each entry of the row in the format's own order:  s = reduce(s, combine(A_ij, x_j)),
+    through cmi_spmv_*_semiring_* (one lane per chain, the host loops' bits).  combine: "plus", "multiplies", "minimum", "maximum",
+    "project1st" (the matrix value), "project2nd" (the vector value); reduce: the first four.  A CooMatrix -- and the COO part of a
+    HybMatrix -- must be sorted by row (ValueError naming sort_by_row() otherwise).  HYB is two launches: the ELL part, then the COO part
+    on top of it."""
+    y0 = y if init is None else None
+    init = 0.0 if init is None else init
+    if isinstance(A, CsrMatrix):
+        B.spmv_csr_semiring(A.num_rows, A.num_cols, A.row_offsets, A.column_indices, A.values, x, y, combine, reduce, y0, init, stream=stream)
+    elif isinstance(A, CooMatrix):
+        if A.num_entries > 0 and not A.is_sorted_by_row(stream):
+            raise ValueError("spmv_semiring: the entries of a CooMatrix must be sorted by row; call sort_by_row() first")
+        B.spmv_coo_semiring(A.num_rows, A.num_cols, A.row_indices, A.column_indices, A.values, x, y, combine, reduce, y0, init, stream)
+    elif isinstance(A, EllMatrix):
+        B.spmv_ell_semiring(A.num_rows, A.num_cols, A.num_entries_per_row, A.pitch, A.column_indices, A.values, x, y, combine, reduce, y0, init, stream)
+    elif isinstance(A, DiaMatrix):
+        B.spmv_dia_semiring(A.num_rows, A.num_cols, A.diagonal_offsets.numel(), A.pitch, A.diagonal_offsets, A.values, x, y, combine, reduce, y0, init,
+                            stream)
+    elif isinstance(A, HybMatrix):
+        e, c = A.ell, A.coo
+        if c.num_entries > 0 and not c.is_sorted_by_row(stream):
+            raise ValueError("spmv_semiring: the COO part of a HybMatrix must be sorted by row; call A.coo.sort_by_row() first")
+        B.spmv_ell_semiring(A.num_rows, A.num_cols, e.num_entries_per_row, e.pitch, e.column_indices, e.values, x, y, combine, reduce, y0, init, stream)
+        B.spmv_coo_semiring(A.num_rows, A.num_cols, c.row_indices, c.column_indices, c.values, x, y, combine, reduce, y, 0.0, stream)
+    else:
+        raise TypeError(f"spmv_semiring: unsupported matrix type {type(A).__name__}")
+    return y
+
+
 def spgemm(A, B_, stream=None):
     """C = A B for two sparse matrices (the three-matrix cusp::multiply; cmi_spgemm_csr_*): CSR operands on the device, or on
     the host (copied to the current device and the product copied back); COO operands go through convert(.., "csr").

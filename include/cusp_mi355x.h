@@ -835,6 +835,65 @@ int cmi_spmv_coo_dot_plan_f64(const cmi_plan *plan, const int32_t *Ai, const int
 int cmi_spmv_coo_dot_plan_f32(const cmi_plan *plan, const int32_t *Ai, const int32_t *Aj, const float *Ax, const float *x,
                               float *y, const float *w, double *dot_dev, void *workspace, void *stream);
 
+/* The semiring multiply (spmv_semiring.hip): what cusp::multiply(A, x, y, initialize, combine, reduce) means
+ * for the named functors of cusp/functional.h, on the device.  For every row i, in the matrix's value type, one rounding
+ * per operation, nothing contracted:
+ *     s = y0 ? y0[i] : init_value;  for each entry of row i in the format's own order: s = reduce(s, combine(A_ij, x_j));  y[i] = s
+ * The format's own order is the host loops' (cusp::detail::host_multiply): CSR storage order; COO the row's entries in
+ * storage order; ELL slots ascending, a slot with column -1 skipped; DIA diagonals in storage order, every in-range slot
+ * taking part, stored zeros included.  A row without entries gets its initial value.  HYB is two calls: the ELL part, then
+ * the COO part with y0 = y.
+ *   combine: any cmi_op, called as combine(matrix value, vector value).  reduce: PLUS, MULTIPLIES, MINIMUM or MAXIMUM,
+ *   called as reduce(running value, new term).  MINIMUM is a < b ? a : b and MAXIMUM is a < b ? b : a (thrust's): with a NaN
+ *   or a signed zero in a row the chain depends on its order, so ONE lane runs a row's whole chain and no partial results
+ *   are ever joined; a long row is a long serial chain.
+ *   y0 == NULL: every row starts from init_value (any value, +-inf and NaN included); otherwise from y0[i].  y0 may be y
+ *   itself (a lane reads its own element before it writes it) or x.  y must not overlap x.
+ *   Streams the operations do not need are not read and may be NULL: with PROJECT2ND the matrix values; with PROJECT1ST x
+ *   and, for CSR and COO, the column indices (ELL reads them to know its padding).
+ *   COO: the entries must be sorted by row (cmi_coo_sort_by_row_*, stable), as the reference's device multiply requires;
+ *   the row lane finds its segment by a binary search in Ai.  On unsorted entries the chains are unspecified; row indices
+ *   are only compared, never used as addresses.  ELL has no row_lengths operand.  ELL skips a slot with column -1 as the host
+ *   loop does and, unlike the host loop, also a slot with any other column outside [0, num_cols): malformed input gives another
+ *   result than on the host, never an address outside x.
+ * Refused with CMI_ERROR_INVALID_VALUE before any device call: an operation outside the enum or a projection as reduce,
+ * negative sizes, sizes beyond the CSR ceiling (rows, cols <= INT32_MAX, entries / slots per row / diagonals
+ * <= INT32_MAX - 65536), a pitch below num_rows, a null array that the chosen operations read, y overlapping x.
+ * num_rows == 0: success, nothing launched.  No allocation, no synchronisation, no atomics; the launch shape comes from the
+ * sizes alone.  Callers find the feature by the symbols (CMI_VERSION is unchanged). */
+typedef enum cmi_op {
+    CMI_OP_PLUS = 0,       /* a + b */
+    CMI_OP_MULTIPLIES = 1, /* a * b */
+    CMI_OP_MINIMUM = 2,    /* a < b ? a : b */
+    CMI_OP_MAXIMUM = 3,    /* a < b ? b : a */
+    CMI_OP_PROJECT1ST = 4, /* a: the matrix value (combine only) */
+    CMI_OP_PROJECT2ND = 5  /* b: the vector value (combine only) */
+} cmi_op;
+int cmi_spmv_csr_semiring_f64(int64_t num_rows, int64_t num_cols, int64_t num_entries, const int32_t *Ap, const int32_t *Aj,
+                              const double *Ax, const double *x, const double *y0, double init_value, int combine, int reduce,
+                              double *y, void *stream);
+int cmi_spmv_csr_semiring_f32(int64_t num_rows, int64_t num_cols, int64_t num_entries, const int32_t *Ap, const int32_t *Aj,
+                              const float *Ax, const float *x, const float *y0, float init_value, int combine, int reduce, float *y,
+                              void *stream);
+int cmi_spmv_ell_semiring_f64(int64_t num_rows, int64_t num_cols, int64_t num_entries_per_row, int64_t pitch, const int32_t *Aj,
+                              const double *Ax, const double *x, const double *y0, double init_value, int combine, int reduce,
+                              double *y, void *stream);
+int cmi_spmv_ell_semiring_f32(int64_t num_rows, int64_t num_cols, int64_t num_entries_per_row, int64_t pitch, const int32_t *Aj,
+                              const float *Ax, const float *x, const float *y0, float init_value, int combine, int reduce, float *y,
+                              void *stream);
+int cmi_spmv_dia_semiring_f64(int64_t num_rows, int64_t num_cols, int64_t num_diagonals, int64_t pitch,
+                              const int32_t *diagonal_offsets, const double *values, const double *x, const double *y0,
+                              double init_value, int combine, int reduce, double *y, void *stream);
+int cmi_spmv_dia_semiring_f32(int64_t num_rows, int64_t num_cols, int64_t num_diagonals, int64_t pitch,
+                              const int32_t *diagonal_offsets, const float *values, const float *x, const float *y0,
+                              float init_value, int combine, int reduce, float *y, void *stream);
+int cmi_spmv_coo_semiring_f64(int64_t num_rows, int64_t num_cols, int64_t num_entries, const int32_t *Ai, const int32_t *Aj,
+                              const double *Ax, const double *x, const double *y0, double init_value, int combine, int reduce,
+                              double *y, void *stream);
+int cmi_spmv_coo_semiring_f32(int64_t num_rows, int64_t num_cols, int64_t num_entries, const int32_t *Ai, const int32_t *Aj,
+                              const float *Ax, const float *x, const float *y0, float init_value, int combine, int reduce, float *y,
+                              void *stream);
+
 /* HYB = ELL part (caller's accumulate) then COO part accumulating on top
  * (generic/multiply/spmv.h:275-290; oracle sequential/multiply/hyb_spmv.h:42-57).
  * cfg_ell / cfg_coo may be NULL. */
