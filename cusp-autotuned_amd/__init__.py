@@ -29,7 +29,7 @@ from .binding import (  # noqa: F401
     pcg_update_jacobi, pcg_direction_x_jacobi, bicgstab_s, bicgstab_xr, bicgstab_p, cr_xr, cr_py,
     cg_m_coefficients, cg_m_update_xp, bicgstab_m_s, bicgstab_m_coefficients, bicgstab_m_update_xs, lobpcg_residual, lobpcg_gram, lobpcg_update, dense_gemm,
     csr_abs_row_sums, ell_abs_row_sums, dia_abs_row_sums, random_fill, blas_scal_recip,
-    csr_strength_symmetric, csr_scale_rows, aggregates_fit, csr_elementwise, relax_jacobi_presmooth,
+    csr_strength_symmetric, csr_transpose_positions, csr_masked_product, csr_evolution_strength, csr_scale_rows, aggregates_fit, csr_elementwise, relax_jacobi_presmooth,
     csr_ring_max, maximal_independent_set, mis_aggregate,
     spmv_csr_semiring, spmv_coo_semiring, spmv_ell_semiring, spmv_dia_semiring, semiring_op, SEMIRING_OPS,
     OP_PLUS, OP_MULTIPLIES, OP_MINIMUM, OP_MAXIMUM, OP_PROJECT1ST, OP_PROJECT2ND,

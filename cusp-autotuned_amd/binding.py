@@ -273,6 +273,11 @@ def _declare(L):
         getattr(L, f"cmi_aggregates_fit_{suf}").argtypes = [i64, i64, vp, vp, vp, vp, vp, i64, vp, vp]
         getattr(L, f"cmi_csr_elementwise_{suf}").argtypes = [i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, c_int, vp, vp, vp, i64, POINTER(c_int), vp]
         getattr(L, f"cmi_relax_jacobi_presmooth_{suf}").argtypes = [i64, vp, vp, real, vp, vp]
+    # evolution strength of connection (csrc/evolution.hip)
+    L.cmi_csr_transpose_positions.argtypes = [i64, vp, vp, vp, POINTER(c_int), vp]
+    for suf in ("f64", "f32"):
+        getattr(L, f"cmi_csr_masked_product_{suf}").argtypes = [i64, vp, vp, vp, vp, vp, vp]
+        getattr(L, f"cmi_csr_evolution_strength_{suf}").argtypes = [i64, i64, vp, vp, vp, vp, c_double, c_double, vp, vp, vp, i64, POINTER(c_int), vp]
     # the maximal independent set and its aggregation (csrc/mis.hip)
     L.cmi_csr_ring_max_u64.argtypes = [i64, i64, vp, vp, vp, vp, vp]
     # the semiring multiply (csrc/spmv_semiring.hip): ..., x, y0, init_value, combine, reduce, y, stream
@@ -460,6 +465,60 @@ def csr_strength_symmetric(num_rows, Ap, Aj, Ax, theta=0.0, stream=None):
     Sx = torch.empty(nnz, dtype=Ax.dtype, device=Ax.device)
     check(getattr(lib(), "cmi_csr_strength_symmetric_" + _suffix(Ax))(num_rows, num_rows, nnz, _ptr(Ap), _ptr(Aj), _ptr(Ax), float(theta), _ptr(Sp),
                                                                       _ptr(Sj), _ptr(Sx), nnz, _stream(stream)))
+    kept = int(Sp[num_rows].item())
+    return Sp, Sj[:kept].clone(), Sx[:kept].clone()
+
+
+def csr_transpose_positions(num_rows, Ap, Aj, stream=None):
+    """cmi_csr_transpose_positions: tpos[e] = the position of the entry (col(e), row(e)) of a square CSR pattern.  Returns tpos,
+    or None when the pattern does not conform (not symmetric, a row not strictly ascending, a column outside the matrix)."""
+    import torch
+    for t, nm in ((Ap, "Ap"), (Aj, "Aj")):
+        _need(t, nm, torch.int32)
+    if Ap.numel() != num_rows + 1:
+        raise ValueError("csr_transpose_positions: array lengths do not match the matrix shape")
+    tpos = torch.empty(Aj.numel(), dtype=torch.int32, device=Aj.device)
+    ok = c_int(0)
+    check(lib().cmi_csr_transpose_positions(num_rows, _ptr(Ap), _ptr(Aj), _ptr(tpos), byref(ok), _stream(stream)))
+    return tpos if ok.value else None
+
+
+def csr_masked_product(num_rows, Ap, Aj, Vx, Wx, out=None, stream=None):
+    """cmi_csr_masked_product_*: out[e] = the sum of Vx[p] * Wx[q] over the columns that rows row(e) and col(e) have in common,
+    in ascending column order from +0.  Returns out (a new tensor unless given)."""
+    import torch
+    for t, nm in ((Ap, "Ap"), (Aj, "Aj")):
+        _need(t, nm, torch.int32)
+    if out is None:
+        out = torch.empty_like(Vx)
+    for t, nm in ((Vx, "Vx"), (Wx, "Wx"), (out, "out")):
+        _need(t, nm, Vx.dtype)
+    if Ap.numel() != num_rows + 1 or not (Aj.numel() == Vx.numel() == Wx.numel() == out.numel()):
+        raise ValueError("csr_masked_product: array lengths do not match the matrix shape")
+    check(getattr(lib(), "cmi_csr_masked_product_" + _suffix(Vx))(num_rows, _ptr(Ap), _ptr(Aj), _ptr(Vx), _ptr(Wx), _ptr(out), _stream(stream)))
+    return out
+
+
+def csr_evolution_strength(num_rows, Ap, Aj, Ax, B_, rho_DinvA, epsilon=4.0, stream=None):
+    """cmi_csr_evolution_strength_*: the evolution measure of the square CSR matrix A for the candidate vector B and a given
+    non-zero rho(D^-1 A).  Returns (Sp, Sj, Sx), the kept entries in storage order with their final values, or None when the
+    pattern does not conform (see csr_transpose_positions)."""
+    import torch
+    for t, nm in ((Ap, "Ap"), (Aj, "Aj")):
+        _need(t, nm, torch.int32)
+    _need(Ax, "Ax")
+    _need(B_, "B", Ax.dtype)
+    if Ap.numel() != num_rows + 1 or Aj.numel() != Ax.numel() or B_.numel() != num_rows:
+        raise ValueError("csr_evolution_strength: array lengths do not match the matrix shape")
+    nnz = Aj.numel()
+    Sp = torch.empty(num_rows + 1, dtype=torch.int32, device=Ax.device)
+    Sj = torch.empty(nnz, dtype=torch.int32, device=Ax.device)
+    Sx = torch.empty(nnz, dtype=Ax.dtype, device=Ax.device)
+    ok = c_int(0)
+    check(getattr(lib(), "cmi_csr_evolution_strength_" + _suffix(Ax))(num_rows, nnz, _ptr(Ap), _ptr(Aj), _ptr(Ax), _ptr(B_), float(rho_DinvA), float(epsilon),
+                                                                      _ptr(Sp), _ptr(Sj), _ptr(Sx), nnz, byref(ok), _stream(stream)))
+    if not ok.value:
+        return None
     kept = int(Sp[num_rows].item())
     return Sp, Sj[:kept].clone(), Sx[:kept].clone()
 

@@ -1,4 +1,4 @@
-// amg_shared.h -- what the set-up translation units of smoothed aggregation (amg.hip, mis.hip) and the graph searches (bfs.hip)
+// amg_shared.h -- what the set-up translation units of smoothed aggregation (amg.hip, evolution.hip, mis.hip) and the graph searches (bfs.hip)
 // share: the size ceiling, the launch shape of one lane per row, the clamp of a row offset and the one-allocation scratch arena.
 #pragma once
 #include "setup_scan.h"

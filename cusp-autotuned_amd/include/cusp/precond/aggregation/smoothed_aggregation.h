@@ -13,7 +13,11 @@
 // smoother (the reference passes it by value and so estimates it twice).
 // mis_aggregation (public, false by default): set it on a default-constructed object before initialize(A) to aggregate every
 // level with mis_aggregate instead of standard_aggregate; the cross-space constructor copies it.
-// Not built: evolution strength, other smoothers, several candidate vectors, a sharded hierarchy.
+// evolution_strength (public, false by default) with evolution_epsilon (4): set them the same way to take every level's strength
+// matrix from evolution_strength_of_connection(A, C, B, rho_DinvA, evolution_epsilon) instead of the symmetric measure; the
+// level's rho is then estimated before the strength step (still once per level) and theta is not used.  Combines with
+// mis_aggregation.  With the flag clear the order of calls and every bit are what they were.
+// Not built: other smoothers, several candidate vectors, a sharded hierarchy.
 #pragma once
 #include "../../detail/multilevel.h"
 #include "../smoother/jacobi_smoother.h"
@@ -46,6 +50,8 @@ class smoothed_aggregation
 public:
     double theta = 0.0;
     bool mis_aggregation = false; // aggregate with mis_aggregate (MIS(2)) instead of standard_aggregate; read by extend_hierarchy
+    bool evolution_strength = false; // strength from evolution_strength_of_connection instead of the symmetric measure; read by extend_hierarchy
+    double evolution_epsilon = 4.0;  // its distance filter
     std::vector<sa_level<IndexType, ValueType, MemorySpace>> sa_levels;
 
     smoothed_aggregation() {}
@@ -65,7 +71,7 @@ public:
         initialize(A, B);
     }
     template <typename MemorySpace2>
-    smoothed_aggregation(const smoothed_aggregation<IndexType, ValueType, MemorySpace2> &o) : Parent(o), theta(o.theta), mis_aggregation(o.mis_aggregation)
+    smoothed_aggregation(const smoothed_aggregation<IndexType, ValueType, MemorySpace2> &o) : Parent(o), theta(o.theta), mis_aggregation(o.mis_aggregation), evolution_strength(o.evolution_strength), evolution_epsilon(o.evolution_epsilon)
     {
         for (size_t i = 0; i < o.sa_levels.size(); i++) sa_levels.push_back(sa_level<IndexType, ValueType, MemorySpace>(o.sa_levels[i]));
     }
@@ -97,11 +103,14 @@ private:
         const Csr &A = cur.A_;
         Csr C, T, P, R, RAP;
         cusp::array1d<ValueType, MemorySpace> B_coarse;
-        symmetric_strength_of_connection(A, C, theta);
+        if (evolution_strength) {
+            cur.rho_DinvA = cusp::eigen::estimate_rho_Dinv_A(A);
+            evolution_strength_of_connection(A, C, cur.B, cur.rho_DinvA, evolution_epsilon);
+        } else symmetric_strength_of_connection(A, C, theta);
         if (mis_aggregation) mis_aggregate(C, cur.aggregates);
         else standard_aggregate(C, cur.aggregates);
         fit_candidates(cur.aggregates, cur.B, T, B_coarse);
-        cur.rho_DinvA = cusp::eigen::estimate_rho_Dinv_A(A);
+        if (!evolution_strength) cur.rho_DinvA = cusp::eigen::estimate_rho_Dinv_A(A);
         smooth_prolongator(A, T, P, cur.rho_DinvA);
         form_restriction(P, R);
         galerkin_product(R, A, P, RAP);

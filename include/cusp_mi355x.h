@@ -565,6 +565,40 @@ int cmi_csr_elementwise_f32(int64_t num_rows, int64_t num_cols, int64_t a_entrie
                             float *Cx, int64_t capacity, int *sorted_host, void *stream);
 int cmi_relax_jacobi_presmooth_f64(int64_t n, const double *d, const double *b, double omega, double *x, void *stream);
 int cmi_relax_jacobi_presmooth_f32(int64_t n, const float *d, const float *b, float omega, float *x, void *stream);
+/* Evolution strength of connection (evolution.hip): the reference's evolution_strength_of_connection on the
+ * device, for a square CSR matrix whose pattern is symmetric and whose rows are strictly ascending by column.  The contract
+ * of the block above holds: one lane per value in a stated order, multiply / add / divide rounded separately, no atomics,
+ * row offsets clamped to [0, num_entries] before they address anything, a column outside the matrix addresses no row.
+ * Rejected with CMI_ERROR_INVALID_VALUE before any device call: negative sizes, sizes beyond the CSR ceiling, null arrays
+ * with non-zero sizes, capacity below num_entries, rho_DinvA zero or not finite.  (The calls take no column count: the
+ * matrix is square by construction; cusp::precond::aggregation::evolution_strength_of_connection refuses a non-square one.)
+ *
+ * cmi_csr_transpose_positions: tpos[e] = the position of the entry (col(e), row(e)), found by a binary search of row
+ *   col(e).  The entry count is Ap[num_rows] (read from the device first).  *conforming_host = 1 when the offsets run from 0
+ *   to the entry count without a decrease, every row's columns are strictly ascending and inside the matrix, and every entry
+ *   has its partner; 0 otherwise (found on the device, read once), and then tpos holds nothing defined.  Synchronises.
+ * cmi_csr_masked_product_*: out[e] = the sum of Vx[p] * Wx[q] over the columns that rows row(e) and col(e) have in common,
+ *   p and q being the two positions: one merge of the two rows in ascending column order, the sum started from +0, product
+ *   and sum rounded separately.  With Wx[q] = Vx[tpos[q]] this is the square of the matrix sampled on its own pattern.
+ *   Rows are assumed ascending by column (otherwise the merge is still the reference's, over whatever order is stored); a
+ *   column outside the matrix gives 0.  One lane owns an entry's whole chain; a wave owns 64 consecutive entries and stages
+ *   the rows they lie in (columns and values) in LDS once: rows of up to 64 entries in one piece, a longer row in chunks of
+ *   192 entries while each lane keeps its place in its own partner row.  The entry count is Ap[num_rows] (read from the
+ *   device first: the one synchronisation); nothing is allocated.
+ * cmi_csr_evolution_strength_*: S = the measure of cusp/precond/aggregation/strength.h (its steps 1 to 19) for a given
+ *   non-zero rho_DinvA and the candidate vector B (num_rows values): the kept entries in storage order with their final
+ *   values s[e].  *conforming_host = 0: the pattern does not conform (as above) and nothing was written.  epsilon equal to
+ *   the value type's infinity skips the distance filter.  Allocates scratch (one block), releases it on every path out and
+ *   synchronises.  capacity >= num_entries. */
+int cmi_csr_transpose_positions(int64_t num_rows, const int32_t *Ap, const int32_t *Aj, int32_t *tpos, int *conforming_host, void *stream);
+int cmi_csr_masked_product_f64(int64_t num_rows, const int32_t *Ap, const int32_t *Aj, const double *Vx, const double *Wx, double *out, void *stream);
+int cmi_csr_masked_product_f32(int64_t num_rows, const int32_t *Ap, const int32_t *Aj, const float *Vx, const float *Wx, float *out, void *stream);
+int cmi_csr_evolution_strength_f64(int64_t num_rows, int64_t num_entries, const int32_t *Ap, const int32_t *Aj, const double *Ax, const double *B,
+                                   double rho_DinvA, double epsilon, int32_t *Sp, int32_t *Sj, double *Sx, int64_t capacity,
+                                   int *conforming_host, void *stream);
+int cmi_csr_evolution_strength_f32(int64_t num_rows, int64_t num_entries, const int32_t *Ap, const int32_t *Aj, const float *Ax, const float *B,
+                                   double rho_DinvA, double epsilon, int32_t *Sp, int32_t *Sj, float *Sx, int64_t capacity,
+                                   int *conforming_host, void *stream);
 /* A maximal independent set and the aggregation built on it (mis.hip): the reference's parallel
  * cusp::graph::maximal_independent_set and mis_aggregate on the device.  All integer work, exact in any order.  The graph is
  * the stored pattern of a square CSR matrix: every stored entry is an edge whatever its value, columns may repeat, rows may
