@@ -251,7 +251,7 @@ static int csr_to_dia(int64_t rows, int64_t cols, const int *Ap, const int *Aj, 
     if (rows == 0 || ndiag == 0) return CMI_SUCCESS;
     if (!Ap || !Aj || !Ax || !offsets || !slot_map || !values) return fail(CMI_ERROR_INVALID_VALUE, "cmi_csr_to_dia: null array");
     hipStream_t s = as_stream(stream);
-    CMI_HIP(hipMemsetAsync(values, 0, (size_t)pitch * ndiag * sizeof(T), s));
+    CMI_HIP(zero_store(values, pitch * ndiag, s));
     hipLaunchKernelGGL(dia_slot_kernel, dim3((unsigned)ceil_div(ndiag, 256)), dim3(256), 0, s, rows, ndiag, offsets, slot_map);
     hipLaunchKernelGGL((dia_scatter_kernel<T>), dim3(grid_1d(rows * 8)), dim3(256), 0, s, rows, Ap, Aj, Ax, slot_map, pitch, values);
     CMI_LAUNCH_CHECK("csr_to_dia");

@@ -380,7 +380,7 @@ template <typename T> static int spgemm_take(cmi_spgemm *r, int32_t *Cp, int32_t
     if (!Cp || (r->num_entries > 0 && (!Cj || !Cx))) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spgemm_take: null array");
     hipStream_t s = as_stream(stream);
     if (r->Cp) CMI_HIP(hipMemcpyAsync(Cp, r->Cp.get(), (size_t)(r->m + 1) * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    else CMI_HIP(hipMemsetAsync(Cp, 0, (size_t)(r->m + 1) * sizeof(int32_t), s));
+    else CMI_HIP(zero_store(Cp, r->m + 1, s)); // an empty product; a kernel, not a memset node: the call records into a capture (common.h)
     int64_t at = 0;
     for (const cmi_spgemm::piece &q : r->pieces) {
         if (q.count == 0) continue;

@@ -461,7 +461,7 @@ static int spmv_coo(int dtype, int64_t rows, int64_t cols, int64_t nnz, const in
     }
     if (c.kernel == CMI_COO_TILE) { c.kernel = CMI_COO_LANE4; if (c.items_per_thread > 32 || c.items_per_thread < 1) c.items_per_thread = 4; } // unaligned views / no entries: the order-agnostic path
     // y = initialize(y): zero bytes are +0.0 (sequential/multiply/coo_spmv.h:56-57)
-    if (!accumulate) CMI_HIP(hipMemsetAsync(y, 0, (size_t)rows * sizeof(T), s));
+    if (!accumulate) CMI_HIP(zero_store(y, rows, s));
     if (nnz == 0) return CMI_SUCCESS;
     const int block = c.block_size;
     const int steps = c.items_per_thread < 1 ? 1 : c.items_per_thread; // steps per wave interval

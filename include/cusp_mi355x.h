@@ -379,6 +379,7 @@ int cmi_plan_create(int format, int dtype, int64_t num_rows, int64_t num_cols, i
 /* CSR with both structure arrays: cmi_plan_create(CMI_FORMAT_CSR, ...) plus, when asked for, the 16-bit column copy  */
 /* of CMI_CSR_STREAM_C16 -- asked for by cfg->kernel == CMI_CSR_STREAM_C16, or for every AUTO-kernel plan after             */
 /* cmi_set_index_compression(1) (initial value: $CMI_COMPRESS_INDICES).  cmi_plan_config tells whether it was granted.      */
+/* Like cmi_plan_create, this and the two creators below allocate what the plan owns and SYNCHRONISE `stream`.              */
 int cmi_plan_create_csr(int dtype, int64_t num_rows, int64_t num_cols, int64_t num_entries, const int32_t *row_offsets,
                         const int32_t *column_indices, const cmi_config *cfg, void *stream, cmi_plan **plan);
 /* COO with both index arrays (round 4): cmi_plan_create(CMI_FORMAT_COO, ...) whose CSR sub-plan -- row-sorted entries -- is made WITH   */
@@ -481,7 +482,7 @@ int cmi_spmm_csr_f32(int64_t num_rows, int64_t num_cols, int64_t num_entries, co
  *     re-association: bit for bit the host loop's chain (a lone product of -0.0 is stored as +0.0; NaN and Inf propagate).
  * The size of C is not known in advance and the work is done once, so cmi_spgemm_csr_* returns a HANDLE that owns C on
  * the device: read its size with cmi_spgemm_num_entries, copy it into arrays of your own with cmi_spgemm_take_* (Cp has
- * m + 1 elements, Cj and Cx `capacity` >= num_entries; device to device on `stream`, may be called several times), free
+ * m + 1 elements, Cj and Cx `capacity` >= num_entries; device to device on `stream`, no allocation, no synchronisation: the handle must outlive the copies; may be called several times), free
  * it with cmi_spgemm_destroy (NULL: a no-op).
  * cmi_spgemm_csr_* allocates scratch (about 40 + sizeof(value) bytes per product of a slab, 8 bytes per entry of A and
  * per row, all released on every path out) and synchronises the stream, as cmi_coo_sort_by_row_* does.  Method: the
@@ -631,7 +632,7 @@ int cmi_csr_evolution_strength_f32(int64_t num_rows, int64_t num_entries, const 
  *   written).  The last sweep of a round computes undecided rows only and applies the first of the two state lines; one
  *   further launch applies the second, forms the next keys and counts (one integer atomic per wave).  Scratch: 8 bytes per
  *   node for each of two (k == 1) or three key arrays and 4 for the states, ONE device allocation, released on every path out.  More than
- *   num_rows + 1 rounds cannot happen and would return CMI_ERROR_NOT_SUPPORTED.
+ *   num_rows + 1 rounds cannot happen and would return CMI_ERROR_NOT_SUPPORTED.  Synchronises the stream (every round's read does).
  * cmi_csr_mis_aggregate: aggregates from MIS(2).
  *     mis = the stencil of MIS(2) above
  *     key[i] = mis[i] << 31 | i;  key = sweep(key);  key[i] += mis[i] << 31;  key = sweep(key)
@@ -697,16 +698,18 @@ int cmi_csr_mis_aggregate(int64_t num_rows, int64_t num_entries, const int32_t *
  *   of the last-level vertices themselves: the reference gathers row_lengths[0 .. count), the lengths of the FIRST count
  *   vertices of the graph, which is a bug.  num_entries == 0: every level is -1, so vertex 0 after one search.  y is one
  *   reduction of  row length << 32 | index  (an integer minimum).  levels (int32, device, num_rows) is written at the very end.
+ *   Scratch as the search's, one allocation; synchronises the stream (one host read per search).
  * cmi_csr_symmetric_rcm: levels as above from `start`; the vertices ordered by (level, index), vertices the last search did
  *   not reach (level -1) first -- the reference's stable sort_by_key of the levels; permutation[v] = the position of v.  The
  *   order is unique, so the device radix sort of  level + 1 << 32 | index  gives it.  Like the reference this is a LEVEL
  *   ORDERING from a pseudo-peripheral vertex, not a reversed Cuthill-McKee with degree order inside the levels.  *vertex is
- *   the pseudo-peripheral vertex.  Scratch: 28 bytes per vertex plus the sort's, one allocation.
+ *   the pseudo-peripheral vertex.  Scratch: 28 bytes per vertex plus the sort's, one allocation.  Synchronises the stream.
  * cmi_gather_* / cmi_scatter_*:
  *     gather:   out[i] = in[map[i]]  for i < n          scatter:   out[map[i]] = in[i]  for i < n
  *   with map entries in [0, m), m being the length of the array they index.  An entry outside is never used as an address;
  *   after the launch the call returns CMI_ERROR_INVALID_VALUE (one flag read; the other elements have moved).  That a scatter
- *   map holds no value twice is the caller's promise.  out must not be in.  n == 0: success, nothing done.
+ *   map holds no value twice is the caller's promise.  out must not be in.  n == 0: success, nothing done.  The flag is read on the
+ *   host: both calls allocate it and synchronise the stream.
  * Callers find the feature by the symbols (CMI_VERSION is unchanged). */
 int cmi_bfs_levels_per_read(void);
 int cmi_csr_breadth_first_search(int64_t num_rows, int64_t num_entries, const int32_t *Ap, const int32_t *Aj, int64_t src, int mark_levels,
@@ -967,6 +970,9 @@ int cmi_spmv_hyb_dot_plan_f32(const cmi_plan *plan, int64_t ell_pitch, const int
 /* (conversions/dia_to_other.h:109-163, csr_to_other.h:56-70,155-227), done     */
 /* directly in HBM so 1e7..1e8-row inputs do not go through the host.            */
 /* Sizes: N = m*n rows, nnz = 5mn - 2m - 2n.                                     */
+/* The builders and the conversions below launch on `stream` and return: no     */
+/* allocation, no synchronisation, unless the call's own comment says it        */
+/* synchronises (the calls that hand a count or a flag back to the host).        */
 /* ------------------------------------------------------------------------- */
 int64_t cmi_poisson5pt_num_entries(int64_t m, int64_t n);
 /* Rows [row_begin, row_end) of the global matrix with GLOBAL column indices (row-block shard,
@@ -1007,7 +1013,8 @@ int cmi_csr_to_hyb_coo_f32(int64_t num_rows, const int32_t *Ap, const int32_t *A
 /* CSR -> DIA on the device (reference conversions/csr_to_other.h:73-153, there with Thrust sorts):   */
 /* cmi_csr_diagonals flags the occupied diagonals in slot_map (num_rows + num_cols ints of scratch)  */
 /* and lists their offsets (col - row) UNORDERED in diag_list (at most `capacity`; the true count    */
-/* comes back in *num_diagonals_host -- larger than capacity means "too much fill-in, give up").     */
+/* comes back in *num_diagonals_host -- larger than capacity means "too much fill-in, give up";     */
+/* cmi_csr_diagonals reads it on the host: it synchronises the stream, cmi_csr_to_dia_* does not).   */
 /* The caller sorts the few offsets ascending (the reference's order), uploads them, and             */
 /* cmi_csr_to_dia_* zeroes `values` (pitch x num_diagonals, column-major) and scatters the entries.  */
 int cmi_csr_diagonals(int64_t num_rows, int64_t num_cols, const int32_t *Ap, const int32_t *Aj, int32_t *slot_map,
@@ -1087,6 +1094,8 @@ int cmi_ell_row_lengths(int64_t num_rows, int64_t width, int64_t pitch, const in
 /* dot / nrm2 write their scalar to a DEVICE double (*result_dev) without a     */
 /* host sync; the caller copies it back when it needs the value.                */
 /* `workspace` is a device buffer of cmi_blas_workspace_bytes() bytes.          */
+/* No call of this section (down to cmi_csr_diagonal_*) allocates or             */
+/* synchronises: launches only, scalars read from device memory by the kernels.  */
 /* ------------------------------------------------------------------------- */
 size_t cmi_blas_workspace_bytes(void);
 int cmi_blas_axpy_f64(int64_t n, double alpha, const double *x, double *y, void *stream);  /* y += a x */
@@ -1232,7 +1241,9 @@ int cmi_blas_scal_recip_f32(int64_t n, const void *s_dev, int s_is_squared_norm,
  * The element arithmetic is the reference's (one multiply and one add per update, unfused).
  * rr_host_mirror (may be NULL): cmi_malloc_host memory that also receives <r, r> -- written by the
  * reduction's last workgroup, so the convergence check needs no copy; read it after an event
- * recorded behind this call has been synchronised. */
+ * recorded behind this call has been synchronised.
+ * No call from here to cmi_blas_dotd_f32 allocates or synchronises; the partial counts the fold-ahead forms hand back are
+ * functions of the sizes and the plan, not device reads. */
 int cmi_cg_update_f64(int64_t n, const double *rz_dev, const double *yp_dev, const double *p, const double *y,
                       double *x, double *r, double *rr_dev, double *rr_host_mirror, void *workspace, void *stream);
 int cmi_cg_direction_f64(int64_t n, const double *rr_new_dev, const double *rr_old_dev, const double *r,
