@@ -204,6 +204,7 @@ def _declare(L):
     L.cmi_plan_wavev_shift_tiles.argtypes = [vp, POINTER(c_int64)]
     L.cmi_set_index_compression.argtypes = [c_int]
     L.cmi_plan_hyb_launches.argtypes = [vp, POINTER(c_int)]
+    L.cmi_plan_set_row_scale.argtypes = [vp, vp]
     L.cmi_plan_create_hyb.argtypes = [c_int, i64, i64, i64, i64, vp, cfgp, cfgp, vp, POINTER(c_void_p)]
     for suf in ("f64", "f32"):
         getattr(L, f"cmi_spmv_hyb_plan_{suf}").argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp]
@@ -1160,6 +1161,21 @@ def set_index_compression(on):
 
 def get_index_compression():
     return bool(lib().cmi_get_index_compression())
+
+
+def plan_set_row_scale(plan, scale):
+    """cmi_plan_set_row_scale: every later multiply through the one-launch HYB plan stores y[i] = (A x)[i] * scale[i] (one more multiply, rounded
+    on its own: the bits of spmv_hyb_plan followed by blas_xmy); None clears it.  The plan keeps the pointer: `scale` (num_rows device values of
+    the plan's type) is held by the Plan object so that it outlives the multiplies, and its values may be changed in place.  CmiError
+    NOT_SUPPORTED for any plan that is not a HYB plan with hyb_launches() == 1, INVALID_VALUE for plan None."""
+    import torch
+    if plan is not None and scale is not None:
+        want = torch.float64 if plan.dtype == F64 else torch.float32
+        if not scale.is_cuda or scale.dtype != want or scale.numel() != plan.num_rows or not scale.is_contiguous():
+            raise ValueError("plan_set_row_scale: scale must be a contiguous device vector of num_rows values of the plan's value type")
+    check(lib().cmi_plan_set_row_scale(None if plan is None else plan.handle, _ptr(scale)))
+    if plan is not None:
+        plan._row_scale = scale
 
 
 def spmv_hyb_plan(plan, pitch, ell_Aj, ell_Ax, coo_Ai, coo_Aj, coo_Ax, x, y, accumulate=False, stream=None):

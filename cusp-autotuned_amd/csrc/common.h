@@ -449,6 +449,9 @@ struct cmi_plan {
     cmi_config hyb_coo_cfg = {};
     cmi::device_array<int32_t> hyb_tile_start; // tiles + 1 entries; empty: two launches
     cmi_plan *hyb_coo_plan = nullptr;  // two launches: the COO half's own plan (sorted: row offsets + CSR kernels, accumulating)
+    // cmi_plan_set_row_scale (the one field written after creation): the caller's device array of `rows` values of the plan's type, not owned;
+    // set only on a plan that multiplies in one launch of hyb_tile_kernel, which then stores y[i] = (A x)[i] * row_scale[i]
+    const void *row_scale = nullptr;
     // COO whose entries are sorted by row (plan.hip): the row offsets the row indices imply (num_rows + 1 ints, built once) and
     // the CSR plan for them -- the multiply then runs the CSR kernels on (offsets, Aj, Ax) and never reads the row indices:
     // 12 nnz + 20 N bytes instead of 16 nnz + 16 N, storage-order sums, long rows handled as CSR handles them

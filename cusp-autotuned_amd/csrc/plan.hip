@@ -841,6 +841,17 @@ CMI_API int cmi_plan_hyb_launches(const cmi_plan *plan, int *launches)
     return CMI_SUCCESS;
 }
 
+// y[i] = (A x)[i] * scale[i] for every later multiply through this plan (NULL: plain again).  Launches nothing and reads nothing on the device;
+// only the plans whose multiply is ONE launch of hyb_tile_kernel take it (tile ranges, or an empty COO part).
+CMI_API int cmi_plan_set_row_scale(cmi_plan *plan, const void *scale_dev)
+{
+    if (!plan) return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_set_row_scale: null plan");
+    if (plan->format != CMI_FORMAT_HYB || !(plan->hyb_tile_start || plan->hyb_coo == 0))
+        return fail(CMI_ERROR_NOT_SUPPORTED, "cmi_plan_set_row_scale: only a HYB plan that multiplies in one launch carries a row scale");
+    plan->row_scale = scale_dev;
+    return CMI_SUCCESS;
+}
+
 CMI_API int cmi_plan_wavev_shift_tiles(const cmi_plan *plan, int64_t *marked)
 {
     if (!plan || !marked) return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_wavev_shift_tiles: null argument");

@@ -496,13 +496,19 @@ static int spmv_coo(int dtype, int64_t rows, int64_t cols, int64_t nnz, const in
 // 256 at a time, marks where each row's run begins and ends, and every lane adds its run to the same accumulator in entry
 // order.  y is written once, with the bits of the host loops.  Bytes: ELL part + 16 per COO entry + 16 per row + 4 per tile.
 // DOT: the workgroup also leaves sum_r y[r] * w[r] over its rows in dot_partial[tile] (the CG step <A p, p>, as csr_stream DOT).
-template <typename T, int POL, bool ACC, bool DOT = false>
+// SCALE (cmi_plan_set_row_scale; never with ACC): y[row] = chain * dscale[row] -- one more multiply by the row's lane, rounded on its own, the bits
+// of the multiply followed by cmi_blas_xmy_*; the dot then takes the scaled y.  dscale[row] is requested with the row's first loads (coalesced,
+// one element per lane), so it is in a register long before the chain ends.  A SCALE launch also serves a plan without tile ranges (an empty
+// COO part: tile_start == nullptr, every tile's range is empty).  Instances without SCALE are what they were before the parameter existed.
+template <typename T, int POL, bool ACC, bool DOT = false, bool SCALE = false>
 __global__ void __launch_bounds__(kHybTileRows)
 hyb_tile_kernel(int64_t num_rows, int width, int64_t pitch, const int *__restrict__ eAj, const T *__restrict__ eAx,
                 const int *__restrict__ cAi, const int *__restrict__ cAj, const T *__restrict__ cAx,
                 const int32_t *__restrict__ tile_start, const T *__restrict__ x, T *__restrict__ y, int64_t tiles,
-                int64_t tiles_per_xcd, int swizzle, const T *__restrict__ w = nullptr, double *__restrict__ dot_partial = nullptr)
+                int64_t tiles_per_xcd, int swizzle, const T *__restrict__ w = nullptr, double *__restrict__ dot_partial = nullptr,
+                const T *__restrict__ dscale = nullptr)
 {
+    static_assert(!(SCALE && ACC), "a row scale replaces y, it does not accumulate");
     __shared__ double dot_slots[DOT ? kHybTileRows / kWave : 1];
     constexpr bool NT = (POL & kPolLoadNT) != 0, NTS = (POL & kPolStoreNT) != 0;
     constexpr int R = kHybTileRows;
@@ -514,7 +520,16 @@ hyb_tile_kernel(int64_t num_rows, int width, int64_t pitch, const int *__restric
     const int tid = threadIdx.x;
     const int64_t row0 = tile * R, row = row0 + tid;
     const bool live = row < num_rows;
-    const int cb = tile_start[tile], ce = tile_start[tile + 1];
+    int cb, ce;
+    if constexpr (SCALE) {
+        cb = tile_start ? tile_start[tile] : 0;
+        ce = tile_start ? tile_start[tile + 1] : 0;
+    } else {
+        cb = tile_start[tile];
+        ce = tile_start[tile + 1];
+    }
+    T ds = T(1);
+    if constexpr (SCALE) ds = dscale[live ? row : 0]; // (x-like reuse across applies: a plain load)
     // the first COO chunk's loads go out before the ELL walk (they do not depend on it)
     int ci = 0, cj = 0;
     T cv = T(0);
@@ -583,6 +598,7 @@ hyb_tile_kernel(int64_t num_rows, int width, int64_t pitch, const int *__restric
             ci = ni; cj = nj; cv = nv; cx = nx;
         }
     }
+    if constexpr (SCALE) acc = acc * ds;
     if (live) st<NTS>(y + row, acc);
     if constexpr (DOT) {
         tile_dot_store(live ? (double)acc * (double)w[row] : 0.0, dot_slots, dot_partial + tile);
@@ -634,7 +650,9 @@ static int spmv_hyb_plan(const cmi_plan *plan, int dtype, int64_t pitch, const i
     if (!plan || plan->format != CMI_FORMAT_HYB || plan->dtype != dtype)
         return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_hyb_plan: null plan, or a plan made for another format or value type");
     const int64_t rows = plan->rows, width = plan->hyb_width, coo = plan->hyb_coo;
-    if (!plan->hyb_tile_start) { // COO part empty or not sorted by row: the two launches of cmi_spmv_hyb_*
+    const T *scale = static_cast<const T *>(plan->row_scale); // set only on plans that run hyb_tile_kernel (cmi_plan_set_row_scale)
+    if (scale && accumulate) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_hyb_plan: a plan with a row scale does not accumulate");
+    if (!plan->hyb_tile_start && !scale) { // COO part empty or not sorted by row: the two launches of cmi_spmv_hyb_*
         int st;
         if constexpr (std::is_same<T, double>::value) st = cmi_spmv_ell_f64(rows, plan->cols, width, pitch, eAj, eAx, nullptr, x, y, accumulate, &plan->cfg, stream);
         else st = cmi_spmv_ell_f32(rows, plan->cols, width, pitch, eAj, eAx, nullptr, x, y, accumulate, &plan->cfg, stream);
@@ -644,10 +662,21 @@ static int spmv_hyb_plan(const cmi_plan *plan, int dtype, int64_t pitch, const i
     }
     if (rows == 0) return CMI_SUCCESS;
     if (width > 0 && pitch < rows) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_hyb_plan: pitch < num_rows");
-    if (!y || !x || (width > 0 && (!eAj || !eAx)) || !cAi || !cAj || !cAx) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_hyb_plan: null array");
+    if (!y || !x || (width > 0 && (!eAj || !eAx)) || (coo > 0 && (!cAi || !cAj || !cAx))) return fail(CMI_ERROR_INVALID_VALUE, "cmi_spmv_hyb_plan: null array");
     tile_launch g;
     if (int st = tile_launch_for(ceil_div(rows, kHybTileRows), plan->cfg.xcd_swizzle, "cmi_spmv_hyb_plan", &g)) return st;
     hipStream_t s = as_stream(stream);
+    if (scale) { // y <- (A x) .* scale in the same launch (the plan has tile ranges, or an empty COO part and none)
+        const bool dot = d.fits(g.tiles);
+        with_policy(plan->cfg.nontemporal & 3, [&](auto P) {
+            constexpr int POL = decltype(P)::value;
+            if (dot) hipLaunchKernelGGL((hyb_tile_kernel<T, POL, false, true, true>), dim3(g.grid), dim3(kHybTileRows), 0, s, rows, (int)width, pitch, eAj, eAx, cAi, cAj, cAx, plan->hyb_tile_start.get(), x, y, g.tiles, g.tiles_per_xcd, g.swizzle, d.w, d.partial, scale);
+            else     hipLaunchKernelGGL((hyb_tile_kernel<T, POL, false, false, true>), dim3(g.grid), dim3(kHybTileRows), 0, s, rows, (int)width, pitch, eAj, eAx, cAi, cAj, cAx, plan->hyb_tile_start.get(), x, y, g.tiles, g.tiles_per_xcd, g.swizzle, (const T *)nullptr, (double *)nullptr, scale);
+        });
+        CMI_LAUNCH_CHECK("hyb tile spmv, row scale");
+        if (dot) d.left(g.tiles);
+        return CMI_SUCCESS;
+    }
     if (!accumulate && d.fits(g.tiles)) { // (the dot instance does not accumulate)
         with_policy(plan->cfg.nontemporal & 3, [&](auto P) {
             constexpr int POL = decltype(P)::value;

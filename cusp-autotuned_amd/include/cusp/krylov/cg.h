@@ -17,7 +17,12 @@
 #include "detail/multiply_dot.h"
 
 namespace cusp {
-namespace precond { template <typename ValueType, typename MemorySpace> class diagonal; }
+namespace precond {
+template <typename ValueType, typename MemorySpace> class diagonal;
+template <typename ValueType, typename MemorySpace> class scaled_bridson_ainv;
+template <typename ValueType, typename MemorySpace> class bridson_ainv;
+template <typename ValueType, typename MemorySpace> class nonsym_bridson_ainv;
+} // namespace precond
 namespace krylov {
 
 namespace detail {
@@ -28,6 +33,11 @@ template <typename M> struct is_identity : std::false_type {};
 template <typename V, typename S, typename I> struct is_identity<cusp::identity_operator<V, S, I>> : std::true_type {};
 template <typename V, typename S, typename I> struct is_identity<const cusp::identity_operator<V, S, I>> : std::true_type {};
 template <typename T> using not_policy = typename std::enable_if<!is_policy<T>::value>::type;
+// the approximate-inverse preconditioners of cusp/precond/ainv.h on device_memory with the solver's value type (cg's fused branch for them)
+template <typename M, typename T> struct is_device_ainv : std::false_type {};
+template <typename T> struct is_device_ainv<cusp::precond::scaled_bridson_ainv<T, cusp::device_memory>, T> : std::true_type {};
+template <typename T> struct is_device_ainv<cusp::precond::bridson_ainv<T, cusp::device_memory>, T> : std::true_type {};
+template <typename T> struct is_device_ainv<cusp::precond::nonsym_bridson_ainv<T, cusp::device_memory>, T> : std::true_type {};
 
 // z <- M r for a matrix-like preconditioner or a linear operator with operator()
 template <typename M, typename X, typename Y> auto apply(const M &m, const X &x, Y &y, int) -> decltype(m(x, y), void()) { m(x, y); }
@@ -187,6 +197,42 @@ void cg_fused_jacobi_device(const LinearOperator &A, VectorType1 &x, const Vecto
     cusp::detail::check(cmi_device_synchronize()); // the discarded SpMV must not outlive y
 }
 
+// M = one of the approximate-inverse preconditioners (cusp/precond/ainv.h) on device_memory: the same schedule with z STORED.  The update is
+// cmi_cg_update_* with x == NULL and <r,z> in the numerator slot (r <- r - alpha y and <r,r> for the monitor, into the pinned mirror); the apply's
+// last multiply is multiply_dot(w_t, t, z, r, <r,z>), so <r,z> costs no launch; cmi_cg_direction_x_* takes z in the slot of r (x <- x + alpha p,
+// p <- z + beta p).  Five launches (SpMV + dot, update, the apply's two multiplies, direction) and one host read per iteration, against cg_plain's
+// operation by operation with three host reads.  No new vector kernel: the existing ones take these operands as pointers.
+template <typename LinearOperator, typename VectorType1, typename VectorType2, typename Monitor, typename Ainv>
+void cg_fused_ainv_device(const LinearOperator &A, VectorType1 &x, const VectorType2 &b, Monitor &monitor, const Ainv &M)
+{
+    typedef typename LinearOperator::value_type T;
+    const size_t N = A.num_rows;
+    cusp::array1d<T, cusp::device_memory> y(N), r(N), p(N), z(N);
+    cusp::array1d<double, cusp::device_memory> scalars(4); // <r,z>[0], <r,z>[1], <y,p>, <r,r>
+    cusp::blas::detail::device_workspace &w = cusp::blas::detail::workspace();
+    double *rz[2] = {scalars.data(), scalars.data() + 1};
+    double *yp = scalars.data() + 2, *rr = scalars.data() + 3;
+    pinned_scalar rr_host;
+    cusp::multiply(A, x, y);
+    cusp::blas::axpby(b, y, r, T(1), T(-1));
+    M.apply_dot(r, z, rz[0], w.ws);                                   // z <- M r, <r, z>
+    cusp::blas::copy(z, p);
+    cusp::detail::check(by_type<T>(cmi_blas_dot_f64, cmi_blas_dotd_f32)(N, r.data(), r.data(), rr, w.ws, nullptr));
+    rr_host.fetch(rr);
+    int cur = 0;
+    for (;;) {
+        multiply_dot(A, p, y, p, yp, w.ws); // the hot path, speculative: y <- A p, *yp <- <y, p>
+        if (monitor.finished_norm(static_cast<typename Monitor::Real>(std::sqrt(rr_host.wait())))) break; // the one host read
+        cusp::detail::check(by_type<T>(cmi_cg_update_f64, cmi_cg_update_f32)(N, rz[cur], yp, nullptr, y.data(), nullptr, r.data(), rr, rr_host.host, w.ws, nullptr));
+        rr_host.record();
+        M.apply_dot(r, z, rz[cur ^ 1], w.ws);
+        cusp::detail::check(by_type<T>(cmi_cg_direction_x_f64, cmi_cg_direction_x_f32)(N, rz[cur ^ 1], rz[cur], yp, z.data(), p.data(), x.data(), nullptr));
+        cur ^= 1;
+        ++monitor;
+    }
+    cusp::detail::check(cmi_device_synchronize()); // the discarded SpMV must not outlive y
+}
+
 template <typename LinearOperator, typename VectorType1, typename VectorType2, typename Monitor, typename Preconditioner>
 void cg_plain(const LinearOperator &A, VectorType1 &x, const VectorType2 &b, Monitor &monitor, Preconditioner &M);
 
@@ -205,6 +251,10 @@ void cg(const LinearOperator &A, VectorType1 &x, const VectorType2 &b, Monitor &
         const char *e = std::getenv("CMI_CG_FUSED_JACOBI");
         if (e && e[0] == '0') detail::cg_plain(A, x, b, monitor, M); // (measurements: the operation-by-operation path)
         else detail::cg_fused_jacobi_device(A, x, b, monitor, M);
+    } else if constexpr (eligible && detail::is_device_ainv<typename std::remove_const<Preconditioner>::type, T>::value) {
+        const char *e = std::getenv("CMI_CG_FUSED_AINV");
+        if (e && e[0] == '0') detail::cg_plain(A, x, b, monitor, M); // (measurements and tests: the operation-by-operation path)
+        else detail::cg_fused_ainv_device(A, x, b, monitor, M);
     } else {
         detail::cg_plain(A, x, b, monitor, M);
     }

@@ -415,6 +415,14 @@ int cmi_plan_create_hyb(int dtype, int64_t num_rows, int64_t num_cols, int64_t e
 /* entries per row on average, no 256-row tile holding more than 4096 -- or empty) or 2 (ELL kernel, then a COO kernel        */
 /* accumulating: heavy or unsorted COO parts).  $CMI_HYB_ONE_LAUNCH=0/1 at plan creation overrides the weight rule.           */
 int cmi_plan_hyb_launches(const cmi_plan *plan, int *launches);
+/* A row scale carried by a one-launch HYB plan: every later multiply through it (cmi_spmv_hyb_plan_*, cmi_spmv_hyb_dot_plan_*) stores  */
+/* y[i] = s_i * scale[i], where s_i is the row's unchanged chain (from +0, the ELL slots in slot order, then the row's COO entries in    */
+/* entry order) and the product is one more multiply rounded on its own: the bits of the multiply followed by cmi_blas_xmy_*, without   */
+/* that pass and its launch; the fused dot takes the scaled y.  The plan keeps the POINTER (num_rows values of the plan's value type in  */
+/* device memory), not a copy: the caller keeps the array alive and may change its values between multiplies.  NULL clears the scale.    */
+/* Launches nothing, hence no stream.  CMI_ERROR_NOT_SUPPORTED, plan unchanged: any plan that is not a HYB plan with                    */
+/* cmi_plan_hyb_launches == 1.  CMI_ERROR_INVALID_VALUE: a NULL plan; and, from the multiply, accumulate != 0 through a scaled plan.     */
+int cmi_plan_set_row_scale(cmi_plan *plan, const void *scale_dev);
 int cmi_plan_destroy(cmi_plan *plan);
 /* Have the arrays the plan was made from changed since?  One streaming pass over them on the device (an order-sensitive    */
 /* 64-bit checksum, compared with the one taken at creation); SYNCHRONISES `stream`.  *valid_host: 1 same contents, 0 edited  */
