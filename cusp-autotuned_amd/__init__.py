@@ -17,7 +17,7 @@ from .binding import (  # noqa: F401
     F64, F32,
     KERNEL_AUTO, CSR_SCALAR, CSR_VECTOR, CSR_STREAM, CSR_STREAM_PIPE, CSR_BALANCED, CSR_STREAM_C16, CSR_STREAM_WAVE, CSR_STREAM_WAVEV, CSR_STREAM_WAVEX, CSR_STREAM_WAVER, CSR_STREAM_PACKED, POLICY_COLS16, ELL_ROW, DIA_ROW, COO_SEGMENTED, COO_LANE4, COO_TILE, CSR_SPMM_ROWS, CSR_SPMM_COLS,
     lib, lib_path, build, version, check,
-    Plan, spmv_csr_plan, spmv_coo_plan, spmv_hyb_plan, plan_set_row_scale, set_index_compression, get_index_compression,
+    Plan, spmv_csr_plan, spmv_coo_plan, spmv_hyb_plan, plan_set_row_scale, plan_drop_const_tiles, set_index_compression, get_index_compression,
     spmv_csr, spmm_csr, spgemm_csr, spgemm_limits, spgemm_set_workspace, spmv_csr_axpby, csr_jacobi_sweep, relax_jacobi_update, csr_gauss_seidel_colour, spmv_csr_dot, spmv_ell_dot, spmv_dia_dot, spmv_ell, spmv_dia, spmv_coo, spmv_hyb,
     count_zeros, tuning_hyb_rule, tuning_set_hyb_rule, hyb_entries_per_row, HYB_RULE_REFERENCE, HYB_RULE_COST, HYB_RULE_COST2, tuning_hyb_light_speed, tuning_set_hyb_light_speed, tuning_waver_rule, tuning_set_waver_rule, WaverRule,
     tuning_select, tuning_set, tuning_load, tuning_save, tuning_clear,

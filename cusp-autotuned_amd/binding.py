@@ -205,6 +205,8 @@ def _declare(L):
     L.cmi_set_index_compression.argtypes = [c_int]
     L.cmi_plan_hyb_launches.argtypes = [vp, POINTER(c_int)]
     L.cmi_plan_set_row_scale.argtypes = [vp, vp]
+    L.cmi_plan_const_tiles.argtypes = [vp, POINTER(c_int64)]
+    L.cmi_plan_drop_const_tiles.argtypes = [vp]
     L.cmi_plan_create_hyb.argtypes = [c_int, i64, i64, i64, i64, vp, cfgp, cfgp, vp, POINTER(c_void_p)]
     for suf in ("f64", "f32"):
         getattr(L, f"cmi_spmv_hyb_plan_{suf}").argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, vp]
@@ -824,7 +826,9 @@ class Plan:
     @classmethod
     def csr_values(cls, num_rows, num_cols, Ap, Aj, Ax, cfg=None, stream=None):
         """cmi_plan_create_csr_values: Plan.csr plus the values -- with cfg.kernel == CSR_STREAM_PACKED the plan copies pieces AND values into
-        one span per wave tile (the plan then owns a copy of the values: validate_values tells whether they have changed since)."""
+        one span per wave tile (the plan then owns a copy of the values: validate_values tells whether they have changed since).  With cfg None
+        (or an AUTO kernel) a plan that keeps csr_wavev's shift table also marks its CONSTANT tiles (const_tiles()): marks only, the values are
+        read live; after a non-uniform in-place edit of the values ask validate_values and drop_const_tiles() if it says False."""
         import torch
         self = cls.__new__(cls)
         self._h = c_void_p()
@@ -839,7 +843,8 @@ class Plan:
         return self
 
     def validate_values(self, values, stream=None):
-        """cmi_plan_validate_values: False when a CSR_STREAM_PACKED plan's copy of the values no longer matches `values`."""
+        """cmi_plan_validate_values: False when a CSR_STREAM_PACKED plan's copy of the values no longer matches `values`, or when a tile the
+        plan marked constant no longer has identical rows in `values`."""
         ok = c_int(-1)
         check(lib().cmi_plan_validate_values(self._h, _ptr(values), _stream(stream), byref(ok)))
         return bool(ok.value)
@@ -855,6 +860,16 @@ class Plan:
         n = c_int64()
         check(lib().cmi_plan_wavev_shift_tiles(self._h, byref(n)))
         return n.value
+
+    def const_tiles(self):
+        """cmi_plan_const_tiles: the wave tiles multiplied from their first row's values alone; 0 when the plan keeps no marks."""
+        n = c_int64()
+        check(lib().cmi_plan_const_tiles(self._h, byref(n)))
+        return n.value
+
+    def drop_const_tiles(self):
+        """cmi_plan_drop_const_tiles: frees the marks; the plan then multiplies as one made without the values."""
+        check(lib().cmi_plan_drop_const_tiles(self._h))
 
     @classmethod
     def hyb(cls, dtype, num_rows, num_cols, width, coo_row_indices, cfg_ell=None, cfg_coo=None, stream=None):
@@ -901,11 +916,16 @@ class Plan:
 
     def info(self):
         """dict: max_row_length, entries_in_long_rows (CSR; -1 otherwise), coo_sorted (COO: True/False, else None),
-        storage_order_sums (every result bit-identical to the host loop?)."""
+        storage_order_sums (every result bit-identical to the host loop?) and -- only while the plan keeps constant-tile marks --
+        constant_tiles (const_tiles(); a plan without marks has no such key: info().get("constant_tiles", 0))."""
         a, b, s, e = c_int64(), c_int64(), c_int(), c_int()
         check(lib().cmi_plan_info(self._h, byref(a), byref(b), byref(s), byref(e)))
-        return {"max_row_length": a.value, "entries_in_long_rows": b.value,
-                "coo_sorted": None if s.value < 0 else bool(s.value), "storage_order_sums": bool(e.value)}
+        out = {"max_row_length": a.value, "entries_in_long_rows": b.value,
+               "coo_sorted": None if s.value < 0 else bool(s.value), "storage_order_sums": bool(e.value)}
+        const = self.const_tiles()
+        if const:
+            out["constant_tiles"] = const
+        return out
 
 
 def spmv_csr_plan(plan, Ap, Aj, Ax, x, y, accumulate=False, stream=None):
@@ -1176,6 +1196,11 @@ def plan_set_row_scale(plan, scale):
     check(lib().cmi_plan_set_row_scale(None if plan is None else plan.handle, _ptr(scale)))
     if plan is not None:
         plan._row_scale = scale
+
+
+def plan_drop_const_tiles(plan):
+    """cmi_plan_drop_const_tiles (no stream: it launches nothing).  CmiError INVALID_VALUE for plan None."""
+    check(lib().cmi_plan_drop_const_tiles(None if plan is None else plan.handle))
 
 
 def spmv_hyb_plan(plan, pitch, ell_Aj, ell_Ax, coo_Ai, coo_Aj, coo_Ax, x, y, accumulate=False, stream=None):

@@ -474,6 +474,13 @@ struct cmi_plan {
     // copy and only when at least a quarter of the tiles that have entries are marked (wavev_cols16_build); empty otherwise.
     cmi::device_array<int32_t> wavev_shift;
     int64_t wavev_shift_marked = 0;   // marked tiles (0 without the table)
+    int64_t wavev_tiles_with_entries = 0; // ... and the tiles that have entries, counted with them (what both keep rules compare against)
+    // ... and, only on a plan made WITH the values under an AUTO config (cmi_plan_create_csr_values), the CONSTANT tiles' marks: one bit per wave
+    // tile (word wt / 32, bit wt % 32), set on a marked tile above whose rows all hold the first row's values bit for bit.  The multiply then
+    // reads that one row of the caller's values instead of the tile's stream; no value is copied.  Kept iff constant tiles >= 1/4 of the tiles
+    // that have entries (wavev_const_build); cmi_plan_drop_const_tiles frees them (the other field written after creation).
+    cmi::device_array<uint32_t> wavev_const;
+    int64_t wavev_const_tiles = 0;    // constant tiles (0 without the marks)
     // order-sensitive 64-bit checksums of the arrays the plan was made from (cmi_plan_validate): the index array (CSR row offsets, COO /
     // HYB-COO row indices) and -- when the plan owns data derived from them (the 16-bit copy) -- the CSR column indices
     uint64_t fp_index = 0, fp_columns = 0;
@@ -503,6 +510,10 @@ constexpr int kHybFusedMaxInTile = 4096;
 // spmv_csr16.hip: the plan's 16-bit column copy (built only if every tile qualifies) and the multiply that reads it
 int wave_partition_build(cmi_plan *p, const int *Ap, int k, hipStream_t s, int q_override = 0); // spmv_csr.hip (q_override: entries per tile, csr_wavev)
 int wavev_cols16_build(cmi_plan *p, const int *Aj, hipStream_t s); // spmv_csr.hip: the 16-bit column copy on that partition (sets cfg.nontemporal & 8 when granted)
+// spmv_csr.hip: the constant tiles' marks of a plan that kept the shift table (build: sets / frees wavev_const; check: *valid = 0 when a tile
+// whose bit is set no longer has identical rows in `values`).  Both synchronise `s`.
+int wavev_const_build(cmi_plan *p, const void *values, hipStream_t s);
+int wavev_const_check(const cmi_plan *p, const void *values, hipStream_t s, int *valid);
 int csr16_build(cmi_plan *p, const int *Ap, const int *Aj, hipStream_t s, int wave_k = 0);
 // spmv_csr_runs.hip: the plan's run-compressed column copy (+ the packed tiles when `values` is given) and the multiply that reads it
 int csr_runs_build(cmi_plan *p, const int *Ap, const int *Aj, int v, double min_mean_piece, const void *values, hipStream_t s, double *mean_piece, int cap = 0);

@@ -364,20 +364,30 @@ CMI_API int cmi_plan_create_coo(int dtype, int64_t num_rows, int64_t num_cols, i
 }
 
 // CSR with the structure arrays AND the values: cmi_plan_create_csr plus -- asked for by cfg->kernel == CMI_CSR_STREAM_PACKED -- the packed
-// per-tile copy of pieces and values (spmv_csr_runs.hip).  The values of any other plan stay the caller's.
+// per-tile copy of pieces and values (spmv_csr_runs.hip).  The values of any other plan stay the caller's.  With non-NULL values, a plan that
+// ends up with csr_wavev's shift table (an AUTO or NULL config on the stencil route, or CMI_CSR_STREAM_WAVEV asked for with nontemporal bit 8)
+// also gets the CONSTANT tiles' marks (spmv_csr.hip wavev_const_build): marks only, the multiply reads the values live.  Every other explicit
+// config ignores the values as before.
 CMI_API int cmi_plan_create_csr_values(int dtype, int64_t num_rows, int64_t num_cols, int64_t num_entries, const int32_t *row_offsets,
                                        const int32_t *column_indices, const void *values, const cmi_config *cfg, void *stream, cmi_plan **plan_out)
 {
     if (num_entries > 0 && !column_indices) return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_create_csr_values: null column indices");
     const bool packed = cfg && cfg->kernel == CMI_CSR_STREAM_PACKED;
     if (packed && num_entries > 0 && !values) return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_create_csr_values: CMI_CSR_STREAM_PACKED needs the values");
-    return plan_create(CMI_FORMAT_CSR, dtype, num_rows, num_cols, num_entries, row_offsets, column_indices, cfg, stream, plan_out, packed ? values : nullptr);
+    int st = plan_create(CMI_FORMAT_CSR, dtype, num_rows, num_cols, num_entries, row_offsets, column_indices, cfg, stream, plan_out, packed ? values : nullptr);
+    // (the shift table exists on two routes only: the AUTO stencil route, and CMI_CSR_STREAM_WAVEV asked for with nontemporal bit 8)
+    if (st == CMI_SUCCESS && values && (*plan_out)->cfg.kernel == CMI_CSR_STREAM_WAVEV && (*plan_out)->wavev_shift) {
+        st = wavev_const_build(*plan_out, values, as_stream(stream));
+        if (st != CMI_SUCCESS) { (void)cmi_plan_destroy(*plan_out); *plan_out = nullptr; }
+    }
+    return st;
 }
 
 CMI_API int cmi_plan_validate_values(const cmi_plan *plan, const void *values, void *stream, int *valid_host)
 {
     if (!plan || !valid_host) return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_validate_values: null plan or result");
     *valid_host = 1;
+    if (plan->wavev_const) return wavev_const_check(plan, values, as_stream(stream), valid_host); // (never on a PACKED plan: marks come with an AUTO config only)
     if (!plan->has_fp_values) return CMI_SUCCESS;
     if (!values) return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_validate_values: the plan owns a copy of the values; pass them");
     uint64_t fp = 0;
@@ -390,7 +400,7 @@ CMI_API int cmi_plan_device_bytes(const cmi_plan *plan, int64_t *bytes)
 {
     if (!plan || !bytes) return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_device_bytes: null argument");
     int64_t b = (int64_t)(plan->hyb_tile_start.bytes() + plan->coo_offsets.bytes() + plan->wave_row_start.bytes() + plan->wavev_base.bytes() +
-                          plan->wavev_cols16.bytes() + plan->wavev_shift.bytes() + plan->csr16_base.bytes() + plan->csr16_cols.bytes() +
+                          plan->wavev_cols16.bytes() + plan->wavev_shift.bytes() + plan->wavev_const.bytes() + plan->csr16_base.bytes() + plan->csr16_cols.bytes() +
                           plan->runs_start.bytes() + plan->runs_pieces.bytes() + plan->runs_packed.bytes() + plan->csr16_packed.bytes());
     int64_t sub = 0;
     if (plan->hyb_coo_plan && cmi_plan_device_bytes(plan->hyb_coo_plan, &sub) == CMI_SUCCESS) b += sub;
@@ -856,6 +866,23 @@ CMI_API int cmi_plan_wavev_shift_tiles(const cmi_plan *plan, int64_t *marked)
 {
     if (!plan || !marked) return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_wavev_shift_tiles: null argument");
     *marked = plan->wavev_shift ? plan->wavev_shift_marked : 0;
+    return CMI_SUCCESS;
+}
+
+CMI_API int cmi_plan_const_tiles(const cmi_plan *plan, int64_t *tiles)
+{
+    if (!plan || !tiles) return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_const_tiles: null argument");
+    *tiles = plan->wavev_const ? plan->wavev_const_tiles : 0;
+    return CMI_SUCCESS;
+}
+
+// Frees the constant tiles' marks (a plan without them: nothing happens).  Launches nothing; the free waits for the multiplies already
+// enqueued, as any hipFree does.  From here on the plan multiplies exactly as a plan made without the values.
+CMI_API int cmi_plan_drop_const_tiles(cmi_plan *plan)
+{
+    if (!plan) return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_drop_const_tiles: null plan");
+    plan->wavev_const.reset();
+    plan->wavev_const_tiles = 0;
     return CMI_SUCCESS;
 }
 

@@ -676,10 +676,116 @@ int wavev_cols16_build(cmi_plan *p, const int *Aj, hipStream_t s)
     if (flag.host[0] != 0) return CMI_SUCCESS;
     if (shift && !(counts.host[0] >= 1 && 4 * counts.host[0] >= counts.host[1])) shift.reset(); // (too few marked tiles to pay for 32 bytes per tile)
     p->wavev_shift_marked = shift ? (int64_t)counts.host[0] : 0;
+    p->wavev_tiles_with_entries = shift ? (int64_t)counts.host[1] : 0;
     p->wavev_base = std::move(base);
     p->wavev_cols16 = std::move(cols16);
     p->wavev_shift = std::move(shift);
     p->cfg.nontemporal |= kPolCols16;
+    return CMI_SUCCESS;
+}
+
+// CONSTANT tiles (round 27): a tile marked in the shift table whose rows all hold its first row's L values BIT FOR BIT (an integer compare of
+// the words: +0 and -0 differ, NaNs of equal payload are equal, nothing is compared as a float).  One wave per tile, as in the scan above; B is
+// the value type's word.  Sixteen tiles per workgroup: their sixteen bits are ONE 16-bit store -- bit wt % 32 of the 32-bit word wt / 32 the
+// multiply reads -- so the marks need no atomic and no zeroing (the grid covers every half word of the array).
+// Building (`check` null): the bit of a constant tile is set.  Checking (`check` = the plan's marks, `marks` null): only tiles whose bit is
+// set are visited and *bad += those that are constant no more (none, as a rule: no atomic then either).
+template <typename B>
+__global__ void __launch_bounds__(1024)
+wavev_const_scan_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, const int32_t *__restrict__ shift, const B *__restrict__ Ax, int L,
+                        unsigned mul, const uint32_t *__restrict__ check, uint16_t *__restrict__ marks, unsigned long long *__restrict__ bad)
+{
+    __shared__ unsigned bits;
+    const int wave = threadIdx.x / kWave, lane = threadIdx.x & (kWave - 1);
+    const int64_t wt = (int64_t)blockIdx.x * 16 + wave;
+    if (threadIdx.x == 0) bits = 0;
+    __syncthreads();
+    bool visit = wt < wave_tiles && shift[kShiftMaxLen * wt] != INT32_MIN; // (uniform per wave; no early return: the barriers are the workgroup's)
+    if (visit && check) visit = (check[wt >> 5] >> (wt & 31)) & 1u;
+    bool constant = false;
+    if (visit) {
+        const int nz0 = start[2 * wt + 1], nz1 = start[2 * wt + 3]; // nr rows of L entries, fewer than 4096 in all (what the table marks)
+        B first = 0; // lanes k < L: the first row's k-th value
+        if (lane < L) first = Ax[nz0 + lane];
+        bool same = true;
+        for (int e0 = nz0; e0 < nz1; e0 += kWave) { // (uniform bound: every lane takes part in the shuffle of every turn)
+            const int e = e0 + lane;
+            const bool in = e < nz1;
+            const B v = in ? Ax[e] : B(0);
+            const unsigned p = (unsigned)(e - nz0), r = (p * mul) >> 16, k = p - r * (unsigned)L;
+            const B f = __shfl(first, (int)(k & (kShiftMaxLen - 1)));
+            same = same && (!in || v == f);
+        }
+        constant = __all(same);
+    }
+    if (lane == 0 && (check ? visit && !constant : constant)) atomicOr(&bits, 1u << wave); // (LDS)
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (marks) marks[blockIdx.x] = (uint16_t)bits;
+        else if (bits) atomicAdd(bad, (unsigned long long)__popc(bits));
+    }
+}
+
+// *count += the bits set in marks[0 .. words): one atomic per wave that has any
+__global__ void __launch_bounds__(256)
+wavev_const_count_kernel(int64_t words, const uint32_t *__restrict__ marks, unsigned long long *__restrict__ count)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    int n = i < words ? __popc(marks[i]) : 0;
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) n += __shfl_down(n, o);
+    if ((threadIdx.x & (kWave - 1)) == 0 && n) atomicAdd(count, (unsigned long long)n);
+}
+
+// `marks`: ceil(wave_tiles / 32) words, every one of them written; `check`, `bad`: see the kernel
+static hipError_t wavev_const_scan(const cmi_plan *p, const void *values, const uint32_t *check, uint32_t *marks, unsigned long long *bad, hipStream_t s)
+{
+    const int L = (int)p->prof.max_len; // 1..8: the plan keeps the shift table
+    const unsigned grid = 2u * (unsigned)ceil_div(p->wave_tiles, (int64_t)32); // sixteen tiles per workgroup, both halves of the last word
+    uint16_t *half = reinterpret_cast<uint16_t *>(marks);
+    if (p->dtype == CMI_F64)
+        return launch(wavev_const_scan_kernel<unsigned long long>, grid, 1024, 0, s, p->wave_row_start.get(), p->wave_tiles, p->wavev_shift.get(),
+                      static_cast<const unsigned long long *>(values), L, shift_div_mul(L), check, half, bad);
+    return launch(wavev_const_scan_kernel<unsigned>, grid, 1024, 0, s, p->wave_row_start.get(), p->wave_tiles, p->wavev_shift.get(),
+                  static_cast<const unsigned *>(values), L, shift_div_mul(L), check, half, bad);
+}
+
+// Gives `p` (a csr_wavev plan that kept the shift table) the constant tiles' marks of `values`: one pass over the values of the marked tiles,
+// ceil(wave_tiles / 32) words of plan memory.  Kept iff constant tiles >= 1/4 of the tiles that have entries -- the shift table's own rule (a
+// condition, not a measurement): below it the kernel's extra scalar load and branch per tile have too few value streams to take out.  No
+// table, no values, no memory for the marks: nothing is kept, not an error.  Synchronises `s`.
+int wavev_const_build(cmi_plan *p, const void *values, hipStream_t s)
+{
+    p->wavev_const.reset();
+    p->wavev_const_tiles = 0;
+    if (!p->wavev_shift || !values || p->wave_tiles <= 0 || p->prof.max_len < 1 || p->prof.max_len > kShiftMaxLen) return CMI_SUCCESS;
+    const size_t words = (size_t)ceil_div(p->wave_tiles, (int64_t)32);
+    device_array<uint32_t> marks;
+    device_counters<unsigned long long> count;
+    hipError_t e = marks.alloc(words);
+    if (e == hipSuccess) e = count.open(s);
+    if (e == hipSuccess) e = wavev_const_scan(p, values, nullptr, marks.get(), nullptr, s);
+    if (e == hipSuccess) e = launch(wavev_const_count_kernel, (unsigned)ceil_div((int64_t)words, (int64_t)256), 256, 0, s, (int64_t)words, marks.get(), count.dev());
+    if (e == hipSuccess) e = count.fetch(s);
+    if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); return CMI_SUCCESS; }
+    if (e != hipSuccess) return hip_fail(e, "cmi_plan_create_csr_values: constant tiles");
+    if (!(count.host[0] >= 1 && 4 * count.host[0] >= (unsigned long long)p->wavev_tiles_with_entries)) return CMI_SUCCESS;
+    p->wavev_const = std::move(marks);
+    p->wavev_const_tiles = (int64_t)count.host[0];
+    return CMI_SUCCESS;
+}
+
+// *valid = 0 when a tile the plan holds as constant no longer has identical rows in `values` (a plan without marks: untouched).  Synchronises `s`.
+int wavev_const_check(const cmi_plan *p, const void *values, hipStream_t s, int *valid)
+{
+    if (!p->wavev_const || !p->wavev_shift) return CMI_SUCCESS;
+    if (!values) return fail(CMI_ERROR_INVALID_VALUE, "cmi_plan_validate_values: the plan holds constant-tile marks of the values; pass them");
+    device_counters<unsigned long long> count;
+    hipError_t e = count.open(s);
+    if (e == hipSuccess) e = wavev_const_scan(p, values, p->wavev_const.get(), nullptr, count.dev(), s);
+    if (e == hipSuccess) e = count.fetch(s);
+    if (e != hipSuccess) return hip_fail(e, "cmi_plan_validate_values: constant tiles");
+    if (count.host[0] != 0) *valid = 0;
     return CMI_SUCCESS;
 }
 
@@ -783,7 +889,12 @@ csr_wavep_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, const in
 // sum + v[k] x[k] in storage order: the host loop's products in the host loop's order.  A tile of more than 64 rows (L <= 3 at V = 1) has
 // its first turn's x in flight with the streams and loads the x of turn t >= 1 at the top of that turn (the values are in LDS by then).
 // y, the dot and the lanes' rows (lane, lane + 64, ...) are the other tiles'.
-template <typename T, int V, int POL, bool DOT, int L, typename S>
+// CONST (round 27): the plan, made with the values, marked this tile CONSTANT -- every row holds the first row's L values bit for bit
+// (wavev_const_scan_kernel above; one bit per wave tile, fetched by the kernel with a scalar load beside the partition entry).  Such a tile
+// issues NO value stream request and uses NO LDS: the first row's L values come from a wave-uniform address (scalar loads), live from the
+// caller's array, in the batch of the L x loads, and the row lane forms sum + v[k] x[k] with them -- the same products in the same order.
+// Everything else (the turns, accumulate, the dot, the y store) is the body below, unchanged.
+template <typename T, int V, int POL, bool DOT, int L, bool CONST, typename S>
 __device__ __forceinline__ void wavev_rowlane_tile(T *mine, int lane, int rs, int nr, int nz0, int nz1, S sh, const T *__restrict__ Ax,
                                                    const T *__restrict__ x, T *__restrict__ y, int accumulate, const T *__restrict__ w, double &d)
 {
@@ -792,12 +903,17 @@ __device__ __forceinline__ void wavev_rowlane_tile(T *mine, int lane, int rs, in
     constexpr bool NT = (POL & kPolLoadNT) != 0, NTS = (POL & kPolStoreNT) != 0;
     const int fbase = nz0 & ~(E - 1), last = (nz1 - 1) & ~(E - 1);
     val_t v[NL];
-    T xk[L];
+    T xk[L], vk[L];
+    if constexpr (CONST) {
 #pragma unroll
-    for (int k = 0; k < NL; k++) {
-        int e = fbase + (k * kWave + lane) * E;
-        e = e < last ? e : last;
-        v[k] = ld<NT>(reinterpret_cast<const val_t *>(Ax + e));
+        for (int k = 0; k < L; k++) vk[k] = Ax[nz0 + k]; // the first row's values: a wave-uniform address, read live from the caller's array
+    } else {
+#pragma unroll
+        for (int k = 0; k < NL; k++) {
+            int e = fbase + (k * kWave + lane) * E;
+            e = e < last ? e : last;
+            v[k] = ld<NT>(reinterpret_cast<const val_t *>(Ax + e));
+        }
     }
     // The turns of the row loop are the WAVE's (a uniform count, at least one: a marked tile has rows): a lane without a row in a turn
     // walks the tile's last row and stores nothing, so the first turn's x is asked for and used by straight-line code.
@@ -805,9 +921,11 @@ __device__ __forceinline__ void wavev_rowlane_tile(T *mine, int lane, int rs, in
 #pragma unroll
     for (int k = 0; k < L; k++) xk[k] = (x + ((int64_t)rs + sh[k]))[row]; // a uniform base per slot, the row per lane; x is reused: a plain load
     __builtin_amdgcn_sched_barrier(0); // every request of the tile is out before anything waits
+    if constexpr (!CONST) {
 #pragma unroll
-    for (int k = 0; k < NL; k++) *reinterpret_cast<val_t *>(mine + (k * kWave + lane) * E) = v[k]; // 16 bytes per lane, lanes contiguous: no bank conflict
-    __builtin_amdgcn_wave_barrier(); // (compiler only: the hardware runs a wave's LDS instructions in order)
+        for (int k = 0; k < NL; k++) *reinterpret_cast<val_t *>(mine + (k * kWave + lane) * E) = v[k]; // 16 bytes per lane, lanes contiguous: no bank conflict
+        __builtin_amdgcn_wave_barrier(); // (compiler only: the hardware runs a wave's LDS instructions in order)
+    }
     int r0 = 0;
     do {
         const int r = r0 + lane; // this lane's rows are lane, lane + 64, ... as in every other tile
@@ -816,10 +934,15 @@ __device__ __forceinline__ void wavev_rowlane_tile(T *mine, int lane, int rs, in
 #pragma unroll
             for (int k = 0; k < L; k++) xk[k] = (x + ((int64_t)rs + sh[k]))[row];
         }
-        const T *val = mine + (nz0 - fbase) + row * L;
         T sum = accumulate ? y[rs + row] : T(0);
+        if constexpr (CONST) {
 #pragma unroll
-        for (int k = 0; k < L; k++) sum = sum + val[k] * xk[k];
+            for (int k = 0; k < L; k++) sum = sum + vk[k] * xk[k];
+        } else {
+            const T *val = mine + (nz0 - fbase) + row * L;
+#pragma unroll
+            for (int k = 0; k < L; k++) sum = sum + val[k] * xk[k];
+        }
         if (r < nr) {
             st<NTS>(y + rs + r, sum);
             if constexpr (DOT) d += (double)sum * (double)w[rs + r];
@@ -833,7 +956,7 @@ csr_wavev_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t 
                  const int *__restrict__ Aj, const T *__restrict__ Ax, const T *__restrict__ x, T *__restrict__ y, int64_t num_tiles,
                  int64_t tiles_per_xcd, int swizzle, int accumulate, const T *__restrict__ w, double *__restrict__ dot_partial,
                  int uniform_len, const uint16_t *__restrict__ cols16, const int32_t *__restrict__ tile_base, int last_col,
-                 const int32_t *__restrict__ shift)
+                 const int32_t *__restrict__ shift, const uint32_t *__restrict__ const_marks)
 {
     static_assert(C16 || !SH, "the shift-invariant tiles' table belongs to the 16-bit column copy");
     // Request shape: every load instruction of the wave covers ONE contiguous span and every 128-byte line of the streams is requested
@@ -864,11 +987,16 @@ csr_wavev_kernel(const int32_t *__restrict__ start, int64_t wave_tiles, int64_t 
         bool rowlane = false; // (uniform) a marked tile took the row-lane path
         if constexpr (SH) { // (scalar, beside them: this tile's columns are its first row's plus the row)
             shift_t sh = *reinterpret_cast<const shift_t *>(shift + kShiftMaxLen * wt);
-            asm volatile("" : "+s"(sh), "+s"(cbase)); // requested HERE, with the partition entry, not where the branch on them stands
+            unsigned cw = 0; // the 32 tiles' constant marks this tile's bit lies in (null: the plan keeps none)
+            if (const_marks) cw = const_marks[wt >> 5];
+            asm volatile("" : "+s"(sh), "+s"(cbase), "+s"(cw)); // requested HERE, with the partition entry, not where the branch on them stands
             // marked (nr >= 1 rows of uniform_len entries each; 1..8 by the launcher) and inside the arrays and the slots (`fits` below)
             if (sh[0] != INT32_MIN && (int64_t)((nz1 + E - 1) & ~(E - 1)) <= num_entries && nz1 - (nz0 & ~(E - 1)) <= SLOTS)
                 rowlane = with_int<1, 2, 3, 4, 5, 6, 7, 8>(uniform_len, [&](auto LL) {
-                    wavev_rowlane_tile<T, V, POL, DOT, decltype(LL)::value>(prod[wave], lane, rs, nr, nz0, nz1, sh, Ax, x, y, accumulate, w, d);
+                    if ((cw >> (wt & 31)) & 1u) // a constant tile: the first row's values are every row's
+                        wavev_rowlane_tile<T, V, POL, DOT, decltype(LL)::value, true>(prod[wave], lane, rs, nr, nz0, nz1, sh, Ax, x, y, accumulate, w, d);
+                    else
+                        wavev_rowlane_tile<T, V, POL, DOT, decltype(LL)::value, false>(prod[wave], lane, rs, nr, nz0, nz1, sh, Ax, x, y, accumulate, w, d);
                 });
         }
         if (nr > 0 && !rowlane) { // (uniform per wave)
@@ -1709,7 +1837,7 @@ static int launch_wavev(const cmi_config &c, const cmi_plan *plan, int pol, hipS
                     hipLaunchKernelGGL((csr_wavev_kernel<T, decltype(VV)::value, decltype(P)::value, decltype(DOT)::value, cf >= 1, cf == 2>),
                                        dim3(g.grid), dim3(256), 0, s, plan->wave_row_start.get(), plan->wave_tiles, A.nnz, A.Ap, A.Aj, A.Ax, A.x, A.y, g.tiles,
                                        g.tiles_per_xcd, g.swizzle, A.accumulate, d.w, d.partial, uniform_len, plan->wavev_cols16.get(), plan->wavev_base.get(),
-                                       (int)(cols - 1), plan->wavev_shift.get());
+                                       (int)(cols - 1), plan->wavev_shift.get(), plan->wavev_const.get());
                 });
             });
         });

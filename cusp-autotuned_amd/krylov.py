@@ -156,7 +156,7 @@ def _multiply_dot(A, p, y, yp, ws):
     from .matrices import CooMatrix, CsrMatrix, DiaMatrix, EllMatrix, HybMatrix, multiply
     if isinstance(A, CsrMatrix) and p.is_cuda:
         B.spmv_csr_dot(A.num_rows, A.num_cols, A.row_offsets, A.column_indices, A.values, p, y, p, yp, ws,
-                       plan=A.plan() if A.num_entries > 0 else None)
+                       plan=A.multiply_plan() if A.num_entries > 0 else None)
     elif isinstance(A, CooMatrix) and p.is_cuda and A.num_entries > 0:   # sorted entries: the CSR kernel's fused dot on the plan's offsets
         B.spmv_coo_dot_plan(A.plan(), A.row_indices, A.column_indices, A.values, p, y, p, yp, ws)
     elif isinstance(A, HybMatrix) and A.coo.num_entries == 0 and p.is_cuda:   # everything in the ELL part: its fused dot
@@ -202,7 +202,7 @@ def _cg_fused(A, x, b, monitor, ops, spmv, y, r, p, world, group):
     fold_ahead = (world == 1 and isinstance(A, CsrMatrix) and p.is_cuda and A.num_entries > 0 and os.environ.get("CMI_CG_FOLD_AHEAD", "0") == "1")
 
     def spmv_partials():                         # y <- A p; returns the number of <y,p> partials left in the workspace (0: none)
-        return B.spmv_csr_dot_partials(A.plan(), A.row_offsets, A.column_indices, A.values, p, y, p, ops.ws)
+        return B.spmv_csr_dot_partials(A.multiply_plan(), A.row_offsets, A.column_indices, A.values, p, y, p, ops.ws)
 
     def spmv_dot():                              # y <- A p, yp <- <y, p>
         if isinstance(A, ShardedCsr):

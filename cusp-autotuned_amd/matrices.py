@@ -7,6 +7,7 @@ Storage is torch tensors on the HIP device (plumbing for device memory only); ev
 through the C-ABI library -- see binding.py.  The C++ users' equivalent of this file is the
 header-only layer in include/cusp/.
 """
+import os
 from dataclasses import dataclass, field
 
 from . import binding as B
@@ -50,15 +51,22 @@ class CsrMatrix(_Planned):
     values: object
     format = "csr"
 
+    _plan_args = None  # multiply_plan's state: (key, plan with constant-tile marks) or (key, None) = "no marks: plan() serves"
+
+    def _structure_key(self):
+        compress = getattr(self, "_compress", None)
+        return (self.row_offsets.data_ptr(), self.row_offsets._version, self.column_indices.data_ptr(), self.column_indices._version,
+                self.num_rows, self.num_cols, self.num_entries, self.values.dtype,
+                compress if compress is not None else B.get_index_compression())
+
     def plan(self, stream=None, create=True, compress=None):
-        """compress=True asks for the 16-bit column copy (CSR_STREAM_C16; granted only if every tile qualifies -- see
-        plan().config().kernel); None follows set_index_compression()."""
+        """The plan of the STRUCTURE: made from the row offsets and the columns, valid for any values array a caller passes to
+        spmv_csr_plan with it.  compress=True asks for the 16-bit column copy (CSR_STREAM_C16; granted only if every tile qualifies -- see
+        plan().config().kernel); None follows set_index_compression().  The container's own multiplies go through multiply_plan()."""
         if compress is not None:
             self._compress = bool(compress)  # sticky: later multiplies of this matrix keep the choice
         compress = getattr(self, "_compress", None)
-        key = (self.row_offsets.data_ptr(), self.row_offsets._version, self.column_indices.data_ptr(), self.column_indices._version,
-               self.num_rows, self.num_cols, self.num_entries, self.values.dtype,
-               compress if compress is not None else B.get_index_compression())
+        key = self._structure_key()
         if self._plan_key != key:
             if not create:
                 return None
@@ -69,6 +77,53 @@ class CsrMatrix(_Planned):
                 self._plan = B.Plan.csr(self.values.dtype, self.num_rows, self.num_cols, self.row_offsets, self.column_indices, cfg, stream)
             self._plan_key = key
         return self._plan
+
+    def multiply_plan(self, stream=None, create=True):
+        """The plan for multiplies by THIS matrix's own `values` (multiply(), the solvers): with compress unset and $CMI_CSR_CONST_TILES not 0
+        it is made with the values too (cmi_plan_create_csr_values), and where that plan marks constant tiles -- tiles whose rows all hold the
+        same values; such a tile then reads one row of them -- it is kept beside plan()'s, bound to `values`: its key carries the values'
+        address and in-place version.  An edit of `values` through torch is caught here (validated once on `stream`; the marks are dropped
+        if they no longer hold, and the plan goes on multiplying without them); after an edit torch cannot see, call invalidate().  A matrix
+        whose plan marks nothing has ONE plan, plan()'s, and its values are never looked at again.  The state lives in _plan_args, which a
+        copy of the container that resets its plan fields resets too."""
+        if getattr(self, "_compress", None) is not None or os.environ.get("CMI_CSR_CONST_TILES") == "0":
+            return self.plan(stream, create)
+        key = self._structure_key()
+        held = self._plan_args
+        if held is not None and held[0][:len(key)] == key:
+            if held[1] is None:
+                return self.plan(stream, create)
+            vals = (self.values.data_ptr(), self.values._version)
+            if held[0][len(key):] == vals:
+                return held[1]
+            if not create:
+                return None  # (seen while a capture records: the plan-less call runs, nothing is validated there)
+            # the values were edited in place (or replaced): a uniform edit keeps every constant tile constant -- one pass over the marked tiles
+            # tells; otherwise the marks go and the plan stays, multiplying as a plan made without the values
+            if held[1].validate_values(self.values, stream):
+                self._plan_args = (key + vals, held[1])
+                return held[1]
+            held[1].drop_const_tiles()
+            return self._adopt(key, held[1])
+        if not create:
+            return None
+        made = B.Plan.csr_values(self.num_rows, self.num_cols, self.row_offsets, self.column_indices, self.values, None, stream)
+        if made.const_tiles():
+            self._plan_args = (key + (self.values.data_ptr(), self.values._version), made)
+            return made
+        return self._adopt(key, made)
+
+    def _adopt(self, key, made):
+        """`made` holds no marks: it is what plan() makes.  It becomes plan()'s where plan() has none for this structure yet."""
+        if self._plan_key != key:
+            self._plan, self._plan_key = made, key
+        self._plan_args = (key, None)
+        return self._plan
+
+    def invalidate(self):
+        self._plan_key = None
+        self._plan = None
+        self._plan_args = None
 
 
 @dataclass
@@ -192,7 +247,8 @@ def multiply(A, x, y, accumulate=False, cfg=None, stream=None):
         return y
     plan = None
     if isinstance(A, (CsrMatrix, CooMatrix)) and cfg is None and A.num_entries > 0:
-        plan = A.plan(stream, create=not _capturing(stream))  # an existing plan is used inside a capture, none is made there
+        # an existing plan is used inside a capture, none is made there
+        plan = (A.multiply_plan if isinstance(A, CsrMatrix) else A.plan)(stream, create=not _capturing(stream))
     if plan is not None and isinstance(A, CsrMatrix):
         B.spmv_csr_plan(plan, A.row_offsets, A.column_indices, A.values, x, y, accumulate, stream)
     elif plan is not None:

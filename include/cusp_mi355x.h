@@ -388,12 +388,27 @@ int cmi_plan_create_csr(int dtype, int64_t num_rows, int64_t num_cols, int64_t n
 int cmi_plan_create_coo(int dtype, int64_t num_rows, int64_t num_cols, int64_t num_entries, const int32_t *row_indices,
                         const int32_t *column_indices, const cmi_config *cfg, void *stream, cmi_plan **plan);
 /* ... and with the VALUES (device pointer, `dtype` elements): what cmi_plan_create_csr does, plus -- asked for by                    */
-/* cfg->kernel == CMI_CSR_STREAM_PACKED -- the packed per-tile copy of pieces and values.  Any other config: the values are ignored.  */
+/* cfg->kernel == CMI_CSR_STREAM_PACKED -- the packed per-tile copy of pieces and values.  With non-NULL values, a plan that keeps          */
+/* csr_wavev's shift-invariant tiles' table (cmi_plan_wavev_shift_tiles: an AUTO or NULL config on the stencil route, or                    */
+/* CMI_CSR_STREAM_WAVEV asked for with nontemporal bit 8) also MARKS its CONSTANT tiles: marked                                            */
+/* tiles whose rows all hold the tile's first row's values bit for bit (constant-coefficient stencils).  One bit per wave tile, kept when  */
+/* at least a quarter of the tiles that have entries are constant; no value is copied.  The multiply reads ONE row of values of such a     */
+/* tile, live from the caller's array: a uniform in-place edit (every value scaled, a refreshed constant coefficient) is seen at once.     */
+/* A NON-UNIFORM in-place edit makes the plan WRONG until cmi_plan_validate_values has answered or cmi_plan_drop_const_tiles was called.    */
+/* Every other explicit config: the values are ignored.  cmi_config and cmi_plan_config report nothing of the marks.                      */
 int cmi_plan_create_csr_values(int dtype, int64_t num_rows, int64_t num_cols, int64_t num_entries, const int32_t *row_offsets,
                                const int32_t *column_indices, const void *values, const cmi_config *cfg, void *stream, cmi_plan **plan);
-/* Have the VALUES a CMI_CSR_STREAM_PACKED plan copied changed since?  (*valid_host = 1 for every other plan: nothing of the values  */
-/* is kept.)  One streaming pass, synchronises `stream`.                                                                             */
+/* Have the VALUES a CMI_CSR_STREAM_PACKED plan copied changed since?  A plan with constant-tile marks: does every tile marked constant   */
+/* still have identical rows in `values` (0: drop the marks or make a new plan)?  (*valid_host = 1 for every other plan: nothing of the  */
+/* values is kept.)  One streaming pass, synchronises `stream`.                                                                       */
 int cmi_plan_validate_values(const cmi_plan *plan, const void *values, void *stream, int *valid_host);
+/* The wave tiles a plan multiplies from their first row's values alone (0: the plan keeps no marks); their bits are counted by          */
+/* cmi_plan_device_bytes.                                                                                                              */
+int cmi_plan_const_tiles(const cmi_plan *plan, int64_t *tiles);
+/* Frees a plan's constant-tile marks: every later multiply streams every value again, exactly as through a plan made without the        */
+/* values.  A plan without marks: nothing happens.  Launches nothing, hence no stream (the free waits for the device).                   */
+/* CMI_ERROR_INVALID_VALUE: a NULL plan.                                                                                               */
+int cmi_plan_drop_const_tiles(cmi_plan *plan);
 /* Bytes of device memory the plan owns (partitions, offsets, column copies, packed tiles).                                           */
 int cmi_plan_device_bytes(const cmi_plan *plan, int64_t *bytes);
 /* How many wave tiles of a csr_wavev plan that owns the 16-bit column copy (cfg.nontemporal bit 8 in cmi_plan_config) are multiplied   */

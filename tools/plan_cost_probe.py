@@ -18,6 +18,7 @@ H = cmi.convert(A, "hyb", num_entries_per_row=4)
 H1 = cmi.convert(A, "hyb", num_entries_per_row=1)
 x = cmi.fill_x(N, device="cuda")
 y = torch.empty(N, dtype=torch.float64, device="cuda")
+VARYING = A.values * (1.0 + torch.arange(nnz, dtype=torch.float64, device="cuda") / nnz)  # no two rows of a tile alike
 
 
 def wall_us(make, reps=10):
@@ -48,6 +49,8 @@ def mult_us(fn, iters=200):
 rows = [
     ("CSR (row-length profile)", lambda: cmi.Plan(cmi.FORMAT_CSR, torch.float64, N, N, nnz, A.row_offsets), lambda: cmi.multiply(A, x, y)),
     ("CSR with the columns (what the containers make: + partition, + a look at the columns)", lambda: cmi.Plan.csr(torch.float64, N, N, A.row_offsets, A.column_indices), lambda: cmi.multiply(A, x, y)),
+    ("CSR with the columns and the values (what the CSR container makes: + one pass over the marked tiles' values, constant-tile marks kept)", lambda: cmi.Plan.csr_values(N, N, A.row_offsets, A.column_indices, A.values), None),
+    ("CSR with the columns and VARYING values (the same pass, no tile constant: marks freed, the multiply is the plan's without the values)", lambda: cmi.Plan.csr_values(N, N, A.row_offsets, A.column_indices, VARYING), None),
     ("CSR csr_wavev V = 1 asked for, 32-bit columns", lambda: cmi.Plan.csr(torch.float64, N, N, A.row_offsets, A.column_indices, cfg=cmi.Config(kernel=cmi.CSR_STREAM_WAVEV, items_per_thread=1, nontemporal=3)), None),
     ("CSR csr_wavev V = 1 asked for, + its 16-bit column copy (nontemporal bit 8)", lambda: cmi.Plan.csr(torch.float64, N, N, A.row_offsets, A.column_indices, cfg=cmi.Config(kernel=cmi.CSR_STREAM_WAVEV, items_per_thread=1, nontemporal=11)), None),
     ("CSR + 16-bit column copy", lambda: cmi.Plan.csr(torch.float64, N, N, A.row_offsets, A.column_indices, cfg=cmi.Config(kernel=cmi.CSR_STREAM_C16)), None),

@@ -24,6 +24,7 @@ A = cmi.poisson5pt(M, M, "csr")
 x = cmi.fill_x(N, device="cuda")
 y = torch.empty(N, dtype=torch.float64, device="cuda")
 alg = {}
+const_tiles = None
 for fmt in fmts:
     # hyb: width 4 leaves the fifth entry of the interior rows to the COO part (a width of 5 would time ELL alone)
     if fmt == "csr16":  # the opt-in plan with the 16-bit column copy (CMI_CSR_STREAM_C16): same matrix, same arrays
@@ -47,6 +48,8 @@ for fmt in fmts:
     alg[fmt] = {"csr": cmi.csr_bytes(N, A.num_entries), "csr16p": (packed_bytes + 16 * N) if fmt == "csr16p" else 0, "csr16": cmi.csr_bytes(N, A.num_entries) - 2 * A.num_entries, "ell": cmi.ell_bytes(N, 5, 9998272), "dia": cmi.dia_bytes(N, 5, N),
                 "coo": cmi.coo_bytes(N, A.num_entries),
                 "hyb": cmi.ell_bytes(N, 4, 9998272) + 16 * (A.num_entries - 4 * N if fmt != "hyb" else Afmt.coo.num_entries)}[fmt]
+    if fmt == "csr":  # the container's own plan, made with the values as every caller's is: the constant tiles' marks are part of what is measured
+        const_tiles = A.multiply_plan().const_tiles()
     del Afmt
 # calibration: z = 2x + 3y over 2^25 doubles (256 MiB per vector: far beyond the 256 MiB Infinity Cache in total)
 n_cal = 1 << 25
@@ -57,6 +60,6 @@ torch.cuda.synchronize()
 for _ in range(10):
     cmi.blas_axpby(2.0, a, 3.0, b, c)
 torch.cuda.synchronize()
-print(json.dumps({"formats": fmts, "spmv_algorithmic_bytes": alg, "spmv_write_bytes": 8 * N,
+print(json.dumps({"formats": fmts, "spmv_algorithmic_bytes": alg, "spmv_write_bytes": 8 * N, "csr_constant_tiles": const_tiles,
                   "calibration_kernel": "axpby_kernel", "calibration_read_bytes": 16 * n_cal,
                   "calibration_write_bytes": 8 * n_cal}))
